@@ -500,6 +500,31 @@ def cpu_baseline(denoiser, cfg, budget_s=60.0):
     )
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # (64 MB in all, with room for the .npy headers)
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    r"""Writes each tensor as ``dirname/<name>.npy`` (float64 stays float64, everything else becomes float32).  A tensor
+    that would take the dump past DUMP_LIMIT_BYTES is written as ``<name>_sample.npy``: a fixed, seeded choice of its
+    samples (first axis, in index order) that depends only on its shape, with their indices in ``<name>_sample_index.npy``."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        if a.nbytes > budget:
+            keep = max(1, budget // (a[:1].nbytes + 8))
+            idx = np.sort(np.random.default_rng(0).permutation(a.shape[0])[:keep])
+            a, name = a[idx], name + "_sample"
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            budget -= idx.size * 8
+        assert a.nbytes <= budget, f"--dump-outputs: {name} ({a.nbytes} bytes) does not fit the {DUMP_LIMIT_BYTES}-byte dump"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def self_launch(n: int) -> int:
     r"""Re-run this command line as `n` ranks (one per GPU) under `torch.distributed.run` on a free 127.0.0.1 port and
     return its exit code.  Same processes, environment and JSON line as the explicit launcher form of the docstring."""
@@ -532,7 +557,12 @@ def main() -> None:
                     help="how the DIRECT-kernel fp32 convs / GEMMs use the matrix pipe (default: env AZ_FP32_MFMA or bf16x3 = exact "
                          "3-piece bf16 split, 6 partial products, fp32 accumulate; native = v_mfma_f32_32x32x2_f32 everywhere)")
     ap.add_argument("--no-native-line", action="store_true", help="skip the extra native-fp32-MFMA sampling reported beside a bf16x3 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the x0 of the last timed step to DIR/x0.npy (float32, whole node's batch; "
+                         "a seeded sample of its images beyond 60 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.fp32_mfma:
         os.environ["AZ_FP32_MFMA"] = args.fp32_mfma  # read by azula_amd.engine at import
 
@@ -621,6 +651,8 @@ def main() -> None:
         x0 = one_pass()
     fence()
     elapsed = local_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x0": x0})  # before any later pass can reuse the plan's buffers
     if world > 1:
         tmax = torch.tensor([elapsed], device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
