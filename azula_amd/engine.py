@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -136,9 +137,10 @@ class Act:
         # activation operand has a stated range (|x| < ~1e6, include/azula_amd.h), are chosen only for bounded inputs; residual /
         # input streams (which grow with x_t: an unstable multistep sampler reaches 1e7 in tests/test_gpu_unet.py) go through
         # the bf16x3 kernels, whose domain is all of fp32.  Default False: unknown = unbounded.
+        # Set by Builder.wrote (and view()).  Content facts below end in the serial of the write they describe (Builder.fact).
         self.bounded = False
-        self.absmax = None  # AZ_ABSMAX_SLOTS floats written by az_absmax_f32 over this tensor on the tape so far (Builder.absmax_of), or None
-        self.gn_quads = None  # (partials tensor, chunks per image): GroupNorm moments written by the producing conv
+        self.absmax = None  # (AZ_ABSMAX_SLOTS floats written by az_absmax_f32 / ..._from_moments_f32, serial): Builder.absmax_of
+        self.gn_quads = None  # (partials tensor, chunks per image, serial): GroupNorm moments written by the producing conv
         self.qk_prepared = False  # a fused qkv projection whose q / k are already normalised / gained / rotated (AzConvArgs.act = 5)
         self.affine = None    # ([scale | shift] tensor, act): a normalisation whose apply pass has not run -- the values are
         #                       act(buf * scale + shift); Builder.conv evaluates it inside the Winograd gather or materialises it
@@ -146,6 +148,16 @@ class Act:
     @property
     def ptr(self) -> int:
         return self.buf.data_ptr()
+
+    def view(self, B: int | None = None, H: int | None = None, W: int | None = None, C_: int | None = None, cs: int | None = None,
+             *, buf: torch.Tensor | None = None, pinned: bool = True, bounded: bool | None = None, gn_quads: tuple | None = None) -> "Act":
+        r"""Another shape over this allocation (``buf``: a slice of it).  Carries ``bounded``; carries GroupNorm moments only as the
+        record the caller passes, re-chunked for the new shape -- content facts of the old shape do not describe the new one."""
+        v = Act(self.buf if buf is None else buf, self.B if B is None else B, self.H if H is None else H, self.W if W is None else W,
+                self.C if C_ is None else C_, self.cs if cs is None else cs, pinned)
+        v.bounded = self.bounded if bounded is None else bounded
+        v.gn_quads = gn_quads
+        return v
 
 
 # Winograd for stride-1 3x3 convs (see conv.hip): "1" = exact F(2x2,3x3) where it pays (default), "0" = never,
@@ -202,6 +214,100 @@ GN_FUSED_SPLITK = os.environ.get("AZ_GN_FUSED", "1") != "epilogue"  # ("epilogue
 
 
 WINO_X3_NAMES = ("az_conv2d_winograd_x3_f32", "az_conv2d_winograd_f16x2_f32")  # wino_x3.hip: the piece forms of the Winograd kernel
+H2_NAMES = ("az_conv2d_winograd_f16x2_f32", "az_conv2d_f16x2_f32")
+PACKED = {"az_conv2d_winograd4_f32": "winograd4", "az_conv2d_winograd_f32": "winograd", "az_conv2d_winograd_x3_f32": "winograd_x3",  # ConvWeights
+          "az_conv2d_winograd_f16x2_f32": "winograd_f16x2", "az_conv2d_x3_f32": "direct_x3", "az_conv2d_f16x2_f32": "direct_f16x2",
+          "az_conv2d_f32": "direct"}
+# Builder.conv(winograd=...): None = the policy below; False / 0 = never Winograd, True / 1 / 2 = Winograd where legal, 4 = F(4x4,3x3);
+# "x3" / "wx3": the bf16x3 kernels, "h2" / "wh2": the f16x2 ones, "h2d" / "wh2d": those with the activation scale measured from the
+# sources (az_absmax_f32), whatever the mode ("w...": the Winograd form) -- kernel tests
+CONV_OVERRIDES = (None, False, True, 0, 1, 2, 4, "x3", "wx3", "h2", "wh2", "h2d", "wh2d")
+
+
+# What the kernel choice reads of one source of a convolution: its real channels, the elements of its buffer (what an az_absmax_f32
+# pass streams), Act.bounded, a pending normalisation (Act.affine), and whether a maximum (Builder.absmax_of) / its producer's
+# GroupNorm moments (Act.gn_quads) of its current contents are recorded
+ConvSource = NamedTuple("ConvSource", [("C", int), ("numel", int), ("bounded", bool), ("affine", bool), ("absmax", bool), ("moments", bool)])
+# ... and of the convolution: geometry (aniso: a stride / upsampling per axis), channel strides, one depth tap of a 3-D convolution,
+# Builder.half, the winograd= override (CONV_OVERRIDES) and the sources
+ConvLayer = NamedTuple("ConvLayer", [
+    ("ks", int), ("stride", int), ("aniso", bool), ("B", int), ("hout", int), ("wout", int), ("c0s", int), ("c1s", int), ("cout", int),
+    ("cout_s", int), ("up0", int), ("depth", bool), ("half", "torch.dtype | None"), ("winograd", object), ("src0", ConvSource),
+    ("src1", "ConvSource | None")])
+# the C entry, the f16x2 form (H2_NAMES), with the activation scale from the sources' maxima (AzConvArgs.in_absmax0 / in_absmax1)
+ConvChoice = NamedTuple("ConvChoice", [("name", str), ("h2", bool), ("dyn", bool)])
+
+
+def sources_bounded(src0, src1) -> bool:
+    r"""Every source of a convolution (Act or ConvSource) bounded; a pending normalisation is applied in the gather / materialised."""
+    return bool(src0.bounded or src0.affine) and (src1 is None or src1.bounded)
+
+
+def choose_conv(l: ConvLayer) -> ConvChoice:
+    r"""Kernel and arithmetic of one convolution.  Pure: reads the module switches at call time (bench.py flips FP32_MFMA between
+    plans), calls nothing on the device."""
+    w = l.winograd
+    if w not in CONV_OVERRIDES:
+        raise ValueError(f"winograd={w!r}: one of {CONV_OVERRIDES}")
+    srcs = [s for s in (l.src0, l.src1) if s is not None]
+    cin_s = l.c0s + l.c1s
+    # (half-precision modules: the direct bf16 / f16 kernel; one factor per axis: the direct kernel's loaders only)
+    legal = l.ks == 3 and l.stride == 1 and not l.aniso and l.half is None
+    # image head (<= 4 output channels) on a map that fills the chip with 16 x 16-pixel workgroups:
+    # az_conv2d_f32 runs its narrow-output VALU kernel (104 vs 342 us at 4 x 256^2, 256 -> 3)
+    head = (w is None and legal and l.cout_s == 4 and l.src1 is None and l.up0 == 0 and l.c0s % 16 == 0
+            and l.B * ((l.hout + 15) // 16) * ((l.wout + 15) // 16) >= 256 and not l.depth)
+    wino_ok = legal and not head and w not in ("x3", "h2", "h2d")
+    tiles4 = l.B * ((l.hout + 3) // 4) * ((l.wout + 3) // 4)
+    use_f4 = wino_ok and not l.depth and (w == 4 or (w is None and WINOGRAD == "4" and tiles4 >= WINOGRAD4_MIN_TILES))
+    use_wino = wino_ok and not use_f4 and ((WINOGRAD != "0") if w is None else bool(w))
+    if use_wino and w is None and WINOGRAD in ("1", "4") and l.B * ((l.hout + 1) // 2) * ((l.wout + 1) // 2) < 64:
+        use_wino = False  # less than one 64-tile block (measured: 8x8 at batch < 4): the direct kernel wins
+    # bf16x3 mode replaces the DIRECT fp32 kernel (1x1 convs / token GEMMs, stride 2, small maps: 147-181 vs 113-128
+    # TF/s); the 3x3 stride-1 layers stay on the fp32 Winograd kernel, which executes 2.25x fewer multiplies
+    # (221 vs 181 TF/s algorithmic at 4 x 256^2, 256 -> 256).
+    use_x3 = l.half is None and (
+        w in ("x3", "h2", "h2d")
+        or (w is None and pieces() and not head and not use_wino and not use_f4 and cin_s >= X3_MIN_CHANNELS and l.cout_s >= X3_MIN_CHANNELS)
+    )
+    h2 = w in ("h2", "wh2", "h2d", "wh2d") or (w not in ("x3", "wx3") and FP32_MFMA == "f16x2" and sources_bounded(l.src0, l.src1))
+    dyn = w in ("h2d", "wh2d")
+    if (not h2 and w is None and FP32_MFMA == "f16x2" and F16X2_DYNAMIC and l.half is None and not l.depth
+            and (use_wino or use_x3) and not use_f4 and not any(s.affine for s in srcs)):
+        # unbounded sources: f16x2 with the scale measured per step, where the pass over the sources costs clearly less than the
+        # matrix instructions it saves (~12 % of a Winograd layer at ~350 TF/s algorithmic, ~25 % of a direct one at ~190);
+        # never on a pending normalisation (its maximum is not that of the stored tensor)
+        flops = 2.0 * l.B * l.hout * l.wout * l.cout * sum(s.C for s in srcs) * l.ks * l.ks
+        gain_s = 0.12 * flops / 350e12 if use_wino else 0.25 * flops / 190e12
+        cost_s = sum(4e-6 + (0.0 if (s.moments and F16X2_MOMENTS) else s.numel * 4 / 5.0e12) for s in srcs if not s.absmax)
+        dyn = h2 = gain_s > 1.5 * cost_s
+    if use_f4:
+        name = "az_conv2d_winograd4_f32"
+    elif use_wino and l.wout >= 3 and (w in ("wx3", "wh2", "wh2d") or (w is None and WINO_X3 and pieces())):
+        # the frequency GEMMs on the bf16 pipe as exact 3 x bf16 splits (wino_x3.hip); same descriptor, 16-channel steps
+        # (f16x2: the same kernel with two half pieces per operand and three products)
+        name = "az_conv2d_winograd_f16x2_f32" if h2 else "az_conv2d_winograd_x3_f32"
+    elif use_wino:
+        name = "az_conv2d_winograd_f32"
+    elif use_x3:
+        name = "az_conv2d_f16x2_f32" if h2 else "az_conv2d_x3_f32"
+    elif l.half is not None:
+        name = "az_conv2d_f16_f32" if l.half == torch.float16 else "az_conv2d_bf16_f32"
+    else:
+        name = "az_conv2d_f32"
+    h2 = name in H2_NAMES
+    return ConvChoice(name, h2, dyn and h2)
+
+
+def choose_attention(dim: int, bounded: bool, half: torch.dtype | None) -> str:
+    r"""C entry of an attention layer (head size ``dim``, ``bounded`` q | k | v, Builder.half); reads the switches at call time."""
+    if half is not None:  # module cast to half precision: contractions on the bf16 / f16 MFMA
+        return "az_attention_f16_f32" if half == torch.float16 else "az_attention_bf16_f32"
+    if pieces() and ATTN_X3 and dim in (16, 32, 64, 80):
+        # the two contractions as 3 x bf16 pieces / 6 partial products: fp32 accuracy, 0.375 x the pipe time (64 x 12 heads x 256
+        # tokens x 64: 140 -> 111 us; head_dim 128 needs one wave per SIMD there and measured slower, 458 vs 516 us: fp32 kernel)
+        return "az_attention_f16x2_f32" if FP32_MFMA == "f16x2" and ATTN_H2 and bounded else "az_attention_x3_f32"
+    return "az_attention_f32"
 
 
 class ConvWeights:
@@ -236,53 +342,43 @@ class ConvWeights:
         if bias is not None:
             self.bias = torch.zeros(self.cout_s, dtype=torch.float32, device=bld.device)
             self.bias[: self.cout] = bias.detach().to(device=bld.device, dtype=torch.float32)
-        self._direct = self._wino = self._wino4 = self._x3 = self._h2 = self._wino_h2 = None
-        self._half: dict = {}
+        self._forms: dict = {}  # packed layouts, made on first use
         self._amax = None
+
+    def _form(self, key, numel: int, dtype: torch.dtype, pack: str, *args) -> torch.Tensor:
+        r"""The layout ``key``: a (numel,) tensor written by the C packing entry ``pack(dst, w, *args, stream)``, made once."""
+        if key not in self._forms:
+            t = torch.empty(numel, dtype=dtype, device=self.device)
+            _lib.call(pack, t.data_ptr(), self.w.data_ptr(), *args, _lib.stream_ptr())
+            self._forms[key] = t
+        return self._forms[key]
+
+    def _direct_args(self, pieces: int) -> tuple:
+        cin_s = self.c0s + self.c1s
+        return pieces * self.ks * self.ks * self.cout_s * cin_s, (self.cout, self.cin, self.ks, self.cout_s, self.cin0, self.c0s, cin_s)
 
     def direct(self) -> torch.Tensor:
         r"""[tap][cout_s][cin_s] (K contiguous), zero padded (az_pack_conv_weight_f32)."""
-        if self._direct is None:
-            cin_s = self.c0s + self.c1s
-            packed = torch.empty(self.ks * self.ks * self.cout_s * cin_s, dtype=torch.float32, device=self.device)
-            _lib.call(
-                "az_pack_conv_weight_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.ks,
-                self.cout_s, self.cin0, self.c0s, cin_s, _lib.stream_ptr(),
-            )
-            self._direct = packed
-        return self._direct
+        n, args = self._direct_args(1)
+        return self._form("direct", n, torch.float32, "az_pack_conv_weight_f32", *args)
 
     def stem(self) -> torch.Tensor:
         r"""(3, 3, cin, cout_s): tap-major, output channels contiguous (``az_conv2d_stem_f32``)."""
-        if getattr(self, "_stem", None) is None:
+        if "stem" not in self._forms:
             w = torch.zeros(self.ks, self.ks, self.cin, self.cout_s, dtype=torch.float32, device=self.device)
             w[..., : self.cout] = self.w.permute(2, 3, 1, 0)
-            self._stem = w.contiguous()
-        return self._stem
+            self._forms["stem"] = w.contiguous()
+        return self._forms["stem"]
 
     def direct_half(self, f16: bool) -> torch.Tensor:
         r"""The direct layout in bf16 (``f16=False``) or IEEE half, for ``az_conv2d_{bf16,f16}_f32``."""
-        if f16 not in self._half:
-            cin_s = self.c0s + self.c1s
-            packed = torch.empty(self.ks * self.ks * self.cout_s * cin_s, dtype=torch.int16, device=self.device)
-            _lib.call(
-                "az_pack_conv_weight_half_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.ks,
-                self.cout_s, self.cin0, self.c0s, cin_s, int(f16), _lib.stream_ptr(),
-            )
-            self._half[f16] = packed
-        return self._half[f16]
+        n, args = self._direct_args(1)
+        return self._form(("half", f16), n, torch.int16, "az_pack_conv_weight_half_f32", *args, int(f16))
 
     def direct_x3(self) -> torch.Tensor:
         r"""The direct layout as three bf16 planes (w = w1 + w2 + w3 exactly), for ``az_conv2d_x3_f32``."""
-        if self._x3 is None:
-            cin_s = self.c0s + self.c1s
-            packed = torch.empty(3 * self.ks * self.ks * self.cout_s * cin_s, dtype=torch.int16, device=self.device)
-            _lib.call(
-                "az_pack_conv_weight_x3_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.ks,
-                self.cout_s, self.cin0, self.c0s, cin_s, _lib.stream_ptr(),
-            )
-            self._x3 = packed
-        return self._x3
+        n, args = self._direct_args(3)
+        return self._form("x3", n, torch.int16, "az_pack_conv_weight_x3_f32", *args)
 
     def w_scale(self, winograd: bool) -> float:
         r"""The power of two the f16x2 packings multiply the weights by (``az_f16x2_weight_scale``: the largest magnitude -- of
@@ -293,71 +389,37 @@ class ConvWeights:
 
     def direct_f16x2(self) -> torch.Tensor:
         r"""The direct layout as three IEEE half planes [wh | wl | wh / 2^11] of w * w_scale, for ``az_conv2d_f16x2_f32``."""
-        if self._h2 is None:
-            cin_s = self.c0s + self.c1s
-            packed = torch.empty(3 * self.ks * self.ks * self.cout_s * cin_s, dtype=torch.int16, device=self.device)
-            _lib.call(
-                "az_pack_conv_weight_f16x2_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.ks,
-                self.cout_s, self.cin0, self.c0s, cin_s, self.w_scale(False), _lib.stream_ptr(),
-            )
-            self._h2 = packed
-        return self._h2
+        n, args = self._direct_args(3)
+        return self._form("h2", n, torch.int16, "az_pack_conv_weight_f16x2_f32", *args, self.w_scale(False))
+
+    def _wino_args(self, step: int, pieces: int) -> tuple:
+        nk0, nk1 = (self.c0s + step - 1) // step, (self.c1s + step - 1) // step
+        cb = (self.cout_s + 63) // 64
+        return (nk0 + nk1) * cb * 16 * 64 * step * pieces, (self.cout, self.cin, self.cin0, nk0, nk0 + nk1, cb)
 
     def winograd_f16x2(self) -> torch.Tensor:
         r"""The x3 Winograd filter layout with the f16x2 pieces of U * w_scale, for ``az_conv2d_winograd_f16x2_f32``."""
-        if self._wino_h2 is None:
-            nk0, nk1 = (self.c0s + 15) // 16, (self.c1s + 15) // 16
-            cb = (self.cout_s + 63) // 64
-            packed = torch.empty((nk0 + nk1) * cb * 16 * 64 * 16 * 3, dtype=torch.int16, device=self.device)
-            _lib.call(
-                "az_winograd_pack_filter_f16x2_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.cin0,
-                nk0, nk0 + nk1, cb, self.w_scale(True), _lib.stream_ptr(),
-            )
-            self._wino_h2 = packed
-        return self._wino_h2
+        n, args = self._wino_args(16, 3)
+        return self._form("wino_h2", n, torch.int16, "az_winograd_pack_filter_f16x2_f32", *args, self.w_scale(True))
 
     def winograd(self) -> torch.Tensor:
         r"""Filter transform U = G g G^T (az_winograd_pack_filter_f32: fp64 accumulate, one-off) laid out
         [8-channel chunk][64-cout block][16 frequencies][64][8]; source 1 starts on a chunk boundary."""
-        if self._wino is None:
-            nk0, nk1 = (self.c0s + 7) // 8, (self.c1s + 7) // 8
-            cb = (self.cout_s + 63) // 64
-            packed = torch.empty((nk0 + nk1) * cb * 16 * 64 * 8, dtype=torch.float32, device=self.device)
-            _lib.call(
-                "az_winograd_pack_filter_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.cin0,
-                nk0, nk0 + nk1, cb, _lib.stream_ptr(),
-            )
-            self._wino = packed
-        return self._wino
-
+        n, args = self._wino_args(8, 1)
+        return self._form("wino", n, torch.float32, "az_winograd_pack_filter_f32", *args)
 
     def winograd_x3(self) -> torch.Tensor:
         r"""The same filter transform as three bf16 pieces in MFMA fragment order, 16-channel steps
         (az_winograd_pack_filter_x3_f32), for ``az_conv2d_winograd_x3_f32``; source 1 starts on a step boundary."""
-        if getattr(self, "_wino_x3", None) is None:
-            nk0, nk1 = (self.c0s + 15) // 16, (self.c1s + 15) // 16
-            cb = (self.cout_s + 63) // 64
-            packed = torch.empty((nk0 + nk1) * cb * 16 * 64 * 16 * 3, dtype=torch.int16, device=self.device)
-            _lib.call(
-                "az_winograd_pack_filter_x3_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.cin0,
-                nk0, nk0 + nk1, cb, _lib.stream_ptr(),
-            )
-            self._wino_x3 = packed
-        return self._wino_x3
+        n, args = self._wino_args(16, 3)
+        return self._form("wino_x3", n, torch.int16, "az_winograd_pack_filter_x3_f32", *args)
 
     def winograd4(self) -> torch.Tensor:
         r"""F(4x4,3x3) filter transform (az_winograd4_pack_filter_f32) laid out
         [4-channel chunk][64-cout block][36 frequencies][64][4]."""
-        if self._wino4 is None:
-            nk = (self.c0s + self.c1s) // 4
-            cb = (self.cout_s + 63) // 64
-            packed = torch.empty(nk * cb * 36 * 64 * 4, dtype=torch.float32, device=self.device)
-            _lib.call(
-                "az_winograd4_pack_filter_f32", packed.data_ptr(), self.w.data_ptr(), self.cout, self.cin, self.cin0,
-                self.c0s, nk, cb, _lib.stream_ptr(),
-            )
-            self._wino4 = packed
-        return self._wino4
+        nk, cb = (self.c0s + self.c1s) // 4, (self.cout_s + 63) // 64
+        return self._form("wino4", nk * cb * 36 * 64 * 4, torch.float32, "az_winograd4_pack_filter_f32",
+                          self.cout, self.cin, self.cin0, self.c0s, nk, cb)
 
 
 class Builder:
@@ -375,6 +437,8 @@ class Builder:
         self._ws_need = 0
         self._ws_users: list[AzConvArgs] = []
         self.workspace: torch.Tensor | None = None
+        self._writes = 0  # launches that reported a write (Builder.wrote) so far
+        self._last_write: dict[int, int] = {}  # allocation (storage address) -> serial of its last write
 
     # -- buffers ---------------------------------------------------------------------------
     def pad(self, c: int) -> int:
@@ -443,10 +507,8 @@ class Builder:
         # (height, width) pairs select the anisotropic descriptor (a stride sequence such as (2, 1), unet.py:159-186)
         (stride, stride_w), (up0, up0_w), (up1, up1_w) = (v if isinstance(v, (tuple, list)) else (v, v) for v in (stride, up0, up1))
         aniso = stride != stride_w or up0 != up0_w or up1 != up1_w
-        if hin is None:
-            hin = src0.H << up0
-        if win is None:
-            win = src0.W << up0_w
+        hin = src0.H << up0 if hin is None else hin
+        win = src0.W << up0_w if win is None else win
         hout = (hin + 2 * pad - ks) // stride + 1
         wout = (win + 2 * pad - ks) // stride_w + 1
         a = AzConvArgs()
@@ -499,83 +561,23 @@ class Builder:
         npix = B * hout * wout
         cin_s = a.c0s + a.c1s
         lib = _lib.lib()
-        # (half-precision modules: the direct bf16 / f16 kernel; one factor per axis: the direct kernel's loaders only)
-        legal = ks == 3 and stride == 1 and not aniso and self.half is None
-        tiles4 = B * ((hout + 3) // 4) * ((wout + 3) // 4)
-        head_wgs = B * ((hout + 15) // 16) * ((wout + 15) // 16)
-        # image head (<= 4 output channels) on a map that fills the chip with 16 x 16-pixel workgroups:
-        # az_conv2d_f32 runs its narrow-output VALU kernel (104 vs 342 us at 4 x 256^2, 256 -> 3)
-        head = (winograd is None and legal and not aniso and a.cout_s == 4 and src1 is None and up0 == 0 and a.c0s % 16 == 0
-                and head_wgs >= 256 and depth is None)
-        wino_ok = legal and not head and winograd not in ("x3", "h2", "h2d")
-        use_f4 = wino_ok and depth is None and (winograd == 4 or (winograd is None and WINOGRAD == "4" and tiles4 >= WINOGRAD4_MIN_TILES))
-        use_wino = wino_ok and not use_f4 and ((WINOGRAD != "0") if winograd is None else bool(winograd))
-        if use_wino:
-            tiles = B * ((hout + 1) // 2) * ((wout + 1) // 2)
-            a.splitk = lib.az_conv2d_winograd_suggest_splitk(B, hout, wout, a.cout_s, cin_s)
-            if winograd is None and WINOGRAD in ("1", "4") and tiles < 64:
-                use_wino = False  # less than one 64-tile block (measured: 8x8 at batch < 4): the direct kernel wins
-        # bf16x3 mode replaces the DIRECT fp32 kernel (1x1 convs / token GEMMs, stride 2, small maps: 147-181 vs 113-128
-        # TF/s); the 3x3 stride-1 layers stay on the fp32 Winograd kernel, which executes 2.25x fewer multiplies
-        # (221 vs 181 TF/s algorithmic at 4 x 256^2, 256 -> 256).
-        use_x3 = self.half is None and (
-            winograd in ("x3", "h2", "h2d")
-            or (winograd is None and pieces() and not head and not use_wino and not use_f4
-                and cin_s >= X3_MIN_CHANNELS and a.cout_s >= X3_MIN_CHANNELS)
-        )
-        # (winograd = "x3" / "wx3": the bf16x3 kernels, "h2" / "wh2": the f16x2 ones, "h2d" / "wh2d": those with the activation scale
-        #  measured from the sources -- az_absmax_f32 --, whatever the mode: kernel tests)
-        src_bounded = (src0.bounded or src0.affine is not None) and (src1 is None or src1.bounded)  # (a pending normalisation is applied in the gather / materialised)
-        h2 = winograd in ("h2", "wh2", "h2d", "wh2d") or (winograd not in ("x3", "wx3") and FP32_MFMA == "f16x2" and src_bounded)
-        dyn = winograd in ("h2d", "wh2d")
-        if (not h2 and winograd is None and FP32_MFMA == "f16x2" and F16X2_DYNAMIC and self.half is None and depth is None
-                and (use_wino or use_x3) and not use_f4):
-            # unbounded sources: f16x2 with the scale measured per step, where the pass over the sources costs clearly less than the
-            # matrix instructions it saves (~12 % of a Winograd layer at ~350 TF/s algorithmic, ~25 % of a direct one at ~190)
-            flops = 2.0 * npix * cout * (src0.C + (src1.C if src1 is not None else 0)) * ks * ks
-            gain_s = 0.12 * flops / 350e12 if use_wino else 0.25 * flops / 190e12
-            cost_s = sum(4e-6 + (0.0 if (s_.gn_quads is not None and F16X2_MOMENTS) else s_.buf.numel() * 4 / 5.0e12)
-                         for s_ in (src0, src1) if s_ is not None and s_.absmax is None)
-            dyn = h2 = gain_s > 1.5 * cost_s
-        if use_f4:
-            a.weight = packed.winograd4().data_ptr()
+        ch = choose_conv(ConvLayer(ks, stride, aniso, B, hout, wout, a.c0s, a.c1s, cout, a.cout_s, up0, depth is not None, self.half,
+                                   winograd, self._source(src0), self._source(src1) if src1 is not None else None))
+        name = ch.name
+        a.weight = (packed.direct_half(self.half == torch.float16) if self.half is not None else getattr(packed, PACKED[name])()).data_ptr()
+        if ch.h2:
+            a.w_scale = packed.w_scale(name == "az_conv2d_winograd_f16x2_f32")
+        if name == "az_conv2d_winograd4_f32":
             a.splitk = lib.az_conv2d_winograd4_suggest_splitk(B, hout, wout, a.cout_s, cin_s)
-            name = "az_conv2d_winograd4_f32"
-        elif use_wino and wout >= 3 and (winograd in ("wx3", "wh2", "wh2d") or (winograd is None and WINO_X3 and pieces())):
-            # the frequency GEMMs on the bf16 pipe as exact 3 x bf16 splits (wino_x3.hip); same descriptor, 16-channel steps
-            # (f16x2: the same kernel with two half pieces per operand and three products)
-            if h2:
-                a.weight, a.w_scale = packed.winograd_f16x2().data_ptr(), packed.w_scale(True)
-                name = "az_conv2d_winograd_f16x2_f32"
-                if dyn:
-                    a.in_absmax0 = self.absmax_of(src0).data_ptr()
-                    a.in_absmax1 = self.absmax_of(src1).data_ptr() if src1 is not None else None
-            else:
-                a.weight = packed.winograd_x3().data_ptr()
-                name = "az_conv2d_winograd_x3_f32"
-        elif use_wino:
-            a.weight = packed.winograd().data_ptr()
-            name = "az_conv2d_winograd_f32"
-        elif use_x3:
-            if h2:
-                a.weight, a.w_scale = packed.direct_f16x2().data_ptr(), packed.w_scale(False)
-                if dyn:
-                    a.in_absmax0 = self.absmax_of(src0).data_ptr()
-                    a.in_absmax1 = self.absmax_of(src1).data_ptr() if src1 is not None else None
-            else:
-                a.weight = packed.direct_x3().data_ptr()
-            a.splitk = lib.az_conv2d_x3_suggest_splitk(C.byref(a))  # (the 256 x 256-tile kernel has its own rule)
-            name = "az_conv2d_f16x2_f32" if h2 else "az_conv2d_x3_f32"
-        elif self.half is not None:
-            a.weight = packed.direct_half(self.half == torch.float16).data_ptr()
-            a.splitk = lib.az_conv2d_suggest_splitk(npix, a.cout_s, cin_s, ks)
-            if a.c0s % 64 == 0 and a.c1s % 64 == 0:  # (the 256 x 256-tile kernel has its own rule where it takes the launch)
-                a.splitk = lib.az_conv2d_x3_suggest_splitk(C.byref(a))
-            name = "az_conv2d_f16_f32" if self.half == torch.float16 else "az_conv2d_bf16_f32"
+        elif name in ("az_conv2d_winograd_f32", *WINO_X3_NAMES):
+            a.splitk = lib.az_conv2d_winograd_suggest_splitk(B, hout, wout, a.cout_s, cin_s)
+        elif name in ("az_conv2d_x3_f32", "az_conv2d_f16x2_f32") or (self.half is not None and a.c0s % 64 == 0 and a.c1s % 64 == 0):
+            a.splitk = lib.az_conv2d_x3_suggest_splitk(C.byref(a))  # (the 256 x 256-tile kernel has its own rule where it takes the launch)
         else:
-            a.weight = packed.direct().data_ptr()
             a.splitk = lib.az_conv2d_suggest_splitk(npix, a.cout_s, cin_s, ks)
-            name = "az_conv2d_f32"
+        if ch.dyn:
+            a.in_absmax0 = self.absmax_of(src0).data_ptr()
+            a.in_absmax1 = self.absmax_of(src1).data_ptr() if src1 is not None else None
         tmp_src = None
         if src0.affine is not None:  # a normalisation whose apply pass has not run (group_norm(lazy=True))
             ST, in_act = src0.affine
@@ -587,48 +589,26 @@ class Builder:
             else:
                 tmp_src = self.materialize(src0)
                 a.src0 = tmp_src.ptr
-        if (gn_stats and GN_FUSED and name in ("az_conv2d_winograd_f32", *WINO_X3_NAMES) and a.splitk == 1 and out is not None and cout == a.cout_s
-                and cout % 64 == 0 and hout % 2 == 0 and wout % 2 == 0 and ((hout // 2) * (wout // 2)) % 64 == 0):
-            # the output feeds a GroupNorm: its epilogue also writes per-(tile block, channel quad) moments
-            chunks = ((hout // 2) * (wout // 2)) // 64
-            quads = torch.empty(B * chunks * (cout // 4) * 4, dtype=torch.float32, device=self.device)
-            a.gn_quads, a.gn_chunks = quads.data_ptr(), chunks
-            out.gn_quads = (quads, chunks)
-            self.tape.keep.append(quads)
-        elif (gn_stats and GN_FUSED and GN_FUSED_SPLITK and a.splitk > 1 and out is not None and cout == a.cout_s and name != "az_conv2d_winograd4_f32"
-              and not (name == "az_conv2d_f32" and a.cout_s == 4)):
-            # split-K layers (the small maps): the combine kernel leaves the moments, one partial per (image, pixel chunk, quad)
-            hw = hout * wout
-            # a workgroup of the combine kernel = 256 // quads pixel slots; about 2 pixels per thread (each costs splitk
-            # dependent-latency loads: parallelism, not bandwidth, decides), at most 128 partials per image (two finalize passes)
-            cpix = 2 * max(1, 256 // (cout // 4))
-            chunks = max(1, min(128, (hw + cpix - 1) // cpix))
-            while (hw + chunks - 1) // chunks * (chunks - 1) >= hw:
-                chunks -= 1
-            quads = torch.empty(B * chunks * (cout // 4) * 4, dtype=torch.float32, device=self.device)
-            a.gn_quads, a.gn_chunks = quads.data_ptr(), chunks
-            out.gn_quads = (quads, chunks)
-            self.tape.keep.append(quads)
+        moments = None
+        if gn_stats and GN_FUSED and out is not None and cout == a.cout_s:
+            if (name in ("az_conv2d_winograd_f32", *WINO_X3_NAMES) and a.splitk == 1 and cout % 64 == 0 and hout % 2 == 0
+                    and wout % 2 == 0 and ((hout // 2) * (wout // 2)) % 64 == 0):
+                # the output feeds a GroupNorm: its epilogue also writes per-(tile block, channel quad) moments
+                moments = self._moments(a, B, cout, ((hout // 2) * (wout // 2)) // 64)
+            elif GN_FUSED_SPLITK and a.splitk > 1 and name != "az_conv2d_winograd4_f32" and not (name == "az_conv2d_f32" and a.cout_s == 4):
+                # split-K layers (the small maps): the combine kernel leaves the moments, one partial per (image, pixel chunk, quad)
+                hw = hout * wout
+                # a workgroup of the combine kernel = 256 // quads pixel slots; about 2 pixels per thread (each costs splitk
+                # dependent-latency loads: parallelism, not bandwidth, decides), at most 128 partials per image (two finalize passes)
+                cpix = 2 * max(1, 256 // (cout // 4))
+                chunks = max(1, min(128, (hw + cpix - 1) // cpix))
+                while (hw + chunks - 1) // chunks * (chunks - 1) >= hw:
+                    chunks -= 1
+                moments = self._moments(a, B, cout, chunks)
         if (qk_prep is not None and QK_PREP and name in ("az_conv2d_f32", "az_conv2d_bf16_f32", "az_conv2d_f16_f32", "az_conv2d_x3_f32", "az_conv2d_f16x2_f32")
                 and a.splitk == 1 and act == 0 and gate is None and res is None and out is not None and a.cout_s == cout
                 and qk_prep["head_dim"] in (32, 64, 128) and cout == 3 * qk_prep["heads"] * qk_prep["head_dim"]):
-            # the fused q | k | v projection of an attention layer: q / k RMS norm, gains and RoPE in THIS epilogue, once per
-            # layer, instead of in every workgroup of the attention kernel (three per head at 288 tokens: 123 -> 163 us)
-            a.act = 5
-            if name != "az_conv2d_f32" and lib.az_conv2d_x3_suggest_splitk(C.byref(a)) != 1:
-                a.act = 0  # (the tile plan of THIS epilogue wants a split K walk, which the epilogue cannot take: plain projection)
-        if a.act == 5:
-            a.qk_head_dim, a.qk_heads, a.qk_tokens = qk_prep["head_dim"], qk_prep["heads"], hout * wout
-            a.qk_rmsnorm, a.qk_eps = int(qk_prep["rmsnorm"]), qk_prep["eps"]
-            keep = []
-            if qk_prep.get("weight") is not None:
-                a.qk_q_weight, a.qk_k_weight = (t.data_ptr() for t in qk_prep["weight"])
-                keep += list(qk_prep["weight"])
-            if qk_prep.get("rope") is not None:
-                a.qk_rope_cos, a.qk_rope_sin = (t.data_ptr() for t in qk_prep["rope"])
-                keep += list(qk_prep["rope"])
-            self.tape.keep.extend(keep)
-            out.qk_prepared = True
+            self._qk_prep(a, qk_prep, name, hout * wout)
         if a.splitk > 1:
             self._ws_need = max(self._ws_need, a.splitk * npix * a.cout_s)
             self._ws_users.append(a)
@@ -638,9 +618,35 @@ class Builder:
         if tmp_src is not None:
             self.free(tmp_src)
         if out is not None:
-            out.absmax = None  # (a caller-owned destination is rewritten: maxima recorded for its previous contents are stale)
-            out.bounded = src_bounded and (res is None or res.bounded)  # (a residual add of the stream joins the stream; of a bounded tensor -- y + MSA(y) of a DiT block -- stays bounded)
+            # (a residual add of the stream joins the stream; of a bounded tensor -- y + MSA(y) of a DiT block -- stays bounded)
+            self.wrote(out, bounded=sources_bounded(src0, src1) and (res is None or res.bounded), moments=moments)
+            out.qk_prepared = a.act == 5
         return out
+
+    def _source(self, s: Act) -> ConvSource:
+        return ConvSource(s.C, s.buf.numel(), s.bounded, s.affine is not None, self.fact(s, s.absmax) is not None,
+                          self.fact(s, s.gn_quads) is not None)
+
+    def _moments(self, a: AzConvArgs, B: int, cout: int, chunks: int) -> tuple:
+        r"""Per-(image, chunk, channel quad) GroupNorm moments of the output, written by the launch of ``a``."""
+        quads = self.empty(B * chunks * (cout // 4) * 4)
+        a.gn_quads, a.gn_chunks = quads.data_ptr(), chunks
+        return quads, chunks
+
+    def _qk_prep(self, a: AzConvArgs, qk_prep: dict, name: str, tokens: int) -> None:
+        r"""The fused q | k | v projection of an attention layer: q / k RMS norm, gains and RoPE in THIS epilogue, once per
+        layer, instead of in every workgroup of the attention kernel (three per head at 288 tokens: 123 -> 163 us)."""
+        a.act = 5
+        if name != "az_conv2d_f32" and _lib.lib().az_conv2d_x3_suggest_splitk(C.byref(a)) != 1:
+            a.act = 0  # (the tile plan of THIS epilogue wants a split K walk, which the epilogue cannot take: plain projection)
+            return
+        a.qk_head_dim, a.qk_heads, a.qk_tokens = qk_prep["head_dim"], qk_prep["heads"], tokens
+        a.qk_rmsnorm, a.qk_eps = int(qk_prep["rmsnorm"]), qk_prep["eps"]
+        for key, fields in (("weight", ("qk_q_weight", "qk_k_weight")), ("rope", ("qk_rope_cos", "qk_rope_sin"))):
+            if qk_prep.get(key) is not None:
+                for f, t in zip(fields, qk_prep[key]):
+                    setattr(a, f, t.data_ptr())
+                self.tape.keep.extend(qk_prep[key])
 
     def conv_stem(self, x: torch.Tensor, B: int, cin: int, H: int, W: int, packed: "ConvWeights", cout: int, *,
                   periodic: bool = False, gn_stats: bool = False) -> Act:
@@ -656,41 +662,49 @@ class Builder:
         a.pad_mode = 1 if periodic else 0
         out = self.new_act(B, H, W, cout)
         a.dst = out.ptr
-        if gn_stats and GN_FUSED:
-            chunks = ((H + 7) // 8) * ((W + 31) // 32)
-            quads = torch.empty(B * chunks * (cout // 4) * 4, dtype=torch.float32, device=self.device)
-            a.gn_quads, a.gn_chunks = quads.data_ptr(), chunks
-            out.gn_quads = (quads, chunks)
-            self.tape.keep.append(quads)
+        moments = self._moments(a, B, cout, ((H + 7) // 8) * ((W + 31) // 32)) if gn_stats and GN_FUSED else None
         a._flops = 0  # (27 multiplies per output on the vector ALUs: a store-bound pass, accounted by its bytes in bench.py)
         a._algo = "az_conv2d_stem_f32"
         self.tape.add("az_conv2d_stem_f32", C.byref(a), keep=[a, x])
-        return out
+        return self.wrote(out, bounded=False, moments=moments)
+
+    # -- content facts -------------------------------------------------------------------------
+    def wrote(self, y: Act, *, bounded: bool, moments: tuple | None = None) -> Act:
+        r"""Every launch that writes an activation reports here, after it is on the tape.  Facts recorded about the allocation's
+        earlier contents (through any view of it) go stale; ``bounded`` states the producer's rule for the new contents
+        (Act.bounded), ``moments`` the (partials, chunks) GroupNorm record the same launch wrote of them."""
+        self._writes += 1
+        self._last_write[y.buf.untyped_storage().data_ptr()] = self._writes
+        y.bounded, y.absmax = bounded, None
+        y.gn_quads = (*moments, self._writes) if moments is not None else None
+        return y
+
+    def fact(self, x: Act, rec: tuple | None) -> tuple | None:
+        r"""``rec`` (x.absmax / x.gn_quads) if it still describes what x's allocation holds, else None."""
+        return rec if rec is not None and rec[-1] == self._last_write.get(x.buf.untyped_storage().data_ptr()) else None
 
     def absmax_of(self, x: Act) -> torch.Tensor:
-        r"""The AZ_ABSMAX_SLOTS partial maxima of |x| (``az_absmax_f32``: one streaming pass, recorded once per tensor and shared by
-        its consumers) -- the activation scale of an f16x2 launch on an unbounded input (``AzConvArgs.in_absmax0 / in_absmax1``).
-        Valid as long as the tensor is not rewritten on the tape: ops that write into an existing Act reset ``absmax`` (``conv(out=...)``)."""
-        if x.absmax is None:
+        r"""The AZ_ABSMAX_SLOTS partial maxima of |x| (``az_absmax_f32``: one streaming pass, recorded once per tensor contents and
+        shared by its consumers) -- the activation scale of an f16x2 launch on an unbounded input (``AzConvArgs.in_absmax0 / in_absmax1``)."""
+        if self.fact(x, x.absmax) is None:
             assert not x.half and x.affine is None
             slots = self.empty(256)
-            if x.gn_quads is not None and F16X2_MOMENTS:
+            moments = self.fact(x, x.gn_quads)
+            if moments is not None and F16X2_MOMENTS:
                 # the producing convolution left GroupNorm moments of this tensor: |x| <= |mean| + sqrt(M2) per record -- an upper
                 # bound of the maximum for the price of reading the records (az_absmax_from_moments_f32)
-                q = x.gn_quads[0]
-                self.tape.add("az_absmax_from_moments_f32", slots.data_ptr(), q.data_ptr(), q.numel() // 4, keep=[q])
+                self.tape.add("az_absmax_from_moments_f32", slots.data_ptr(), moments[0].data_ptr(), moments[0].numel() // 4, keep=[moments[0]])
             else:
                 self.tape.add("az_absmax_f32", slots.data_ptr(), x.ptr, x.B * x.H * x.W * x.cs, keep=[x.buf])
-            x.absmax = slots
-        return x.absmax
+            x.absmax = (slots, self._last_write.get(x.buf.untyped_storage().data_ptr()))
+        return x.absmax[0]
 
     def upsample_nearest(self, x: Act, sh: int, sw: int, hout: int, wout: int) -> Act:
         r"""``narrow(Upsample(scale_factor=(sh, sw), mode="nearest")(x), (hout, wout))`` as a pass of its own -- only for
         factors that are not powers of two (those are a shift inside the consuming convolution's gather)."""
         y = self.new_act(x.B, hout, wout, x.C)
-        y.bounded = x.bounded
         self.tape.add("az_upsample_nearest_f32", y.ptr, x.ptr, x.B, x.H, x.W, x.cs, sh, sw, hout, wout)
-        return y
+        return self.wrote(y, bounded=x.bounded)
 
     def finish(self) -> None:
         r"""Allocates the shared split-K workspace and patches it into the recorded convs."""
@@ -711,17 +725,17 @@ class Builder:
         ST, act = x.affine
         n = x.B * x.cs
         y = self.new_act(x.B, x.H, x.W, x.C, f32=not x.half)
-        y.bounded = True
-        self._affine_act(y, x, None, 0, ST.data_ptr(), ST.data_ptr() + 4 * n, x.B, x.H, x.W, x.cs, act, 0)
-        return y
+        return self._affine_act(y, x, None, 0, ST.data_ptr(), ST.data_ptr() + 4 * n, x.B, x.H, x.W, x.cs, act, 0, bounded=True)
 
-    def _affine_act(self, y: Act, x: Act, x1p, c0s: int, S: int, T: int, B: int, H: int, W: int, cs: int, act: int, pool: int) -> None:
+    def _affine_act(self, y: Act, x: Act, x1p, c0s: int, S: int, T: int, B: int, H: int, W: int, cs: int, act: int, pool: int, *,
+                    bounded: bool) -> Act:
         r"""y = act(x * S + T) (optionally pooled) on fp32 tensors or on tensors in the module's 2-byte type (x, x1, y alike)."""
         if x.half:
             assert y.half
             self.tape.add("az_affine_act_h16", y.ptr, x.ptr, x1p, c0s, S, T, B, H, W, cs, act, pool, 2 if x.buf.dtype == torch.float16 else 1)
         else:
             self.tape.add("az_affine_act_f32", y.ptr, x.ptr, x1p, c0s, S, T, B, H, W, cs, act, pool)
+        return self.wrote(y, bounded=bounded)
 
     def group_norm(
         self, x: Act, groups: int, *, weight=None, bias=None, scale=None, shift=None, scale_off=0, shift_off=0,
@@ -731,19 +745,19 @@ class Builder:
         input is the channel concatenation [x | x1], read in place (never materialised)."""
         B, HW = x.B, x.H * x.W
         x1p, c0s = None, 0
-        src_quads = [x.gn_quads] + ([x1.gn_quads] if x1 is not None else [])
-        src_channels = [x.C] + ([x1.C] if x1 is not None else [])
+        srcs = [x] + ([x1] if x1 is not None else [])
+        src_quads = [self.fact(s, s.gn_quads) for s in srcs]
+        src_channels = [s.C for s in srcs]
         if x1 is not None:
             assert x.C == x.cs and x1.C == x1.cs and (x1.H, x1.W) == (x.H, x.W) and x1.half == x.half
             x1p, c0s = x1.ptr, x.cs
-            x = Act(x.buf, x.B, x.H, x.W, x.C + x1.C, x.cs + x1.cs, True)
+            x = x.view(C_=x.C + x1.C, cs=x.cs + x1.cs)
         ST = self.empty(2 * B * x.cs)  # [scale | shift]: one buffer (AzConvArgs.in_affine reads both through one descriptor)
         S, T = ST[: B * x.cs], ST[B * x.cs :]
         f = AzNormFinalizeArgs()
         Cg = x.C // groups
-        fused = src_quads is not None and Cg % 4 == 0 and x.C == x.cs and all(q is not None for q in src_quads) \
-            and all((c // 4) % (Cg // 4) == 0 for c in src_channels)
-        if fused:  # every source was produced by a convolution that left its moments: no statistics pass
+        fused = Cg % 4 == 0 and x.C == x.cs and all(q is not None for q in src_quads) and all((c // 4) % (Cg // 4) == 0 for c in src_channels)
+        if fused:  # every source was produced by a convolution that left its moments of what it holds now: no statistics pass
             nchunks = src_quads[0][1]
             f.partials = src_quads[0][0].data_ptr()
             if len(src_quads) > 1:
@@ -770,22 +784,18 @@ class Builder:
         if (lazy and AFFINE_FUSED and x1 is None and not pool and act == 0 and x.C == x.cs and x.cs % 8 == 0
                 and self.half is None):
             # no apply pass: the consumer (Builder.conv) reads x and applies scale / shift itself
-            y = Act(x.buf, B, x.H, x.W, x.C, x.cs, True)
+            y = x.view(bounded=True)  # (the values the consumer sees: act(buf * scale + shift))
             y.affine = (ST, act)
-            y.bounded = True  # (the values the consumer sees: act(buf * scale + shift))
             return y
         if pool:  # 1: 2x2, 2: along the width only (a 1-D signal held as a one-row image)
             y = self.new_act(B, x.H // 2 if pool == 1 else x.H, x.W // 2, x.C, f32=not x.half)
         else:
             y = self.new_act(B, x.H, x.W, x.C, f32=not x.half)
-        self._affine_act(y, x, x1p, c0s, S.data_ptr(), T.data_ptr(), B, x.H, x.W, x.cs, act, pool)
-        y.bounded = True
-        return y
+        return self._affine_act(y, x, x1p, c0s, S.data_ptr(), T.data_ptr(), B, x.H, x.W, x.cs, act, pool, bounded=True)
 
     def row_norm(self, x: Act, kind: int, *, weight=None, scale=None, shift=None, scale_off=0, shift_off=0, bstride=0,
                  eps=1e-5):
         y = self.new_act(x.B, x.H, x.W, x.C, f32=not x.half)
-        y.bounded = True
         rows = x.B * x.H * x.W
         args = (y.ptr, x.ptr, weight.data_ptr() if weight is not None else None,
                 scale.data_ptr() + 4 * scale_off if scale is not None else None,
@@ -795,7 +805,64 @@ class Builder:
             self.tape.add("az_rownorm_mod_h16", *args, 2 if x.buf.dtype == torch.float16 else 1, keep=[weight, scale, shift])
         else:
             self.tape.add("az_rownorm_mod_f32", *args, keep=[weight, scale, shift])
-        return y
+        return self.wrote(y, bounded=True)
+
+    def attention(self, qkv: Act, heads: int, order: str, qk_rmsnorm: bool, scale: float, eps: float = 1e-5,
+                  rope: tuple | None = None, qk_weight: tuple | None = None, mask: torch.Tensor | None = None,
+                  norm_dim: int = 0) -> Act:
+        r"""softmax(q k^T * scale) v over a fused-QKV token tensor (B, L, 1, 3*heads*dim).
+
+        order: "nHC" = azula '(n H C)' (attention.py:90), "H3C" = ADM legacy (unet.py:338),
+        "3HC" = ADM new order (unet.py:371).  Output (B, L, 1, heads*dim) laid out '(H C)'.
+        ``norm_dim``: the real head size of zero-padded heads (see ATTN_HEAD_DIMS)."""
+        from ._lib import AzAttnArgs
+
+        Cq = qkv.C // 3
+        dim = Cq // heads
+        assert qkv.cs == qkv.C and dim * heads == Cq
+        L = qkv.H * qkv.W
+        out = self.new_act(qkv.B, qkv.H, qkv.W, Cq, f32=not qkv.half)
+        a = AzAttnArgs()
+        a.io_dtype = int(qkv.half)  # (q, k, v, out in the module's 2-byte type: the bf16 / f16 entries only)
+        es = 2 if qkv.half else 4
+        base = qkv.ptr
+        if order in ("nHC", "3HC"):
+            offs, hs = (0, Cq, 2 * Cq), dim
+        elif order == "H3C":
+            offs, hs = (0, dim, 2 * dim), 3 * dim
+        else:
+            raise ValueError(order)
+        a.q, a.k, a.v, a.out = base + es * offs[0], base + es * offs[1], base + es * offs[2], out.ptr
+        a.batch, a.heads, a.tokens, a.head_dim = qkv.B, heads, L, dim
+        for n in ("q", "k", "v"):
+            setattr(a, n + "_bstride", L * qkv.cs)
+            setattr(a, n + "_tstride", qkv.cs)
+            setattr(a, n + "_hstride", hs)
+        a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
+        a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, int(qk_rmsnorm), eps, norm_dim
+        if qkv.qk_prepared:  # the projection's epilogue has normalised / gained / rotated q and k already (Builder.conv(qk_prep=...))
+            assert order in ("nHC", "3HC")
+            a.qk_rmsnorm, rope, qk_weight = 0, None, None
+        if rope is not None:  # (cos, sin) tables of shape (L, heads * dim / 2)
+            a.rope_cos, a.rope_sin = rope[0].data_ptr(), rope[1].data_ptr()
+            self.tape.keep.extend(rope)
+        if qk_weight is not None:  # learned (dim,) gains of the q / k RMS norms
+            a.q_weight, a.k_weight = qk_weight[0].data_ptr(), qk_weight[1].data_ptr()
+            self.tape.keep.extend(qk_weight)
+        if mask is not None:  # (L, L), (B | 1, 1 | H, L, L) boolean: True = attend (reference attention.py:97-104)
+            m = mask
+            if m.ndim == 2:
+                m = m[None, None]
+            if m.ndim != 4 or m.shape[-2:] != (L, L) or m.shape[0] not in (1, qkv.B) or m.shape[1] not in (1, heads):
+                raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast to ({qkv.B}, {heads}, {L}, {L})")
+            m8 = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+            a.mask = m8.data_ptr()
+            a.mask_bstride = m8.stride(0) if m.shape[0] > 1 else 0
+            a.mask_hstride = m8.stride(1) if m.shape[1] > 1 else 0
+            self.tape.keep.append(m8)
+        a._flops = 4 * qkv.B * heads * L * L * dim
+        self.tape.add(choose_attention(dim, qkv.bounded, self.half), C.byref(a), keep=[a])
+        return self.wrote(out, bounded=qkv.bounded)  # (a convex combination of the values)
 
 
 # ------------------------------------------------------------------------------- AdaZero modulation helpers
@@ -897,72 +964,3 @@ def pad_head_table(t: torch.Tensor, heads: int, n: int, n_pad: int, fill: float 
     tp = t.new_full((*lead, heads, n_pad), fill)
     tp[..., :n] = t.reshape(*lead, heads, n)
     return tp.reshape(*lead, heads * n_pad)
-
-
-def _builder_attention(self, qkv: Act, heads: int, order: str, qk_rmsnorm: bool, scale: float, eps: float = 1e-5,
-                       rope: tuple | None = None, qk_weight: tuple | None = None, mask: torch.Tensor | None = None,
-                       norm_dim: int = 0) -> Act:
-    r"""softmax(q k^T * scale) v over a fused-QKV token tensor (B, L, 1, 3*heads*dim).
-
-    order: "nHC" = azula '(n H C)' (attention.py:90), "H3C" = ADM legacy (unet.py:338),
-    "3HC" = ADM new order (unet.py:371).  Output (B, L, 1, heads*dim) laid out '(H C)'.
-    ``norm_dim``: the real head size of zero-padded heads (see ATTN_HEAD_DIMS)."""
-    from ._lib import AzAttnArgs
-
-    Cq = qkv.C // 3
-    dim = Cq // heads
-    assert qkv.cs == qkv.C and dim * heads == Cq
-    L = qkv.H * qkv.W
-    out = self.new_act(qkv.B, qkv.H, qkv.W, Cq, f32=not qkv.half)
-    out.bounded = qkv.bounded  # (a convex combination of the values)
-    a = AzAttnArgs()
-    a.io_dtype = int(qkv.half)  # (q, k, v, out in the module's 2-byte type: the bf16 / f16 entries only)
-    es = 2 if qkv.half else 4
-    base = qkv.ptr
-    if order in ("nHC", "3HC"):
-        offs, hs = (0, Cq, 2 * Cq), dim
-    elif order == "H3C":
-        offs, hs = (0, dim, 2 * dim), 3 * dim
-    else:
-        raise ValueError(order)
-    a.q, a.k, a.v, a.out = base + es * offs[0], base + es * offs[1], base + es * offs[2], out.ptr
-    a.batch, a.heads, a.tokens, a.head_dim = qkv.B, heads, L, dim
-    for n in ("q", "k", "v"):
-        setattr(a, n + "_bstride", L * qkv.cs)
-        setattr(a, n + "_tstride", qkv.cs)
-        setattr(a, n + "_hstride", hs)
-    a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
-    a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, int(qk_rmsnorm), eps, norm_dim
-    if qkv.qk_prepared:  # the projection's epilogue has normalised / gained / rotated q and k already (Builder.conv(qk_prep=...))
-        assert order in ("nHC", "3HC")
-        a.qk_rmsnorm, rope, qk_weight = 0, None, None
-    if rope is not None:  # (cos, sin) tables of shape (L, heads * dim / 2)
-        a.rope_cos, a.rope_sin = rope[0].data_ptr(), rope[1].data_ptr()
-        self.tape.keep.extend(rope)
-    if qk_weight is not None:  # learned (dim,) gains of the q / k RMS norms
-        a.q_weight, a.k_weight = qk_weight[0].data_ptr(), qk_weight[1].data_ptr()
-        self.tape.keep.extend(qk_weight)
-    if mask is not None:  # (L, L), (B | 1, 1 | H, L, L) boolean: True = attend (reference attention.py:97-104)
-        m = mask
-        if m.ndim == 2:
-            m = m[None, None]
-        if m.ndim != 4 or m.shape[-2:] != (L, L) or m.shape[0] not in (1, qkv.B) or m.shape[1] not in (1, heads):
-            raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast to ({qkv.B}, {heads}, {L}, {L})")
-        m8 = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
-        a.mask = m8.data_ptr()
-        a.mask_bstride = m8.stride(0) if m.shape[0] > 1 else 0
-        a.mask_hstride = m8.stride(1) if m.shape[1] > 1 else 0
-        self.tape.keep.append(m8)
-    a._flops = 4 * qkv.B * heads * L * L * dim
-    name = "az_attention_f32"
-    if self.half is None and pieces() and ATTN_X3 and dim in (16, 32, 64, 80):
-        # the two contractions as 3 x bf16 pieces / 6 partial products: fp32 accuracy, 0.375 x the pipe time (64 x 12 heads x 256
-        # tokens x 64: 140 -> 111 us; head_dim 128 needs one wave per SIMD there and measured slower, 458 vs 516 us: fp32 kernel)
-        name = "az_attention_f16x2_f32" if FP32_MFMA == "f16x2" and ATTN_H2 and qkv.bounded else "az_attention_x3_f32"
-    if self.half is not None:  # module cast to half precision: contractions on the bf16 / f16 MFMA
-        name = "az_attention_f16_f32" if self.half == torch.float16 else "az_attention_bf16_f32"
-    self.tape.add(name, C.byref(a), keep=[a])
-    return out
-
-
-Builder.attention = _builder_attention

@@ -137,7 +137,7 @@ class UNetBlock(nn.Module):
         if plan is None or plan[0] != versions:
             bld = Builder(x.device, half=next(self.parameters()).dtype)
             xa = bld.new_act(B * Dd, H, W, Cc, pinned=True)
-            xin = Vol(xa.buf, B, Dd, H, W, Cc, xa.cs)
+            xin = Vol(xa, B, Dd)
             mod_buf = torch.empty(max(rows, 1), max(D, 1), dtype=torch.float32, device=x.device)
             jobs: list = []
             out = block3d(self, bld, xin, D, rows, jobs, keep_input=True)

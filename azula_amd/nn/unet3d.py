@@ -24,34 +24,32 @@ from ..engine import Act, Builder, ada_zero_triple, mod_front_tape, pad4
 
 
 class Vol:
-    r"""(B, D, H, W, cs) floats in ``buf``; ``C`` real channels."""
+    r"""B volumes of D planes: ``act`` holds them as B D planes of H x W pixels (its buf, H, W, C, cs and bounded are the volume's)."""
 
-    __slots__ = ("buf", "B", "D", "H", "W", "C", "cs", "bounded")
+    __slots__ = ("act", "B", "D")
 
-    def __init__(self, buf: torch.Tensor, B: int, D: int, H: int, W: int, C: int, cs: int, bounded: bool = False) -> None:
-        self.buf, self.B, self.D, self.H, self.W, self.C, self.cs = buf, B, D, H, W, C, cs
-        self.bounded = bounded  # (engine.Act.bounded: the magnitudes do not scale with the sampler's state -- what the f16x2 kernels take)
+    def __init__(self, act: Act, B: int, D: int) -> None:
+        assert act.B == B * D
+        self.act, self.B, self.D = act, B, D
 
-    def _view(self, a: Act) -> Act:
-        a.bounded = self.bounded
-        return a
+    def __getattr__(self, name: str):
+        return getattr(self.act, name)
 
     def planes(self, b: int, d0: int, d1: int) -> Act:
         n = self.H * self.W * self.cs
-        return self._view(Act(self.buf[(b * self.D + d0) * n : (b * self.D + d1) * n], d1 - d0, self.H, self.W, self.C, self.cs, True))
+        return self.act.view(d1 - d0, buf=self.buf[(b * self.D + d0) * n : (b * self.D + d1) * n])
 
     def image(self) -> Act:
         r"""The volume as B images of (D H) x W pixels: what the norms and elementwise passes see."""
-        return self._view(Act(self.buf, self.B, self.D * self.H, self.W, self.C, self.cs, True))
+        return self.act.view(self.B, self.D * self.H)
 
     def all_planes(self) -> Act:
         r"""The volume as B D images of H x W pixels: what one depth-tap launch over all planes sees."""
-        return self._view(Act(self.buf, self.B * self.D, self.H, self.W, self.C, self.cs, True))
+        return self.act.view()
 
 
 def new_vol(bld: Builder, B: int, D: int, H: int, W: int, C: int) -> Vol:
-    a = bld.new_act(B * D, H, W, C)
-    return Vol(a.buf, B, D, H, W, C, a.cs)
+    return Vol(bld.new_act(B * D, H, W, C), B, D)
 
 
 def free_vol(bld: Builder, v: Vol) -> None:
@@ -73,7 +71,6 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
     ``gate`` / ``res``: out = res + gate * (sum + bias)."""
     w, bias = conv.weight, conv.bias
     cout, _, kd, kh, kw = w.shape
-    assert kh == kw or True
     p = kd // 2
     Din, Hin, Win = (like.D, like.H, like.W) if like is not None else (x.D, x.H, x.W)
     sd_, sh_, sw_ = (stride, stride, stride) if isinstance(stride, int) else stride  # per-axis strides
@@ -83,7 +80,7 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
     Wo = (Win + 2 * (kw // 2) - kw) // sw_ + 1
     out = new_vol(bld, x.B, Do, Ho, Wo, cout)
     # (bounded sources and no residual of the stream: the sum of the taps is bounded by the weights, like a 2-D convolution's output)
-    out.bounded = x.bounded and (x1 is None or x1.bounded) and (res is None or res.bounded)
+    bounded = x.bounded and (x1 is None or x1.bounded) and (res is None or res.bounded)
     taps = [p] + [j for j in range(kd) if j != p]  # centre first: it exists for every output plane and writes it
     packs = {j: bld.pack_conv(w[:, :, j], bias if j == p else None, cin0=x.C if x1 is not None else None) for j in taps}
     # ---- ONE launch per depth tap for all planes of all samples (AzConvArgs.depth: the kernels' loaders take a plane whose
@@ -101,7 +98,6 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
             src1 = x1
             if ud_ == 1:  # nearest x2 along the depth axis (narrowed to Din planes): plane d of the wide volume = plane d >> 1
                 x1u = new_vol(bld, x1.B, Din, x1.H, x1.W, x1.C)
-                x1u.bounded = x1.bounded
                 n = x1.H * x1.W * x1.cs
                 if 2 * x1.D == Din:  # one launch per parity over all samples
                     for half_ in (0, 1):
@@ -113,10 +109,10 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
                             if cnt > 0:
                                 bld.tape.add("az_token_copy_f32", x1u.buf.data_ptr() + 4 * b_ * Din * n, 2, half_,
                                              x1.buf.data_ptr() + 4 * b_ * x1.D * n, 1, 0, 1, cnt, n)
+                bld.wrote(x1u.act, bounded=x1.bounded)
                 src1 = x1u
             kw_ = dict(src1=planes(src1), up1=(uh_, uw_), hin=Hin, win=Win)
         full = out if sd_ == 1 else new_vol(bld, x.B, Din, Ho, Wo, cout)  # (a strided depth axis: every plane, then every sd-th kept)
-        full.bounded = out.bounded
         allo = planes(full)
         allr = planes(res) if res is not None else None
         # (the activation of the sum rides on the last tap's store: act 6 = silu(tap + what the earlier taps left; no pass of its own)
@@ -142,6 +138,7 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
             free_vol(bld, x1u)
         if silu and not fold:
             bld.tape.add("az_silu_f32", out.buf.data_ptr(), out.buf.data_ptr(), out.buf.numel())
+        bld.wrote(out.act, bounded=bounded)
         return out
     for b in range(x.B):
         g = dict(gate=gate, gate_off=gate_off + b * gate_bstride, gate_bstride=0) if gate is not None else {}
@@ -173,6 +170,7 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
                              res=(res.planes(b, d, d + 1) if res is not None else None) if first else dst, **g, **kw_)
     if silu:
         bld.tape.add("az_silu_f32", out.buf.data_ptr(), out.buf.data_ptr(), out.buf.numel())
+    bld.wrote(out.act, bounded=bounded)
     return out
 
 
@@ -184,15 +182,15 @@ def upsample3d_nearest(bld: Builder, x: Vol, factors, like: Vol) -> Vol:
     planes = x.all_planes()
     wide = bld.upsample_nearest(planes, sh_, sw_, like.H, like.W) if (sh_, sw_) != (1, 1) or (x.H, x.W) != (like.H, like.W) else planes
     if sd_ == 1 and x.D == like.D:
-        return Vol(wide.buf, x.B, x.D, like.H, like.W, x.C, x.cs, x.bounded)
+        return Vol(wide, x.B, x.D)
     inv = torch.tensor(1.0 / sd_, dtype=torch.float32)
     src = torch.clamp(torch.floor(torch.arange(like.D, dtype=torch.float32) * inv).to(torch.int64), max=x.D - 1)
     idx = (torch.arange(x.B)[:, None] * x.D + src[None, :]).reshape(-1)
     out = new_vol(bld, x.B, like.D, like.H, like.W, x.C)
-    out.bounded = x.bounded
     n = like.H * like.W * x.cs
     idx_dev = idx.to(bld.device)
     bld.tape.add("az_gather_rows_f32", out.buf.data_ptr(), wide.buf.data_ptr(), idx_dev.data_ptr(), x.B * like.D, n, x.B * x.D, keep=[idx_dev])
+    bld.wrote(out.act, bounded=x.bounded)
     if wide is not planes:
         bld.free(wide)
     return out
@@ -207,7 +205,7 @@ def block3d(blk, bld: Builder, x: Vol, D_mod: int, mod_rows: int, mod_jobs: list
         n_ = bld.group_norm(xi, blk.groups, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
     else:
         n_ = bld.row_norm(xi, 0 if blk.norm_kind == "layer" else 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
-    nv = Vol(n_.buf, x.B, x.D, x.H, x.W, Cc, cs, n_.bounded)  # (the normalised volume: what the block's first convolution reads)
+    nv = Vol(n_.view(x.B * x.D, x.H), x.B, x.D)  # (the normalised volume: what the block's first convolution reads)
     c0, c3 = blk.ffn[0], blk.ffn[3]
     h1 = conv3d(bld, nv, c0, periodic=blk.periodic, silu=True)
     bld.free(n_)
@@ -226,7 +224,7 @@ class UNet3DPlan:
         cin = net.in_channels + net.cond_channels
         Dm = net.mod_features
         xa = Act(torch.empty(B * D * H * W * pad4(cin), dtype=torch.float32, device=device), B * D, H, W, cin, pad4(cin), True)
-        self.x_in = Vol(xa.buf, B, D, H, W, cin, xa.cs)
+        self.x_in = Vol(xa, B, D)
         self.mod = torch.empty(max(mod_rows, 1), max(Dm, 1), dtype=torch.float32, device=device)
         self.out = torch.empty(B, net.out_channels, D, H, W, dtype=torch.float32, device=device)
         self.versions = net._param_versions()

@@ -249,6 +249,7 @@ class DiTBlock(nn.Module):
         if self.ffn_activation == "swiglu" and not fused_glu:  # x1 * silu(x2) over interleaved pairs (layers.py:107-110)
             glu = bld.new_act(f1.B, f1.H, f1.W, f1.C // 2)
             bld.tape.add("az_swiglu_f32", glu.ptr, f1.ptr, f1.B * f1.H * f1.W, f1.C // 2, f1.cs, glu.cs)
+            bld.wrote(glu, bounded=False)
             bld.free(f1)
             f1 = glu
         out = bld.conv(f1, bld.pack_conv(f3.weight, f3.bias), C_, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
@@ -299,6 +300,7 @@ class DiTPlan:
             self.x_nchw = torch.empty(B, Z, H, W, dtype=torch.float32, device=device)
             tokens = bld.new_act(B, L, 1, cin, pinned=True, f32=True)  # (the plan's input stays fp32: the first GEMM rounds it per tile)
             bld.tape.add("az_patchify_f32", tokens.ptr, self.x_nchw.data_ptr(), None, B, Z, H, W, p, tokens.cs)
+            bld.wrote(tokens, bounded=False)
             self.x_in_buf, self.x_in_cs = self.x_nchw, 0
         else:
             tokens = bld.new_act(B, L, 1, cin, pinned=True, f32=True)

@@ -167,19 +167,14 @@ class ADMPlan:
             partials, one set per plane, are D sets per sample."""
             if a is None or not three_d:
                 return a
-            v = Act(a.buf, B, D * a.H, a.W, a.C, a.cs, True)
-            v.bounded = a.bounded
-            if a.gn_quads is not None:
-                v.gn_quads = (a.gn_quads[0], D * a.gn_quads[1])
-            return v
+            q = a.gn_quads
+            return a.view(B, D * a.H, gn_quads=(q[0], D * q[1], q[2]) if q is not None else None)
 
         def planes(a: Act) -> Act:
             r"""Inverse of `vol` for a pass's result (pooled or not): B (D H') x W' images -> B D planes of H' x W'."""
             if not three_d:
                 return a
-            p_ = Act(a.buf, PB, a.H // D, a.W, a.C, a.cs, a.pinned)
-            p_.bounded = a.bounded
-            return p_
+            return a.view(PB, a.H // D, pinned=a.pinned)
 
         def group_norm(x: Act, *args, x1: Act | None = None, **kw) -> Act:
             return planes(bld.group_norm(vol(x), *args, x1=vol(x1), **kw))
@@ -288,7 +283,8 @@ class ADMPlan:
                     bld.tape.add("az_gather_rows_f32", eb.data_ptr(), film.data_ptr(),
                                  row0.data_ptr(), B, ocs, 1)
                 he = bld.new_act(PB, h.H, h.W, oc)
-                bld._affine_act(he, h, None, 0, bld.const(torch.ones(B * ocs)).data_ptr(), eb.data_ptr(), B, D * h.H, h.W, ocs, 0, 0)
+                bld._affine_act(he, h, None, 0, bld.const(torch.ones(B * ocs)).data_ptr(), eb.data_ptr(), B, D * h.H, h.W, ocs, 0, 0,
+                                bounded=False)
                 n2 = group_norm(he, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
                 bld.free(he)
             bld.free(h)
@@ -297,7 +293,7 @@ class ADMPlan:
                 assert x1 is None
                 ones, zeros = bld.const(torch.ones(B * x.cs)), bld.const(torch.zeros(B * x.cs))
                 xs = bld.new_act(PB, *halved(x), x.C)
-                bld._affine_act(xs, x, None, 0, ones.data_ptr(), zeros.data_ptr(), B, D * x.H, x.W, x.cs, 0, pool2)
+                bld._affine_act(xs, x, None, 0, ones.data_ptr(), zeros.data_ptr(), B, D * x.H, x.W, x.cs, 0, pool2, bounded=False)
                 out = conv(n2, co, oc, res=xs, gn_stats=True, winograd=wino)
                 bld.free(xs)
             elif rb.up:
@@ -317,12 +313,11 @@ class ADMPlan:
         def attention(ab: AttentionBlock, x: Act) -> Act:
             Cc = ab.channels
             n_ = group_norm(x, 32, weight=bld.const(ab.norm.weight), bias=bld.const(ab.norm.bias))
-            tok = Act(n_.buf, B, D * n_.H * n_.W, 1, Cc, n_.cs, True)
-            tok.bounded = n_.bounded  # (the normalised tokens: the same memory)
+            tok = n_.view(B, D * n_.H * n_.W, 1, Cc)  # (the normalised tokens: the same memory)
             ch = Cc // ab.num_heads
             chp = engine.attn_padded_dim(ch, bld.half)
             order = "3HC" if ab.new_order else "H3C"
-            xt = Act(x.buf, B, D * x.H * x.W, 1, Cc, x.cs, True)
+            xt = x.view(B, D * x.H * x.W, 1, Cc)
             if chp != ch:  # a head size the kernels are not instantiated for: zero-padded heads (engine.ATTN_HEAD_DIMS; G24)
                 wq, bq = engine.pad_qkv_heads(ab.qkv.weight, ab.qkv.bias, ab.num_heads, ch, chp, order)
                 qkv = bld.conv(tok, bld.pack_conv(wq, bq), 3 * ab.num_heads * chp)
@@ -336,7 +331,7 @@ class ADMPlan:
                 o = bld.conv(att, bld.pack_conv(ab.proj_out.weight, ab.proj_out.bias), Cc, res=xt)
             bld.free(att)
             bld.free(n_)
-            return Act(o.buf, PB, x.H, x.W, Cc, o.cs)
+            return o.view(PB, x.H, x.W, pinned=False)
 
         def run(block: nn.Sequential, h: Act, h1: Act | None = None) -> Act:
             for layer in block:
@@ -352,7 +347,7 @@ class ADMPlan:
                     else:  # AvgPoolNd(2, 2): the pooling form of the elementwise pass with S = 1, T = 0
                         nh = bld.new_act(PB, *halved(h), h.C)
                         bld._affine_act(nh, h, None, 0, bld.const(torch.ones(B * h.cs)).data_ptr(),
-                                        bld.const(torch.zeros(B * h.cs)).data_ptr(), B, D * h.H, h.W, h.cs, 0, pool2)
+                                        bld.const(torch.zeros(B * h.cs)).data_ptr(), B, D * h.H, h.W, h.cs, 0, pool2, bounded=False)
                 elif isinstance(layer, Upsample):
                     if layer.use_conv:  # nearest x2 is a read-side shift of the conv gather
                         nh = conv(h, layer.conv, layer.out_channels, up0=up2, winograd=wino)

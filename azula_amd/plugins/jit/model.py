@@ -155,6 +155,7 @@ class JiTPlan:
         b_all = torch.cat([m.bias.detach() for m in heads_]).to(device)
         c_act = Act(bld.empty(B * Hd), 1, B, 1, Hd, Hd, True)
         tape.add("az_silu_f32", c_act.ptr, c.data_ptr(), B * Hd)
+        bld.wrote(c_act, bounded=False)
         mods = bld.conv(c_act, bld.pack_conv(w_all, b_all), w_all.shape[0], out_f32=True)  # (the modulation table stays fp32)
         mods.pinned = True
         mod, MS = mods.buf, mods.cs  # row stride of the modulation table
@@ -163,6 +164,7 @@ class JiTPlan:
         e = net.x_embedder
         tokens = bld.new_act(B, L, 1, Z * p * p, pinned=True, f32=True)  # (the plan's input stays fp32)
         tape.add("az_patchify_f32", tokens.ptr, self.x_nchw.data_ptr(), None, B, Z, S, S, p, tokens.cs)
+        bld.wrote(tokens, bounded=False)
         low = bld.conv(tokens, bld.pack_conv(e.proj1.weight.detach().reshape(e.proj1.out_channels, -1), None), e.proj1.out_channels)
         pos_t = bld.const(net.pos_embed.detach().reshape(-1))
         if bld.half_act:  # (the residual operand has the destination's element type)
@@ -193,6 +195,7 @@ class JiTPlan:
                 else:
                     tape.add("az_token_fill_f32", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd)
                     tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd)
+                bld.wrote(wide, bounded=False)
                 bld.free(x)
                 x = wide
             m0_ = 6 * Hd * i  # this block's columns: shift_a | scale_a | gate_a | shift_m | scale_m | gate_m
@@ -236,6 +239,7 @@ class JiTPlan:
                 bld.free(n2)
                 glu = bld.new_act(f1.B, f1.H, f1.W, half)
                 tape.add("az_swiglu_f32", glu.ptr, f1.ptr, f1.B * f1.H * f1.W, half, f1.cs, glu.cs)
+                bld.wrote(glu, bounded=False)
                 bld.free(f1)
             x = bld.conv(glu, bld.pack_conv(blk.mlp.w3.weight, blk.mlp.w3.bias), Hd, gate=mod, gate_off=m0_ + 5 * Hd,
                          gate_bstride=MS, res=x2)
@@ -244,6 +248,7 @@ class JiTPlan:
         if Lc and net.in_context_start < len(net.blocks):  # x[:, in_context_len:]
             body = bld.new_act(B, L, 1, Hd)
             tape.add("az_token_copy_f32", body.ptr, L, 0, x.ptr, L + Lc, Lc, L, B, Hd // 2 if body.half else Hd)
+            bld.wrote(body, bounded=False)
             bld.free(x)
             x = body
 
