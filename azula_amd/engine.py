@@ -10,6 +10,7 @@ from it -- serves every sampling step.  Python is only the builder; replay is on
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import NamedTuple
 
@@ -132,11 +133,13 @@ class Act:
 
     def __init__(self, buf: torch.Tensor, B: int, H: int, W: int, C_: int, cs: int, pinned: bool = False) -> None:
         self.buf, self.B, self.H, self.W, self.C, self.cs, self.pinned = buf, B, H, W, C_, cs, pinned
-        # bounded: the magnitudes in this tensor do not scale with the sampler's state -- it is the output of a normalisation, or of
-        # convolutions / attention over such outputs without a residual add (bounded by the WEIGHTS).  The f16x2 kernels, whose
-        # activation operand has a stated range (|x| < ~1e6, include/azula_amd.h), are chosen only for bounded inputs; residual /
-        # input streams (which grow with x_t: an unstable multistep sampler reaches 1e7 in tests/test_gpu_unet.py) go through
-        # the bf16x3 kernels, whose domain is all of fp32.  Default False: unknown = unbounded.
+        # bounded: this tensor is the DIRECT output of a normalisation's apply (GroupNorm, LayerNorm, RMSNorm, with modulation and a
+        # fused activation, or a pending in-gather affine, Act.affine): |x| <= |1 + a| sqrt(n) + |b| per element, whatever the
+        # weights before it produced.  The f16x2 kernels with the FIXED activation scale (|x| < ~1e6, include/azula_amd.h) take
+        # only such inputs.  Outputs of convolutions, attention, SwiGLU and upsampling are NOT bounded, even over bounded inputs:
+        # their magnitude is set by trained weights (a 1e6 gain in a UNet FFN turns the fixed-scale split into NaN), so those
+        # consumers go through choose_conv's dynamic rule -- the f16x2 kernels with a measured (az_absmax_f32) or producer-moment
+        # bound (az_absmax_from_moments_f32) scale, or the bf16x3 kernels, whose domain is all of fp32.  Default False.
         # Set by Builder.wrote (and view()).  Content facts below end in the serial of the write they describe (Builder.fact).
         self.bounded = False
         self.absmax = None  # (AZ_ABSMAX_SLOTS floats written by az_absmax_f32 / ..._from_moments_f32, serial): Builder.absmax_of
@@ -175,11 +178,17 @@ WINOGRAD = os.environ.get("AZ_WINOGRAD", "1")
 # v_mfma_f32_32x32x16_f16 in one fp32 accumulator -- half the matrix instructions of bf16x3, measured the MOST accurate of the
 # modes against fp64 (half as many fp32 accumulation steps: rms 5.2e-7 against 6.7e-7 bf16x3 / 7.5e-7 fp32 MFMA on the K = 2304
 # layer of test_conv2d_x3_accuracy), on a STATED range of its activation operand, |x| < ~1e6 (beyond it NaN, never a wrong finite
-# value: include/azula_amd.h).  It therefore takes only BOUNDED inputs (Act.bounded: outputs of normalisations and of
-# convolutions / attention over them); layers that read the residual / input stream run the bf16x3 kernels in this mode too.
+# value: include/azula_amd.h).  With that FIXED scale it takes only BOUNDED inputs (Act.bounded: direct outputs of normalisations);
+# every other input runs it with a measured / moment-bounded scale (F16X2_DYNAMIC below) or the bf16x3 kernels.
 # C2 16.95 -> 15.2 ms per denoise step, C3 85 -> 107+ images/s, C5 32.1 -> 28.5 ms, C6 63.6 -> 84 images/s (profiles/r06_f16x2_gate*.txt).
 FP32_MFMA = os.environ.get("AZ_FP32_MFMA", "f16x2")
 assert FP32_MFMA in ("native", "bf16x3", "f16x2"), FP32_MFMA
+
+
+def moments_for_scale() -> bool:
+    r"""A consumer's f16x2 activation scale may be bounded from its producer's moments (F16X2_DYNAMIC / F16X2_MOMENTS below):
+    producers without a GroupNorm after them ask for moments (Builder.conv(gn_stats=...)) only then."""
+    return FP32_MFMA == "f16x2" and F16X2_DYNAMIC and F16X2_MOMENTS
 
 
 def pieces() -> bool:
@@ -187,12 +196,14 @@ def pieces() -> bool:
     return FP32_MFMA in ("bf16x3", "f16x2")
 
 
-# f16x2 mode, layers whose input is NOT bounded (residual / input streams): "1" (default) = f16x2 kernels too where it pays, with the
-# activation scale taken from the sources' largest magnitude (one streaming az_absmax_f32 pass per source tensor and step, shared
-# by its consumers; AzConvArgs.in_absmax0 / in_absmax1: no stated range) -- the UNet's strided and skip-merge convolutions; "0" = bf16x3
+# f16x2 mode, layers whose input is NOT bounded (residual / input streams, outputs of convolutions and attention): "1" (default) =
+# f16x2 kernels too where it pays, with the activation scale taken from the sources' largest magnitude (one streaming az_absmax_f32
+# pass per source tensor and step, shared by its consumers; AzConvArgs.in_absmax0 / in_absmax1: no stated range) -- the UNet's
+# strided, skip-merge and second FFN convolutions, the token GEMMs behind attention / an FFN; "0" = bf16x3
 F16X2_DYNAMIC = os.environ.get("AZ_F16X2_DYNAMIC", "1") != "0"
 # ... and where the tensor's producer left GroupNorm moments (Act.gn_quads), the maximum is BOUNDED from them instead of measured
-# (az_absmax_from_moments_f32: no pass over the tensor) -- ADM's 1x1 skip projections, whose pass would cost what it saves ("0": measure)
+# (az_absmax_from_moments_f32: no pass over the tensor) -- ADM's 1x1 skip projections, whose pass would cost what it saves, and the
+# UNet FFN's SiLU(conv) hidden tensor, whose Winograd producer leaves them for its consumer ("0": measure)
 F16X2_MOMENTS = os.environ.get("AZ_F16X2_MOMENTS", "1") != "0"
 ATTN_H2 = os.environ.get("AZ_ATTN_H2", "1") != "0"  # f16x2 mode: the attention contractions in that form too ("0": bf16x3 attention -- A/B)
 ATTN_X3 = os.environ.get("AZ_ATTN_X3", "1") != "0"  # bf16x3 mode: attention contractions on the bf16 pipe too (az_attention_x3_f32)
@@ -229,11 +240,12 @@ CONV_OVERRIDES = (None, False, True, 0, 1, 2, 4, "x3", "wx3", "h2", "wh2", "h2d"
 # GroupNorm moments (Act.gn_quads) of its current contents are recorded
 ConvSource = NamedTuple("ConvSource", [("C", int), ("numel", int), ("bounded", bool), ("affine", bool), ("absmax", bool), ("moments", bool)])
 # ... and of the convolution: geometry (aniso: a stride / upsampling per axis), channel strides, one depth tap of a 3-D convolution,
-# Builder.half, the winograd= override (CONV_OVERRIDES) and the sources
+# Builder.half, the winograd= override (CONV_OVERRIDES), the sources and whether the weights' range fits the f16x2 packing
 ConvLayer = NamedTuple("ConvLayer", [
     ("ks", int), ("stride", int), ("aniso", bool), ("B", int), ("hout", int), ("wout", int), ("c0s", int), ("c1s", int), ("cout", int),
     ("cout_s", int), ("up0", int), ("depth", bool), ("half", "torch.dtype | None"), ("winograd", object), ("src0", ConvSource),
-    ("src1", "ConvSource | None")])
+    ("src1", "ConvSource | None"), ("w_h2", bool)])
+ConvLayer.__new__.__defaults__ = (True,)  # w_h2: the weights' range fits the f16x2 packing (ConvWeights.h2_range)
 # the C entry, the f16x2 form (H2_NAMES), with the activation scale from the sources' maxima (AzConvArgs.in_absmax0 / in_absmax1)
 ConvChoice = NamedTuple("ConvChoice", [("name", str), ("h2", bool), ("dyn", bool)])
 
@@ -270,9 +282,9 @@ def choose_conv(l: ConvLayer) -> ConvChoice:
         w in ("x3", "h2", "h2d")
         or (w is None and pieces() and not head and not use_wino and not use_f4 and cin_s >= X3_MIN_CHANNELS and l.cout_s >= X3_MIN_CHANNELS)
     )
-    h2 = w in ("h2", "wh2", "h2d", "wh2d") or (w not in ("x3", "wx3") and FP32_MFMA == "f16x2" and sources_bounded(l.src0, l.src1))
+    h2 = w in ("h2", "wh2", "h2d", "wh2d") or (w not in ("x3", "wx3") and FP32_MFMA == "f16x2" and l.w_h2 and sources_bounded(l.src0, l.src1))
     dyn = w in ("h2d", "wh2d")
-    if (not h2 and w is None and FP32_MFMA == "f16x2" and F16X2_DYNAMIC and l.half is None and not l.depth
+    if (not h2 and w is None and FP32_MFMA == "f16x2" and F16X2_DYNAMIC and l.w_h2 and l.half is None and not l.depth
             and (use_wino or use_x3) and not use_f4 and not any(s.affine for s in srcs)):
         # unbounded sources: f16x2 with the scale measured per step, where the pass over the sources costs clearly less than the
         # matrix instructions it saves (~12 % of a Winograd layer at ~350 TF/s algorithmic, ~25 % of a direct one at ~190);
@@ -299,14 +311,31 @@ def choose_conv(l: ConvLayer) -> ConvChoice:
     return ConvChoice(name, h2, dyn and h2)
 
 
-def choose_attention(dim: int, bounded: bool, half: torch.dtype | None) -> str:
-    r"""C entry of an attention layer (head size ``dim``, ``bounded`` q | k | v, Builder.half); reads the switches at call time."""
+# The f16x2 attention kernel's stated domain (include/azula_amd.h): |k| < 4094, |q * scale * log2 e| < 1e6; choose_attention takes it
+# only for RMS-normalised q / k whose plan-time bound (attention_qk_bound) is below these limits with a factor 2 to spare
+ATTN_H2_K_MAX = 4094.0 / 2
+ATTN_H2_QS_MAX = 1.0e6 / 2
+
+
+def attention_qk_bound(dim: int, norm_dim: int, scale: float, qk_weight: tuple | None) -> tuple[float, float]:
+    r"""(max |k|, max |q * scale * log2 e|) of RMS-normalised q / k rows: a normalised row has 2-norm sqrt(n) (n = norm_dim or
+    dim; eps only shrinks it), the learned gains multiply it by at most max |g|, RoPE turns channel pairs without changing their
+    norm -- so no element exceeds sqrt(n) max |g|.  Read at plan time from the gain tensors."""
+    n = norm_dim or dim
+    gq, gk = (1.0, 1.0) if qk_weight is None else (float(qk_weight[0].detach().abs().max()), float(qk_weight[1].detach().abs().max()))
+    return math.sqrt(n) * gk, math.sqrt(n) * gq * abs(scale) * 1.4426950408889634
+
+
+def choose_attention(dim: int, qk_normed: bool, half: torch.dtype | None) -> str:
+    r"""C entry of an attention layer (head size ``dim``, Builder.half); ``qk_normed``: q and k are RMS-normalised (in the kernel or
+    in the projection epilogue) with a bound inside the f16x2 kernel's domain (attention_qk_bound).  Reads the switches at call time."""
     if half is not None:  # module cast to half precision: contractions on the bf16 / f16 MFMA
         return "az_attention_f16_f32" if half == torch.float16 else "az_attention_bf16_f32"
     if pieces() and ATTN_X3 and dim in (16, 32, 64, 80):
         # the two contractions as 3 x bf16 pieces / 6 partial products: fp32 accuracy, 0.375 x the pipe time (64 x 12 heads x 256
-        # tokens x 64: 140 -> 111 us; head_dim 128 needs one wave per SIMD there and measured slower, 458 vs 516 us: fp32 kernel)
-        return "az_attention_f16x2_f32" if FP32_MFMA == "f16x2" and ATTN_H2 and bounded else "az_attention_x3_f32"
+        # tokens x 64: 140 -> 111 us; head_dim 128 needs one wave per SIMD there and measured slower, 458 vs 516 us: fp32 kernel).
+        # The f16x2 form only on normalised q / k: un-normalised keys (ADM, qk_norm=False ViTs) reach its |k| < 4094 limit.
+        return "az_attention_f16x2_f32" if FP32_MFMA == "f16x2" and ATTN_H2 and qk_normed else "az_attention_x3_f32"
     return "az_attention_f32"
 
 
@@ -344,6 +373,7 @@ class ConvWeights:
             self.bias[: self.cout] = bias.detach().to(device=bld.device, dtype=torch.float32)
         self._forms: dict = {}  # packed layouts, made on first use
         self._amax = None
+        self._h2_range = None
 
     def _form(self, key, numel: int, dtype: torch.dtype, pack: str, *args) -> torch.Tensor:
         r"""The layout ``key``: a (numel,) tensor written by the C packing entry ``pack(dst, w, *args, stream)``, made once."""
@@ -386,6 +416,16 @@ class ConvWeights:
         if self._amax is None:
             self._amax = float(self.w.abs().max()) if self.w.numel() else 0.0
         return float(_lib.lib().az_f16x2_weight_scale(self._amax, int(winograd)))
+
+    def h2_range(self) -> bool:
+        r"""Every output row's largest |w| within 2^16 of the tensor's (rows of exact zeros aside).  The f16x2 packings scale the
+        WHOLE tensor by one power of two, so a row further down has subnormal low pieces and loses precision (a fused q | k | v
+        projection whose keys carry a gain the queries give back: tests/test_gpu_magnitudes.py); such layers run bf16x3."""
+        if self._h2_range is None:
+            r = self.w.abs().amax(dim=(1, 2, 3))
+            r = r[r > 0]
+            self._h2_range = bool(r.numel() == 0 or float(r.min()) * 2.0 ** 16 >= float(r.max()))
+        return self._h2_range
 
     def direct_f16x2(self) -> torch.Tensor:
         r"""The direct layout as three IEEE half planes [wh | wl | wh / 2^11] of w * w_scale, for ``az_conv2d_f16x2_f32``."""
@@ -562,7 +602,8 @@ class Builder:
         cin_s = a.c0s + a.c1s
         lib = _lib.lib()
         ch = choose_conv(ConvLayer(ks, stride, aniso, B, hout, wout, a.c0s, a.c1s, cout, a.cout_s, up0, depth is not None, self.half,
-                                   winograd, self._source(src0), self._source(src1) if src1 is not None else None))
+                                   winograd, self._source(src0), self._source(src1) if src1 is not None else None,
+                                   self.half is not None or FP32_MFMA != "f16x2" or packed.h2_range()))
         name = ch.name
         a.weight = (packed.direct_half(self.half == torch.float16) if self.half is not None else getattr(packed, PACKED[name])()).data_ptr()
         if ch.h2:
@@ -618,8 +659,8 @@ class Builder:
         if tmp_src is not None:
             self.free(tmp_src)
         if out is not None:
-            # (a residual add of the stream joins the stream; of a bounded tensor -- y + MSA(y) of a DiT block -- stays bounded)
-            self.wrote(out, bounded=sources_bounded(src0, src1) and (res is None or res.bounded), moments=moments)
+            # (not bounded, whatever its sources: the weights set its magnitude -- Act.bounded)
+            self.wrote(out, bounded=False, moments=moments)
             out.qk_prepared = a.act == 5
         return out
 
@@ -704,7 +745,7 @@ class Builder:
         factors that are not powers of two (those are a shift inside the consuming convolution's gather)."""
         y = self.new_act(x.B, hout, wout, x.C)
         self.tape.add("az_upsample_nearest_f32", y.ptr, x.ptr, x.B, x.H, x.W, x.cs, sh, sw, hout, wout)
-        return self.wrote(y, bounded=x.bounded)
+        return self.wrote(y, bounded=False)
 
     def finish(self) -> None:
         r"""Allocates the shared split-K workspace and patches it into the recorded convs."""
@@ -840,6 +881,9 @@ class Builder:
             setattr(a, n + "_hstride", hs)
         a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
         a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, int(qk_rmsnorm), eps, norm_dim
+        # q / k RMS-normalised here or by the projection's epilogue (qk_rmsnorm is the layer's flag either way), with gains in range
+        kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, qk_weight) if qk_rmsnorm else (math.inf, math.inf)
+        qk_normed = kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX
         if qkv.qk_prepared:  # the projection's epilogue has normalised / gained / rotated q and k already (Builder.conv(qk_prep=...))
             assert order in ("nHC", "3HC")
             a.qk_rmsnorm, rope, qk_weight = 0, None, None
@@ -861,8 +905,8 @@ class Builder:
             a.mask_hstride = m8.stride(1) if m.shape[1] > 1 else 0
             self.tape.keep.append(m8)
         a._flops = 4 * qkv.B * heads * L * L * dim
-        self.tape.add(choose_attention(dim, qkv.bounded, self.half), C.byref(a), keep=[a])
-        return self.wrote(out, bounded=qkv.bounded)  # (a convex combination of the values)
+        self.tape.add(choose_attention(dim, qk_normed, self.half), C.byref(a), keep=[a])
+        return self.wrote(out, bounded=False)  # (a convex combination of the values: as large as the weights make them)
 
 
 # ------------------------------------------------------------------------------- AdaZero modulation helpers

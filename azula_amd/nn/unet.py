@@ -110,7 +110,9 @@ class UNetBlock(nn.Module):
         else:
             n_ = bld.row_norm(x, 0 if self.norm_kind == "layer" else 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
         c0, c3 = self.ffn[0], self.ffn[3]
-        h1 = bld.conv(n_, bld.pack_conv(c0.weight, c0.bias), c0.out_channels, act=1, periodic=self.periodic)
+        # (its moments bound the maximum of SiLU(conv) for the second convolution's f16x2 scale: no pass over the hidden tensor)
+        h1 = bld.conv(n_, bld.pack_conv(c0.weight, c0.bias), c0.out_channels, act=1, periodic=self.periodic,
+                      gn_stats=engine.moments_for_scale())
         bld.free(n_)
         y = bld.conv(h1, bld.pack_conv(c3.weight, c3.bias), c3.out_channels, gate=abc, gate_off=2 * cs, gate_bstride=bstride,
                      res=x, periodic=self.periodic, gn_stats=self.norm_kind == "group")  # feeds the next block's norm

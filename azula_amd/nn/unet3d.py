@@ -79,8 +79,8 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
     Ho = (Hin + 2 * (kh // 2) - kh) // sh_ + 1
     Wo = (Win + 2 * (kw // 2) - kw) // sw_ + 1
     out = new_vol(bld, x.B, Do, Ho, Wo, cout)
-    # (bounded sources and no residual of the stream: the sum of the taps is bounded by the weights, like a 2-D convolution's output)
-    bounded = x.bounded and (x1 is None or x1.bounded) and (res is None or res.bounded)
+    # (a convolution's output is not bounded, whatever its sources: the weights set its magnitude -- engine.Act.bounded)
+    bounded = False
     taps = [p] + [j for j in range(kd) if j != p]  # centre first: it exists for every output plane and writes it
     packs = {j: bld.pack_conv(w[:, :, j], bias if j == p else None, cin0=x.C if x1 is not None else None) for j in taps}
     # ---- ONE launch per depth tap for all planes of all samples (AzConvArgs.depth: the kernels' loaders take a plane whose
@@ -109,7 +109,7 @@ def conv3d(bld: Builder, x: Vol, conv, *, stride=1, periodic: bool = False, x1: 
                             if cnt > 0:
                                 bld.tape.add("az_token_copy_f32", x1u.buf.data_ptr() + 4 * b_ * Din * n, 2, half_,
                                              x1.buf.data_ptr() + 4 * b_ * x1.D * n, 1, 0, 1, cnt, n)
-                bld.wrote(x1u.act, bounded=x1.bounded)
+                bld.wrote(x1u.act, bounded=False)  # (a resampled copy: not a normalisation's output)
                 src1 = x1u
             kw_ = dict(src1=planes(src1), up1=(uh_, uw_), hin=Hin, win=Win)
         full = out if sd_ == 1 else new_vol(bld, x.B, Din, Ho, Wo, cout)  # (a strided depth axis: every plane, then every sd-th kept)
@@ -190,7 +190,7 @@ def upsample3d_nearest(bld: Builder, x: Vol, factors, like: Vol) -> Vol:
     n = like.H * like.W * x.cs
     idx_dev = idx.to(bld.device)
     bld.tape.add("az_gather_rows_f32", out.buf.data_ptr(), wide.buf.data_ptr(), idx_dev.data_ptr(), x.B * like.D, n, x.B * x.D, keep=[idx_dev])
-    bld.wrote(out.act, bounded=x.bounded)
+    bld.wrote(out.act, bounded=False)  # (a resampled copy: not a normalisation's output)
     if wide is not planes:
         bld.free(wide)
     return out

@@ -406,9 +406,12 @@ int az_conv2d_winograd_x3_f32(const AzConvArgs* args, az_stream_t stream);
  * gracefully at the small end.  DOMAIN (stated, unlike bf16x3's, which is all of fp32): |x| * AZ_F16X2_IN_SCALE < 65520 --
  * activations up to ~1.0e6 (Winograd form: 4-pixel sums of the input, i.e. inputs up to ~2.6e5); beyond it a piece is Inf and the
  * outputs that depend on it are NaN (never a silently wrong finite value).  At the small end every operand carries an absolute
- * error <= 2^-36 / AZ_F16X2_IN_SCALE = 2.3e-10 (full relative precision from |x| >= 1e-3 on).  That range is for inputs whose
- * magnitude is bounded by construction (behind a normalisation); for any other input pass the sources' largest magnitude
- * (in_absmax0 / in_absmax1, from az_absmax_f32) and the kernel picks the scale itself: no stated range.  bf16x3 stays selectable
+ * error <= 2^-36 / AZ_F16X2_IN_SCALE = 2.3e-10 (full relative precision from |x| >= 1e-3 on).  The host takes that fixed range
+ * only for the DIRECT output of a normalisation: a modulated norm is bounded by |1 + a| sqrt(n) + |b| per element (n = the
+ * channels / group size it averages over), a limit that remains in force and is not checked per step.  The output of a
+ * convolution or attention is never taken on the fixed scale, whatever its inputs: its magnitude is set by the weights.  For
+ * every other input pass the sources' largest magnitude (in_absmax0 / in_absmax1, from az_absmax_f32 or bounded from the
+ * producer's moments by az_absmax_from_moments_f32) and the kernel picks the scale itself: no stated range.  bf16x3 stays selectable
  * (AZ_FP32_MFMA=bf16x3).  `weight` = az_pack_conv_weight_f16x2_f32 / az_winograd_pack_filter_f16x2_f32 output (the layouts of the x3
  * packings: three 2-byte planes), `w_scale` the scale given to that packing; everything else as the x3 entries.  Same reference
  * op: azula/nn/layers.py:25-68 ConvNd / torch.nn.Linear on tokens (azula/nn/dit.py:88-93, azula/nn/attention.py:45-46). */
@@ -500,8 +503,11 @@ int az_attention_x3_f32(const AzAttnArgs* args, az_stream_t stream);
 /* The same kernel in the f16x2 form (see az_conv2d_f16x2_f32): three partial products per contraction on v_mfma_f32_32x32x16_f16 --
  * the keys as [kh | kl | kh / 2^11] of k * 2^4 and the queries as [h | l] of q / 2^4 (the scales cancel); the probabilities (at most
  * 2^8 under the lazy running maximum) as three pieces of p * 2^6, the values as two of v / 2^4 (1 / 4 folded into the final 1 / l).
- * Softmax, norms, gains, RoPE in fp32 as before.  Domain: |k| < 4094, |v| and |q * scale * log2 e| < 1.0e6 (beyond: NaN).  Same
- * reference op: torch SDPA behind azula/nn/attention.py:89-104, plugins/adm/_src/unet.py:338-379.                          */
+ * Softmax, norms, gains, RoPE in fp32 as before.  Domain: |k| < 4094, |v| and |q * scale * log2 e| < 1.0e6 (beyond: NaN).  The
+ * host takes this entry only for RMS-normalised q / k (in the kernel or the projection epilogue), whose elements are bounded by
+ * sqrt(d) max |gain| -- checked at plan time against half of these limits; un-normalised keys run az_attention_x3_f32 (all of
+ * fp32).  There is no dynamic scale for v: |v| < 1.0e6 remains a stated limit.  Same reference op: torch SDPA behind
+ * azula/nn/attention.py:89-104, plugins/adm/_src/unet.py:338-379.                                                       */
 int az_attention_f16x2_f32(const AzAttnArgs* args, az_stream_t stream);
 int az_attention_bf16_f32(const AzAttnArgs* args, az_stream_t stream);
 int az_attention_f16_f32(const AzAttnArgs* args, az_stream_t stream);

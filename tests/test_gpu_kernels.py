@@ -942,11 +942,13 @@ def test_absmax(az, n):
     assert torch.isfinite(slots).all() and slots.max().item() == x[:n].abs().max().item()
 
 
+@pytest.mark.parametrize("act", [0, 1])
 @pytest.mark.parametrize("mode", [True, "wh2", "x3"])
-def test_absmax_from_the_producers_moments(az, mode, monkeypatch):
+def test_absmax_from_the_producers_moments(az, mode, act, monkeypatch):
     """az_absmax_from_moments_f32: the GroupNorm partial moments a convolution leaves of its output (AzConvArgs.gn_quads: Winograd
     epilogue or split-K combine) bound its largest magnitude from above -- |x| <= |mean| + sqrt(M2) per record -- within sqrt(n) of
-    the true maximum, so that a consumer's f16x2 activation scale needs no pass over the tensor (engine.Builder.absmax_of)."""
+    the true maximum, so that a consumer's f16x2 activation scale needs no pass over the tensor (engine.Builder.absmax_of).
+    ``act`` = 1: SiLU in the epilogue (the UNet FFN's hidden tensor) -- the bound holds for the STORED, post-activation values."""
     from azula_amd import _lib, engine
     from azula_amd.engine import Act, Builder
 
@@ -958,7 +960,7 @@ def test_absmax_from_the_producers_moments(az, mode, monkeypatch):
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)
     bld = Builder(torch.device("cuda"))
     xa = Act(to_nhwc(dev(x)).reshape(-1), B, H, W, Cin, Cin, True)
-    y = bld.conv(xa, bld.pack_conv(dev(w), None), Cout, winograd=mode, gn_stats=True)
+    y = bld.conv(xa, bld.pack_conv(dev(w), None), Cout, winograd=mode, gn_stats=True, act=act)
     if mode == "x3":  # the direct kernels leave moments from their split-K combine only
         d = [k for k in bld.tape.keep if hasattr(k, "_flops")][-1]
         assert d.splitk > 1 or y.gn_quads is None
@@ -969,6 +971,9 @@ def test_absmax_from_the_producers_moments(az, mode, monkeypatch):
     bld.finish()
     bld.tape.run()
     out = from_nhwc(y.buf.reshape(B, H, W, Cout), Cout)
+    ref = F.conv2d(x.double(), w.double(), None, padding=1)
+    ref = F.silu(ref) if act == 1 else ref
+    assert max_err(out, ref) < 1e-5 * ref.abs().max().item()  # (what is stored is the activation's output)
     true_max, bound = out.abs().max().item(), slots.max().item()
     n = out.numel() * 4 // y.gn_quads[0].numel()  # elements per record
     print(mode, "max |y|", true_max, "bound from the moments", bound, "elements per record", n)
@@ -1020,6 +1025,74 @@ def test_f16x2_domain(az, mode):
     far = torch.ones(B, Cout, H, W, dtype=torch.bool)
     far[:, :, 5:12, 5:12] = False  # (the Winograd tiles touching that pixel turn NaN as a whole)
     assert torch.isfinite(out[far]).all() and max_err(out[far], ref[far]) < conv_tol(Cin, 3, True)
+
+
+# The f16x2 fixed activation scale's limits (include/azula_amd.h): the direct form splits every activation, |x| * AZ_F16X2_IN_SCALE
+# < 65520; the Winograd form splits V = B^T d B, whose largest element is a +-1 sum of four inputs (rows / columns 1 and 2 of the
+# 4 x 4 patch: B^T row 1 = (0, 1, 1, 0)), so a 2 x 2 block of equal inputs at patch offset (1, 1) reaches it with a quarter of the value
+F16X2_LIMIT = {"h2": 65520.0 / 0.0625, "wh2": 65520.0 / 0.0625 / 4}
+
+
+@pytest.mark.parametrize("mode", ["h2", "wh2"])
+@pytest.mark.parametrize("frac", [0.95, 1.05])
+def test_f16x2_fixed_scale_boundary(az, mode, frac):
+    """The fixed-scale f16x2 kernels at 0.95 x and 1.05 x their stated limit, against fp64: inside, the error is at fp32 level
+    (<= 3e-6 of the reference's max); outside, exactly the outputs that read the offending value (the direct form: the 3 x 3
+    window of the pixel; the Winograd form: the 2 x 2 output tile whose patch sum overflows) are NaN, and every other output is
+    finite and as accurate as inside."""
+    from azula_amd.engine import Act, Builder
+
+    g = torch.Generator().manual_seed(16)
+    B, Cin, Cout, H, W = 1, 64, 64, 16, 16
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    v = frac * F16X2_LIMIT[mode]
+    if mode == "h2":
+        x[0, 3, 8, 8] = -v
+        hit = (slice(7, 10), slice(7, 10))
+    else:  # rows / columns 8, 9 = offsets 1, 2 of the patch of output tile (4, 4), which covers input rows / columns 7 .. 10
+        x[0, 3, 8:10, 8:10] = v
+        hit = (slice(8, 10), slice(8, 10))
+    bld = Builder(torch.device("cuda"))
+    xa = Act(to_nhwc(dev(x)).reshape(-1), B, H, W, Cin, Cin, True)
+    xa.bounded = True
+    y = bld.conv(xa, bld.pack_conv(dev(w), None), Cout, winograd=mode)
+    assert bld.tape.ops[-1][2] == WINO_NAME[mode] and not bld.tape.keep[-1].in_absmax0  # (the fixed scale)
+    bld.finish()
+    bld.tape.run()
+    out = from_nhwc(y.buf.reshape(B, H, W, Cout), Cout).double().cpu()
+    ref = F.conv2d(x.double(), w.double(), None, padding=1)
+    inside = torch.ones_like(ref, dtype=torch.bool)
+    if frac > 1:
+        inside[:, :, hit[0], hit[1]] = False
+        assert torch.isnan(out[~inside]).all(), out[~inside]
+    assert torch.isfinite(out[inside]).all()
+    err, sc = (out[inside] - ref[inside]).abs().max().item(), ref[inside].abs().max().item()
+    print(mode, frac, "relative error", err / sc)
+    assert err <= 3e-6 * sc, (err, sc)
+
+
+@pytest.mark.parametrize("mode", ["h2", "wh2"])
+def test_f16x2_fixed_scale_whole_tensor_near_the_limit(az, mode):
+    """Every activation at 0.9 x the limit with random signs (the Winograd form: 2 x 2 blocks of one sign occur in many patches, so
+    patch sums reach 0.9 x its limit): finite, within 3e-6 of the fp64 reference's max."""
+    from azula_amd.engine import Act, Builder
+
+    g = torch.Generator().manual_seed(17)
+    B, Cin, Cout, H, W = 2, 64, 64, 16, 16
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)
+    x = torch.sign(torch.randn(B, Cin, H, W, generator=g)) * (0.9 * F16X2_LIMIT[mode])
+    bld = Builder(torch.device("cuda"))
+    xa = Act(to_nhwc(dev(x)).reshape(-1), B, H, W, Cin, Cin, True)
+    y = bld.conv(xa, bld.pack_conv(dev(w), None), Cout, winograd=mode)
+    bld.finish()
+    bld.tape.run()
+    out = from_nhwc(y.buf.reshape(B, H, W, Cout), Cout).double().cpu()
+    ref = F.conv2d(x.double(), w.double(), None, padding=1)
+    assert torch.isfinite(out).all()
+    err, sc = (out - ref).abs().max().item(), ref.abs().max().item()
+    print(mode, "relative error", err / sc)
+    assert err <= 3e-6 * sc, (err, sc)
 
 
 @pytest.mark.parametrize("mode", ["x3", "wx3"])

@@ -14,9 +14,16 @@ pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 
-@pytest.mark.parametrize("B,H,T,D", [(2, 4, 16, 16), (1, 2, 64, 32), (2, 3, 256, 64), (1, 2, 100, 64), (1, 1, 1024, 64), (1, 2, 40, 128), (2, 2, 72, 80)])
-@pytest.mark.parametrize("order,rms", [("nHC", True), ("nHC", False), ("H3C", False), ("3HC", False)])
-@pytest.mark.parametrize("x3", [True, False, "f16x2"])
+ATTN_SHAPES = [(2, 4, 16, 16), (1, 2, 64, 32), (2, 3, 256, 64), (1, 2, 100, 64), (1, 1, 1024, 64), (1, 2, 40, 128), (2, 2, 72, 80)]
+ATTN_LAYOUTS = [("nHC", True), ("nHC", False), ("H3C", False), ("3HC", False)]
+# f16x2 mode with un-normalised q / k at a head size the x3 / f16x2 kernels serve: the engine routes these to az_attention_x3_f32
+# (test_attention_kernel_unnormalised_keys); every other combination keeps its entry
+ATTN_CASES = [pytest.param(B, H, T, D, order, rms, x3, id=f"{x3}-{order}-{rms}-{B}-{H}-{T}-{D}")
+              for x3 in (True, False, "f16x2") for order, rms in ATTN_LAYOUTS for B, H, T, D in ATTN_SHAPES
+              if not (x3 == "f16x2" and not rms and D <= 80)]
+
+
+@pytest.mark.parametrize("B,H,T,D,order,rms,x3", ATTN_CASES)
 def test_attention_kernel(monkeypatch, B, H, T, D, order, rms, x3):
     """az_attention_x3_f32 (the contractions as 3 x bf16 pieces / 6 partial products on the bf16 MFMA), az_attention_f16x2_f32
     (2 x f16 pieces / 3 partial products on the f16 MFMA) and az_attention_f32 (fp32 MFMA), all against torch's SDPA at the same bound."""
@@ -49,6 +56,36 @@ def test_attention_kernel(monkeypatch, B, H, T, D, order, rms, x3):
     bld.tape.run()
     got = out.buf.reshape(B, T, H * D)
     assert max_err(got, ref) < 2e-5, max_err(got, ref)
+
+
+@pytest.mark.parametrize("B,H,T,D", [s for s in ATTN_SHAPES if s[3] <= 80])
+@pytest.mark.parametrize("order", ["nHC", "H3C", "3HC"])
+def test_attention_kernel_unnormalised_keys(monkeypatch, B, H, T, D, order):
+    """f16x2 mode, q / k without RMS norm (ADM, ViT(qk_norm=False)): the engine takes az_attention_x3_f32, whose domain is all of
+    fp32, even for a bounded q | k | v tensor -- un-normalised keys reach the f16x2 form's |k| < 4094.  Both entries on the same
+    data against torch's SDPA: the x3 entry the plan holds, and the f16x2 entry itself (its arithmetic inside its domain)."""
+    from azula_amd import _lib, engine
+    from azula_amd.engine import Act, Builder
+
+    monkeypatch.setattr(engine, "ATTN_X3", True)
+    monkeypatch.setattr(engine, "FP32_MFMA", "f16x2")
+    g = torch.Generator().manual_seed(B * T + D)
+    q, k, v = (torch.randn(B, H, T, D, generator=g) for _ in range(3))
+    if order in ("nHC", "3HC"):
+        qkv = torch.stack((q, k, v), dim=0).permute(1, 3, 0, 2, 4).reshape(B, T, 3 * H * D)  # (n H C)
+    else:
+        qkv = torch.stack((q, k, v), dim=2).permute(0, 3, 1, 2, 4).reshape(B, T, 3 * H * D)  # (H 3 C)
+    ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T, H * D)
+    for name in ("az_attention_x3_f32", "az_attention_f16x2_f32"):
+        bld = Builder(torch.device("cuda"))
+        act = Act(qkv.cuda().contiguous().reshape(-1), B, T, 1, 3 * H * D, 3 * H * D, True)
+        act.bounded = True
+        out = bld.attention(act, H, order, False, 1.0 / math.sqrt(D))
+        assert [n for _, _, n in bld.tape.ops] == ["az_attention_x3_f32"]
+        bld.tape.ops[0] = (getattr(_lib.lib(), name), bld.tape.ops[0][1], name)
+        bld.tape.run()
+        got = out.buf.reshape(B, T, H * D)
+        assert max_err(got, ref) < 2e-5, (name, max_err(got, ref))
 
 
 @pytest.mark.parametrize("B,H,T,D", [(2, 4, 48, 32), (2, 3, 288, 64), (1, 2, 100, 128), (3, 12, 64, 64)])
@@ -104,6 +141,106 @@ def test_qk_preparation_in_the_projection_epilogue(B, H, T, D, rms, gains, rope,
     tol = 3e-5 if half is None else 3e-2
     e_ref, e_ab = max_err(outs[True], ref), max_err(outs[True], outs[False])
     assert e_ref < tol and e_ab < tol, (e_ref, e_ab)
+
+
+ATTN_FORMS = ("az_attention_f16x2_f32", "az_attention_x3_f32", "az_attention_f32")
+ATTN_H2_K_LIMIT = 4094.0  # include/azula_amd.h: |k| < 4094, |v| and |q * scale * log2 e| < 1.0e6 for az_attention_f16x2_f32
+ATTN_H2_V_LIMIT = 65520.0 * 16  # (the values enter as two half pieces of v / 2^4)
+ATTN_H2_QS_LIMIT = 1.0e6
+
+
+def _attention_cases(case, B, H, T, D, g):
+    r"""(q, k, v, mask, the (B, H, T, D) outputs that must turn NaN in the f16x2 form or None) for one magnitude case; fp64 tensors."""
+    q, k, v = (torch.randn(B, H, T, D, generator=g, dtype=torch.float64) for _ in range(3))
+    mask, bad = None, None
+    scale = 1.0 / math.sqrt(D)
+    if case in ("k_in", "k_out"):  # one key element at 0.95 / 1.05 x the limit, the rest of its row O(1), queries small
+        k[0, 1, 5, 3] = (0.95 if case == "k_in" else 1.05) * ATTN_H2_K_LIMIT
+        q *= 1e-3
+        if case == "k_out":  # every query of head (0, 1) reads that key: all its outputs
+            bad = torch.zeros(B, H, T, D, dtype=torch.bool)
+            bad[0, 1] = True
+    elif case in ("v_half", "v_in", "v_out"):  # values near the limit in one row (v_half: the whole tensor at 0.5 x)
+        if case == "v_half":
+            v = torch.sign(v) * (0.5 * ATTN_H2_V_LIMIT)
+        else:
+            v[0, 0, 7, 2] = (0.95 if case == "v_in" else 1.05) * ATTN_H2_V_LIMIT
+        if case == "v_out":  # channel 2 of every output of head (0, 0)
+            bad = torch.zeros(B, H, T, D, dtype=torch.bool)
+            bad[0, 0, :, 2] = True
+    elif case in ("qs_in", "qs_out"):  # one query channel at the limit of q * scale * log2 e, whose key channel is zero: scores unchanged
+        q[1, 0, 9, 4] = (0.95 if case == "qs_in" else 1.05) * ATTN_H2_QS_LIMIT / (scale * math.log2(math.e))
+        k[:, :, :, 4] = 0.0
+        if case == "qs_out":  # that query's row
+            bad = torch.zeros(B, H, T, D, dtype=torch.bool)
+            bad[1, 0, 9] = True
+    elif case == "one_hot":  # scores along one channel whose keys are s / T: consecutive scores 100 apart, so every row is one-hot
+        k[:, :, :, 0] = torch.arange(T, dtype=torch.float64) / T  # (on the last key for q > 0, on the first for q < 0)
+        q.zero_()
+        q[:, :, :, 0] = torch.where(torch.rand(B, H, T, generator=g) < 0.5, -1.0, 1.0).double() * (101.0 * T / scale)
+        k[:, :, :, 1:] = 0.0
+    elif case == "near_tie":  # pairs of keys that differ by 1e-6: two scores per row within 1e-6, sharp rows
+        k[:, :, 1::2] = k[:, :, 0::2][:, :, : T // 2] + 1e-6 * torch.randn(B, H, T // 2, D, generator=g, dtype=torch.float64)
+        q = q * 4.0
+    elif case == "masked_tiles":  # keys 0 .. 63 (a whole key tile) and the ragged last tile masked out for every query
+        mask = torch.rand(T, T, generator=g) < 0.7
+        mask[:, :64] = False
+        mask[:, 64 * (T // 64):] = False
+        mask[:, 64] = True  # (every query keeps a key: an all-masked row is NaN in the reference too)
+    return q, k, v, mask, bad
+
+
+@pytest.mark.parametrize("D", [16, 32, 64, 80])
+@pytest.mark.parametrize("case", ["k_in", "k_out", "v_half", "v_in", "v_out", "qs_in", "qs_out", "one_hot", "near_tie", "masked_tiles"])
+def test_attention_magnitudes(monkeypatch, case, D):
+    """The three fp32 attention forms on the same data at the f16x2 form's stated limits (include/azula_amd.h), T = 141 (not a
+    multiple of a tile), against fp64 SDPA: inside a limit every form within 2e-5 of max |v|; outside it the f16x2 form turns
+    exactly the outputs that read the offending value into NaN and keeps the others, while the x3 and fp32 forms (whose domain is all
+    of fp32) stay correct; saturated (one-hot) and near-tie softmax rows and fully masked key tiles in every form."""
+    from azula_amd import _lib, engine
+    from azula_amd.engine import Act, Builder
+
+    monkeypatch.setattr(engine, "FP32_MFMA", "f16x2")
+    B, H, T = 2, 2, 141
+    g = torch.Generator().manual_seed(D * 31 + len(case))
+    q, k, v, mask, bad = _attention_cases(case, B, H, T, D, g)
+    ref = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)  # fp64, scale 1 / sqrt(D)
+    qkv = torch.stack((q, k, v), dim=0).permute(1, 3, 0, 2, 4).reshape(B, T, 3 * H * D).float()  # (n H C)
+    for name in ATTN_FORMS:
+        bld = Builder(torch.device("cuda"))
+        act = Act(qkv.cuda().contiguous().reshape(-1), B, T, 1, 3 * H * D, 3 * H * D, True)
+        act.bounded = True
+        out = bld.attention(act, H, "nHC", False, 1.0 / math.sqrt(D), mask=mask)
+        assert bld.tape.ops[0][2] == "az_attention_x3_f32"  # (un-normalised keys: never the f16x2 form by choice)
+        bld.tape.ops[0] = (getattr(_lib.lib(), name), bld.tape.ops[0][1], name)
+        bld.tape.run()
+        got = out.buf.reshape(B, T, H, D).permute(0, 2, 1, 3).double().cpu()
+        ok = torch.ones(B, H, T, D, dtype=torch.bool) if bad is None or name != ATTN_FORMS[0] else ~bad
+        if bad is not None and name == ATTN_FORMS[0]:
+            assert torch.isnan(got[bad]).all(), (name, case)
+        assert torch.isfinite(got[ok]).all(), (name, case)
+        err, sc = (got[ok] - ref[ok]).abs().max().item(), v.abs().max().item()
+        print(name, case, D, "error / max|v|", err / sc)
+        assert err <= 2e-5 * sc, (name, case, err, sc)
+
+
+def test_attention_routing_by_qk_normalisation(monkeypatch):
+    """engine: the f16x2 attention form only for RMS-normalised q / k whose gains keep sqrt(d) max |g| inside its key limit
+    (un-normalised keys: ADM, ViT(qk_norm=False) -> the x3 form, whose domain is all of fp32)."""
+    from azula_amd import engine
+    from azula_amd.engine import Act, Builder
+
+    monkeypatch.setattr(engine, "FP32_MFMA", "f16x2")
+    B, H, T, D = 1, 2, 32, 64
+    qkv = torch.zeros(B * T * 3 * H * D, device="cuda")
+    ones = torch.ones(D, device="cuda")
+    for rms, gains, name in ((True, None, "az_attention_f16x2_f32"), (False, None, "az_attention_x3_f32"),
+                             (True, (ones, ones * 100), "az_attention_f16x2_f32"), (True, (ones, ones * 1000), "az_attention_x3_f32")):
+        bld = Builder(torch.device("cuda"))
+        act = Act(qkv, B, T, 1, 3 * H * D, 3 * H * D, True)
+        act.bounded = True
+        bld.attention(act, H, "nHC", rms, 1.0 / math.sqrt(D), qk_weight=gains)
+        assert bld.tape.ops[0][2] == name, (rms, gains is not None and gains[1][0].item())
 
 
 def test_attention_spiked_scores():

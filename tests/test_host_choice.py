@@ -42,9 +42,20 @@ CONV_TABLE = [  # (row, switches, layer, entry, dynamic scale)
     ("override_false", {}, dict(HEAD, winograd=False), F32, False),
     ("override_false_bounded", {}, dict(HEAD, winograd=False, bounded=True), F32, False),
     ("two_sources_one_unbounded", {}, dict(B=4, H=64, W=64, cin=512, cin1=256, cout=256, ks=3, bounded=True), WX3, False),
+    # conv-over-conv sources (a convolution's / attention's output is never bounded: Act.bounded): the UNet FFN's second 3 x 3
+    # convolution over SiLU(conv), whose producer left moments; the same without them on a small map; a DiT-B/2 token GEMM
+    # behind attention / an FFN at batch 64 (16384 tokens: the measured pass pays) and at batch 2 (it does not)
+    ("ffn_second_conv_moments", {}, dict(HEAD, moments=True), WH2, True),
+    ("ffn_second_conv_moments_bf16x3", dict(FP32_MFMA="bf16x3"), dict(HEAD, moments=True), WX3, False),
+    ("conv_over_conv_small_map", {}, dict(B=1, H=16, W=16, cin=64, cout=64, ks=3), WX3, False),
+    ("token_gemm_after_attention", {}, dict(B=64, H=256, W=1, cin=768, cout=768, ks=1), H2, True),
+    ("token_gemm_after_attention_b2", {}, dict(B=2, H=256, W=1, cin=768, cout=768, ks=1), X3, False),
+    # weights whose rows span more than 2^16 (ConvWeights.h2_range): bf16x3, bounded source or not
+    ("weight_range_bounded", {}, dict(HEAD, bounded=True, w_h2=False), WX3, False),
+    ("weight_range_unbounded", {}, dict(SKIP, moments=True, w_h2=False), X3, False),
 ]
 
-ATTN_TABLE = [  # (switches, head size, bounded, half, entry)
+ATTN_TABLE = [  # (switches, head size, q / k normalised within the f16x2 key limit, half, entry)
     *[({}, 64, b, None, "az_attention_f16x2_f32" if b else "az_attention_x3_f32") for b in (True, False)],
     *[(dict(FP32_MFMA="bf16x3"), 64, b, None, "az_attention_x3_f32") for b in (True, False)],
     *[(dict(FP32_MFMA=m), 128, b, None, "az_attention_f32") for m in ("f16x2", "bf16x3", "native") for b in (True, False)],
@@ -66,10 +77,11 @@ def source(B, H, W, C, bounded=False, affine=False, moments=False):
     return ConvSource(C, B * H * W * pad4(C), bounded, affine, False, moments)
 
 
-def layer(B, H, W, cin, cout, ks, stride=1, cin1=0, bounded=False, moments=False, depth=False, winograd=None, half=None, affine=False):
+def layer(B, H, W, cin, cout, ks, stride=1, cin1=0, bounded=False, moments=False, depth=False, winograd=None, half=None, affine=False,
+          w_h2=True):
     hout, wout = (H + 2 * (ks // 2) - ks) // stride + 1, (W + 2 * (ks // 2) - ks) // stride + 1
     return ConvLayer(ks, stride, False, B, hout, wout, pad4(cin), pad4(cin1), cout, pad4(cout), 0, depth, half, winograd,
-                     source(B, H, W, cin, bounded, affine, moments), source(B, H, W, cin1) if cin1 else None)
+                     source(B, H, W, cin, bounded, affine, moments), source(B, H, W, cin1) if cin1 else None, w_h2)
 
 
 @pytest.mark.parametrize("row, env, spec, name, dyn", CONV_TABLE, ids=[r[0] for r in CONV_TABLE])
@@ -80,10 +92,45 @@ def test_choose_conv(monkeypatch, row, env, spec, name, dyn):
     assert ch.h2 == (name in engine.H2_NAMES)
 
 
-@pytest.mark.parametrize("env, dim, bounded, half, name", ATTN_TABLE)
-def test_choose_attention(monkeypatch, env, dim, bounded, half, name):
+@pytest.mark.parametrize("env, dim, qk_normed, half, name", ATTN_TABLE)
+def test_choose_attention(monkeypatch, env, dim, qk_normed, half, name):
     switches(monkeypatch, env)
-    assert choose_attention(dim, bounded, half) == name
+    assert choose_attention(dim, qk_normed, half) == name
+
+
+def qkv_act(bld, B=1, T=32, H=2, D=64):
+    a = bld.new_act(B, T, 1, 3 * H * D)
+    return bld.wrote(a, bounded=True)  # (even a bounded projection: the routing reads q / k normalisation, not Act.bounded)
+
+
+@pytest.mark.parametrize("rms, gk, gq, name", [
+    (True, None, None, "az_attention_f16x2_f32"),  # azula ViT / DiT with qk_norm: |k| <= sqrt(64) = 8
+    (False, None, None, "az_attention_x3_f32"),  # ADM, ViT(qk_norm=False): un-normalised keys
+    (True, 200.0, 1.0, "az_attention_f16x2_f32"),  # 8 x 200 = 1600 < 4094 / 2
+    (True, 300.0, 1.0, "az_attention_x3_f32"),  # 8 x 300 = 2400: inside 4094 but not with the factor 2 to spare
+    (True, 1.0, 1e6, "az_attention_x3_f32"),  # |q * scale * log2 e| up to 8 x 1e6 / 8 x 1.44 > 1e6 / 2
+])
+def test_attention_routing_reads_the_qk_normalisation(bld, rms, gk, gq, name):
+    D = 64
+    qk_weight = None if gk is None else (torch.full((D,), gq), torch.full((D,), -gk))
+    out = bld.attention(qkv_act(bld, D=D), 2, "nHC", rms, 1.0 / D ** 0.5, qk_weight=qk_weight)
+    assert ops(bld) == [name]
+    assert not out.bounded  # (attention output: a convex combination of values as large as the weights make them)
+
+
+def test_weight_range_of_the_f16x2_packing(bld):
+    w = torch.randn(8, 4, 3, 3)
+    assert bld.pack_conv(w, None).h2_range()
+    w[3] *= 1e-6  # (one row ~1e6 below the rest: beyond 2^16)
+    assert not bld.pack_conv(w, None).h2_range()
+    w[3] = 0.0  # rows of exact zeros (zero-padded heads) are exact in any packing
+    assert bld.pack_conv(w, None).h2_range()
+
+
+def test_qk_bound_of_padded_heads(bld):
+    r"""Zero-padded heads (ATTN_HEAD_DIMS): the RMS norm averages over the real size, so that is the sqrt(n) of the bound."""
+    kmax, qsmax = engine.attention_qk_bound(64, 48, 48 ** -0.5, None)
+    assert kmax == pytest.approx(48 ** 0.5) and qsmax == pytest.approx(1.4426950408889634)
 
 
 def test_choice_reads_the_switches_at_call_time(monkeypatch):
