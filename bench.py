@@ -8,6 +8,11 @@ r"""Headline benchmark: images/s of DDIMSampler(steps=64) on the ADM-shaped 256x
 A "step" of this contract is one pass of the hot path over one batch: a full 64-step DDIM
 sampling of the per-GPU batch (64 hipGraph replays), followed for N > 1 by the RCCL all-gather
 of x0.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, the W warm-up and K timed passes, --dump-outputs,
+the line.  --full adds everything else to the same line, measured after the timed region: the roofline and per-kernel
+figures of one denoise step (with the rocprofv3 PMC passes), the other arithmetic modes' samplings, the CPU baseline
+and, for N > 1, a pass with its sampling and all-gather phases fenced per rank.
 """
 
 from __future__ import annotations
@@ -548,15 +553,18 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes (roofline.traffic from the committed profile)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline / per-kernel figures, PMC traffic, the other arithmetic modes, "
+                         "the CPU baseline and (N > 1) the per-rank phase split; the --no-* options below trim this")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 PMC passes (roofline.traffic from the committed profile)")
     ap.add_argument("--denoise-steps", type=int, default=0, help="override the config's sampler steps (checks only)")
     ap.add_argument("--half", choices=["bf16", "f16"], default=None,
                     help="cast the backbone to half precision (mixed-precision mode; NOT the headline fp32 number)")
     ap.add_argument("--fp32-mfma", choices=["native", "bf16x3", "f16x2"], default=None,
                     help="how the DIRECT-kernel fp32 convs / GEMMs use the matrix pipe (default: env AZ_FP32_MFMA or bf16x3 = exact "
                          "3-piece bf16 split, 6 partial products, fp32 accumulate; native = v_mfma_f32_32x32x2_f32 everywhere)")
-    ap.add_argument("--no-native-line", action="store_true", help="skip the extra native-fp32-MFMA sampling reported beside a bf16x3 run")
+    ap.add_argument("--no-native-line", action="store_true", help="--full: skip the samplings in the other arithmetic modes")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the x0 of the last timed step to DIR/x0.npy (float32, whole node's batch; "
                          "a seeded sample of its images beyond 60 MB)")
@@ -660,10 +668,13 @@ def main() -> None:
     assert torch.isfinite(x0).all()
     dist_info = {"world_size": world, "dist_backend": None}
     if world > 1:
-        # evidence that the collective backend saw every rank (outside the timed region): one extra pass with the two
-        # phases fenced, per-rank times gathered; x0 must hold every rank's shard
-        one_pass(timings)
-        per_rank = torch.tensor([local_elapsed / args.steps * 1e3, timings["sample_ms"], timings["allgather_ms"]], device=device)
+        # evidence that the collective backend saw every rank (outside the timed region): per-rank times gathered; x0 must
+        # hold every rank's shard.  --full: one extra pass with the two phases fenced
+        per_rank = [local_elapsed / args.steps * 1e3]
+        if args.full:
+            one_pass(timings)
+            per_rank += [timings["sample_ms"], timings["allgather_ms"]]
+        per_rank = torch.tensor(per_rank, device=device)
         allr = [torch.zeros_like(per_rank) for _ in range(world)]
         dist.all_gather(allr, per_rank)
         devs = [None] * world
@@ -673,11 +684,14 @@ def main() -> None:
             "world_size": dist.get_world_size(), "dist_backend": dist.get_backend(), "ranks_seen": len(allr),
             "rank_devices": devs,
             "per_rank_ms_per_step": [round(float(t[0]), 3) for t in allr],
-            "per_rank_sample_ms": [round(float(t[1]), 3) for t in allr],
-            "allgather_ms": round(max(float(t[2]) for t in allr), 3),
-            "allgather_bytes_per_rank": x0.numel() // world * 4,
             "collective": "all_gather_into_tensor(x0) once per sampling; none inside the loop",
         }
+        if args.full:
+            dist_info.update({
+                "per_rank_sample_ms": [round(float(t[1]), 3) for t in allr],
+                "allgather_ms": round(max(float(t[2]) for t in allr), 3),
+                "allgather_bytes_per_rank": x0.numel() // world * 4,
+            })
 
     if world > 1:
         # every collective of the bench is done: ranks > 0 leave now instead of idling in a barrier while rank 0 profiles
@@ -713,8 +727,9 @@ def main() -> None:
             "host": host_info(),
         }
         out["tolerance"] = tolerance_statement(args)
-        out.update(roofline_report(sampler, device, args, world, ms_per_step / cfg["steps"]))
-        if _engine.FP32_MFMA != "native" and not args.half and world == 1 and not args.no_native_line:
+        if args.full:
+            out.update(roofline_report(sampler, device, args, world, ms_per_step / cfg["steps"]))
+        if args.full and _engine.FP32_MFMA != "native" and not args.half and world == 1 and not args.no_native_line:
             # the other modes beside the one that was timed (reviewer's conditions: the all-native line since round 3; both piece modes
             # since f16x2 became selectable): the same workload, same seed, two samplings after one warm-up, same process
             mode_was = _engine.FP32_MFMA
@@ -744,7 +759,7 @@ def main() -> None:
                     torch.cuda.empty_cache()
                 finally:
                     _engine.FP32_MFMA = mode_was
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(den, cfg)
             out["speedup_vs_cpu"] = round(images_per_s / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)

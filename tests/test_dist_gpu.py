@@ -129,3 +129,25 @@ def test_bench_launches_its_own_ranks():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["dist"]["ranks_seen"] == 2 and out["dist"]["world_size"] == 2
     assert out["config"]["global_batch"] == 2 * out["config"]["per_gpu_batch"] and out["value"] > 0
+
+
+def test_bench_full_splits_the_phases_per_rank():
+    """`--full` with 2 ranks (gloo, the box's GPU shared): one extra pass with the sampling and the all-gather fenced, both
+    phases reported per rank beside the roofline of rank 0."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["AZ_DIST_BACKEND"] = "gloo"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "tiny", "--steps", "2",
+                          "--warmup", "1", "--full", "--no-pmc"], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    d = out["dist"]
+    assert d["ranks_seen"] == 2 and len(d["per_rank_ms_per_step"]) == len(d["per_rank_sample_ms"]) == 2
+    assert d["allgather_ms"] >= 0 and d["allgather_bytes_per_rank"] == 2 * 3 * 64 * 64 * 4
+    assert "roofline" in out

@@ -24,7 +24,7 @@ for m in x3 h2; do AZ_WINO=$m python tools/conv_micro.py 4 256 256 256 256 3 2 3
 echo "== bench lines (no CPU baseline / PMC / native line)" | tee -a $OUT
 for cfg in c2 c3; do
   for m in bf16x3 f16x2 bf16x3 f16x2; do
-    python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-native-line --fp32-mfma $m 2>gpurun_out/bench_${cfg}_${m}.err | python -c "
+    python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-native-line --fp32-mfma $m 2>"${OUT%/*}"/bench_${cfg}_${m}.err | python -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

@@ -30,7 +30,7 @@ done
 echo "== bench lines c5 / c6 (no CPU baseline / PMC / native line)" | tee -a $OUT
 for cfg in c5 c6; do
   for m in bf16x3 f16x2; do
-    python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-native-line --fp32-mfma $m 2>gpurun_out/bench_${cfg}_${m}.err | python -c "
+    python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-native-line --fp32-mfma $m 2>"${OUT%/*}"/bench_${cfg}_${m}.err | python -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

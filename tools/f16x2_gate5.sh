@@ -11,7 +11,7 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -v "^$" | tail -8 | te
 echo "== bench lines: AZ_F16X2_DYNAMIC=0 against 1 (no CPU baseline / PMC / other-mode lines)" | tee -a $OUT
 for cfg in c2 c5 c3 c6; do
   for d in 0 1 0 1; do
-    AZ_F16X2_DYNAMIC=$d python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-native-line 2>gpurun_out/bench_${cfg}_dyn$d.err | python -c "
+    AZ_F16X2_DYNAMIC=$d python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --no-native-line 2>"${OUT%/*}"/bench_${cfg}_dyn$d.err | python -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

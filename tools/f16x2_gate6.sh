@@ -12,7 +12,7 @@ for cfg in c5 c2 c4; do
   extra=""; [ $cfg = c4 ] && extra="--denoise-steps 4 --warmup 0 --steps 1"
   [ $cfg = c4 ] || extra="--steps 2 --warmup 1"
   for d in 0 1 0 1; do
-    AZ_F16X2_MOMENTS=$d python bench.py --config $cfg $extra --no-cpu-baseline --no-pmc --no-native-line 2>gpurun_out/bench_${cfg}_mom$d.err | python -c "
+    AZ_F16X2_MOMENTS=$d python bench.py --full --config $cfg $extra --no-cpu-baseline --no-pmc --no-native-line 2>"${OUT%/*}"/bench_${cfg}_mom$d.err | python -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

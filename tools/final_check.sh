@@ -1,5 +1,5 @@
 #!/bin/bash
-# end-of-round check on the final tree: the whole GPU suite (default mode), smoke(), the default bench.py with its wall time
+# end-of-round check on the final tree: the whole GPU suite (default mode), smoke(), bench.py --full with its wall time
 set -u
 OUT=gpurun_out/final_check.txt
 mkdir -p gpurun_out
@@ -7,8 +7,8 @@ mkdir -p gpurun_out
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -3 | tee -a $OUT
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $OUT
 SECONDS=0
-python bench.py > gpurun_out/final_bench_c2.json 2> gpurun_out/final_bench_c2.err
-echo "default bench.py: ${SECONDS} s wall" | tee -a $OUT
+python bench.py --full > "${OUT%/*}"/final_bench_c2.json 2> "${OUT%/*}"/final_bench_c2.err
+echo "bench.py --full: ${SECONDS} s wall" | tee -a $OUT
 python - <<'PY' | tee -a $OUT
 import json
 d = json.load(open("gpurun_out/final_bench_c2.json"))
