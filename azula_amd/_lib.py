@@ -84,6 +84,20 @@ class AzMultistepArgs(C.Structure):
     ]
 
 
+class AzRepaintArgs(C.Structure):
+    _fields_ = [
+        ("x_s", c_f32p),
+        ("y", c_f32p),
+        ("mask", C.c_void_p),
+        ("n_y", c_f32p),
+        ("n_x", c_f32p),
+        ("x_s_out", c_f32p),
+        ("x_t_out", c_f32p),
+        ("coef", c_f32p),
+        ("n", C.c_int64),
+    ]
+
+
 class AzLinearGroup(C.Structure):
     _fields_ = [
         ("y", c_f32p),
@@ -235,6 +249,7 @@ PROTOTYPES: dict[str, list] = {
     "az_step_begin": [vp, vp, vp, i32, c_stream],
     "az_transition_f32": [C.POINTER(AzTransitionArgs), c_stream],
     "az_multistep_f32": [C.POINTER(AzMultistepArgs), c_stream],
+    "az_repaint_f32": [C.POINTER(AzRepaintArgs), c_stream],
     "az_scale_f32": [vp, vp, vp, i64, c_stream],
     "az_silu_f32": [vp, vp, i64, c_stream],
     "az_axpby_f32": [vp, vp, vp, vp, vp, i64, i64, i32, c_stream],

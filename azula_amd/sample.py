@@ -365,6 +365,11 @@ class Sampler(abc.ABC):
         r"""True if the reference's step draws a randn_like that this configuration never reads (DDIM with eta = 0)."""
         return False
 
+    def _fused_draws(self, loop: "_FusedLoop") -> list[Tensor]:
+        r"""The buffers the captured loop draws ``randn_like`` into before each step, in the reference's generator order
+        (default: the noise the kernels read, then the unread draw that ``rng_parity`` keeps)."""
+        return [*loop.noise] + ([loop.dummy] if loop.dummy is not None else [])
+
     def _fused_upload_extra(self, loop: "_FusedLoop") -> None:
         r"""Sampler-specific device tables, refreshed together with the coefficient table."""
 
@@ -665,10 +670,8 @@ class _FusedLoop:
         self.add_input_relayout(None, self.x, self.table[0, COEF_FIELDS.index("c_in")].data_ptr())
         for g in s.progress_bar(range(0, s.steps, self.period)):
             n = min(self.period, s.steps - g)
-            for buf in self.noise:
+            for buf in s._fused_draws(self):
                 s._draw_noise(buf, out=buf)  # same generator calls, in the same order, as the reference's randn_like
-            if self.dummy is not None:
-                s._draw_noise(self.dummy, out=self.dummy)
             graph = self.graphs.get(n)
             if graph is None:  # first group of this length: run eagerly (loads code objects), then capture for the next
                 for t in self.step_tapes[:n]:

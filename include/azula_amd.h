@@ -124,6 +124,29 @@ typedef struct AzMultistepArgs {
 } AzMultistepArgs;
 int az_multistep_f32(const AzMultistepArgs* args, az_stream_t stream);
 
+/* ---- RePaint masked resample --------------------------------------------------------------------
+ * Replaces the per-iteration tensor arithmetic of RePaintSampler.step (azula/guidance/repaint.py:51-61), one pass over n
+ * elements behind each DDIM step:
+ *   x_s' = mask ? alpha_s * y + sigma_s * n_y : x_s                    -> x_s_out   (repaint.py:53-57, torch.where)
+ *   x_t' = (alpha_t / alpha_s) * x_s' + (alpha_t * sqrt(...)) * n_x    -> x_t_out   (repaint.py:59-61)
+ * Separately rounded mul / add in the reference's association order and a select (not a blend), so the result is
+ * bit-identical to the torch op sequence on the same inputs.  `coef` is a DEVICE pointer to the four host-computed 0-d values
+ * [alpha_s, sigma_s, alpha_t / alpha_s, alpha_t * sqrt((sigma_t / alpha_t)^2 - (sigma_s / alpha_s)^2)].  `mask` holds one
+ * byte per element (a contiguous bool tensor, 4-byte aligned); every float pointer is 16-byte aligned.  Either output may be
+ * NULL (not both) and either may alias x_s; n_x is read only when x_t_out != NULL (the last iteration keeps x_s' only). */
+typedef struct AzRepaintArgs {
+  const float* x_s;    /* the DDIM step's x_s                          */
+  const float* y;      /* observation, n elements                      */
+  const uint8_t* mask; /* 1 byte per element, nonzero = observed        */
+  const float* n_y;    /* randn_like(y)                                */
+  const float* n_x;    /* randn_like(x_s), or NULL without x_t_out      */
+  float* x_s_out;      /* optional: x_s'                               */
+  float* x_t_out;      /* optional: x_t'                               */
+  const float* coef;   /* DEVICE pointer, 4 floats                     */
+  int64_t n;
+} AzRepaintArgs; /* 72 bytes */
+int az_repaint_f32(const AzRepaintArgs* args, az_stream_t stream);
+
 /* y = s * x with s read from device memory (azula/denoise.py:317 c_in * x_t, generic backbones). */
 int az_scale_f32(float* y, const float* x, const float* s_dev, int64_t n, az_stream_t stream);
 
