@@ -98,6 +98,53 @@ class AzRepaintArgs(C.Structure):
     ]
 
 
+class AzCgArgs(C.Structure):
+    _fields_ = [
+        ("r0", C.c_void_p),
+        ("x0", C.c_void_p),
+        ("Ap", C.c_void_p),
+        ("x", C.c_void_p),
+        ("r", C.c_void_p),
+        ("p", C.c_void_p),
+        ("rr", C.c_void_p),
+        ("rr_out", C.c_void_p),
+        ("p_io", C.c_void_p),
+        ("out", C.c_void_p),
+        ("partial", C.c_void_p),
+        ("rows", C.c_int64),
+        ("dim", C.c_int64),
+        ("state_dtype", C.c_int32),
+        ("io_dtype", C.c_int32),
+        ("in_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class AzGmresArgs(C.Structure):
+    _fields_ = [
+        ("r0", C.c_void_p),
+        ("x0", C.c_void_p),
+        ("w", C.c_void_p),
+        ("V", C.c_void_p),
+        ("work", C.c_void_p),
+        ("H", C.c_void_p),
+        ("cs", C.c_void_p),
+        ("ss", C.c_void_p),
+        ("B", C.c_void_p),
+        ("v_io", C.c_void_p),
+        ("out", C.c_void_p),
+        ("partial", C.c_void_p),
+        ("rows", C.c_int64),
+        ("dim", C.c_int64),
+        ("iterations", C.c_int32),
+        ("j", C.c_int32),
+        ("state_dtype", C.c_int32),
+        ("io_dtype", C.c_int32),
+        ("in_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class AzLinearGroup(C.Structure):
     _fields_ = [
         ("y", c_f32p),
@@ -250,6 +297,12 @@ PROTOTYPES: dict[str, list] = {
     "az_transition_f32": [C.POINTER(AzTransitionArgs), c_stream],
     "az_multistep_f32": [C.POINTER(AzMultistepArgs), c_stream],
     "az_repaint_f32": [C.POINTER(AzRepaintArgs), c_stream],
+    "az_krylov_segments": [i64],
+    "az_cg_init": [C.POINTER(AzCgArgs), c_stream],
+    "az_cg_step": [C.POINTER(AzCgArgs), c_stream],
+    "az_gmres_init": [C.POINTER(AzGmresArgs), c_stream],
+    "az_gmres_arnoldi": [C.POINTER(AzGmresArgs), c_stream],
+    "az_gmres_finish": [C.POINTER(AzGmresArgs), c_stream],
     "az_scale_f32": [vp, vp, vp, i64, c_stream],
     "az_silu_f32": [vp, vp, i64, c_stream],
     "az_axpby_f32": [vp, vp, vp, vp, vp, i64, i64, i32, c_stream],
@@ -323,7 +376,7 @@ PROTOTYPES: dict[str, list] = {
     "az_calib_mfma_random_bf16": [vp, i32, i32, f32, f32, c_stream],
 }
 
-RESTYPES = {"az_f16x2_weight_scale": C.c_float}  # (everything else returns an int status)
+RESTYPES = {"az_f16x2_weight_scale": C.c_float, "az_krylov_segments": C.c_int64}  # (everything else returns an int status)
 
 _lock = threading.Lock()
 _lib = None

@@ -1,4 +1,6 @@
-r"""Guidance (reference ``azula/guidance``): classifier-free guidance and RePaint inpainting on the HIP path."""
+r"""Guidance (reference ``azula/guidance``): classifier-free guidance, RePaint inpainting and DiffPIR restoration on the HIP
+path."""
 
 from .cfg import CFGDenoiser  # noqa: F401
+from .diffpir import DiffPIRDenoiser  # noqa: F401
 from .repaint import RePaintSampler  # noqa: F401

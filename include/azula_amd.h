@@ -147,6 +147,67 @@ typedef struct AzRepaintArgs {
 } AzRepaintArgs; /* 72 bytes */
 int az_repaint_f32(const AzRepaintArgs* args, az_stream_t stream);
 
+/* ---- Krylov solvers: CG and GMRES ---------------------------------------------------------------------------------
+ * Replace the per-iteration tensor arithmetic of azula/linalg/solve.py; the operator calls A(.) stay with the caller.  b is
+ * (rows, dim) contiguous: one independent system per row (the reference's "...i,...i" dot products reduce over the last
+ * dimension only).  The state (x, r, p, V, ...) is kept in `state_dtype`, b / x0 / the operator input in `io_dtype`, the
+ * operator output and r0 in `in_dtype` (0 = fp32, 1 = fp64; fp64 io requires fp64 state).  Every elementwise operation is
+ * rounded separately, in the reference's order; clip(v, min=eps) passes NaN like torch.clamp.
+ * Row regimes, chosen from `dim` alone: dim <= 1024 runs one wave per row and fuses each entry into one pass (reductions are
+ * wave butterflies); longer rows are split into 1024-element segments, one wave each, whose partial sums go to `partial`
+ * and are reduced by the next pass in a fixed order (no atomics).  The result of a row therefore never depends on the
+ * number of rows or on the launch, and repeats bit for bit.  az_krylov_segments(dim) is the number of segments of a row
+ * (1 in the one-wave regime); `partial` holds rows * slots * segments elements of the state dtype (CG: 2 slots, GMRES:
+ * iterations + 2; unused, may be NULL, when segments == 1).  All entries are asynchronous and graph-capturable. */
+#define AZ_KRYLOV_GMRES_MAX 32 /* largest GMRES `iterations` the kernels take */
+int64_t az_krylov_segments(int64_t dim);
+
+typedef struct AzCgArgs {
+  const void* r0;   /* init: b, or b - A(x0) (in_dtype)                                                    */
+  const void* x0;   /* init: the initial guess (io_dtype), or NULL for zeros                               */
+  const void* Ap;   /* step: A(p.to(b)) (in_dtype)                                                         */
+  void* x;          /* state (rows, dim)                                                                   */
+  void* r;          /* state (rows, dim)                                                                   */
+  void* p;          /* state (rows, dim)                                                                   */
+  const void* rr;   /* step: (rows) r.r before the step                                                    */
+  void* rr_out;     /* (rows) r.r after init / the step; never aliases rr                                  */
+  void* p_io;       /* (rows, dim) io_dtype: p.to(b), the next operator input                              */
+  void* out;        /* step: non-NULL on the last iteration, which writes x.to(b) here and nothing else    */
+  void* partial;    /* long rows: 2 slots                                                                  */
+  int64_t rows, dim;
+  int32_t state_dtype, io_dtype, in_dtype, reserved;
+} AzCgArgs; /* 120 bytes */
+/* solve.py:51-61: x = x0 or 0, r = r0, rr = r.r, p = r; writes x, r, p, rr_out, p_io. */
+int az_cg_init(const AzCgArgs* args, az_stream_t stream);
+/* solve.py:63-73, one iteration after the caller's Ap = A(p_io): pAp -> alpha -> x, r -> rr_ -> beta -> p, p_io. */
+int az_cg_step(const AzCgArgs* args, az_stream_t stream);
+
+typedef struct AzGmresArgs {
+  const void* r0;   /* init: b, or b - A(x0) (in_dtype)                                                    */
+  const void* x0;   /* finish: the initial guess (io_dtype), or NULL                                       */
+  const void* w;    /* arnoldi: A(V_j.to(b)) (in_dtype)                                                    */
+  void* V;          /* state (iterations, rows, dim): the basis                                            */
+  void* work;       /* state (rows, dim): w between the passes of long rows (unused for short rows)        */
+  void* H;          /* state (rows, iterations + 1, iterations), zero-initialised by the caller            */
+  void* cs;         /* state (rows, iterations)                                                            */
+  void* ss;         /* state (rows, iterations)                                                            */
+  void* B;          /* state (rows, iterations + 1); finish overwrites B[:iterations] with y               */
+  void* v_io;       /* (rows, dim) io_dtype: V_{j+1}.to(b) (init: V_0.to(b)), the next operator input      */
+  void* out;        /* finish: x.to(b) (io_dtype)                                                          */
+  void* partial;    /* long rows: iterations + 2 slots                                                     */
+  int64_t rows, dim;
+  int32_t iterations, j;
+  int32_t state_dtype, io_dtype, in_dtype, reserved;
+} AzGmresArgs; /* 136 bytes */
+/* solve.py:113-137: r = r0, V_0, B_0 = normalize(r); writes V_0, B[:, 0], v_io. */
+int az_gmres_init(const AzGmresArgs* args, az_stream_t stream);
+/* solve.py:139-166, iteration j after the caller's w = A(v_io): modified Gram-Schmidt against V_0..V_j (j + 1 dependent
+ * reductions), normalize -> V_{j+1} and v_io (not on the last iteration), then the row's previous Givens rotations, the new
+ * one and the B update on H / cs / ss / B. */
+int az_gmres_arnoldi(const AzGmresArgs* args, az_stream_t stream);
+/* solve.py:168-185: y = (H + eps I)^-1 B by back-substitution (into B), x = x0 + sum_i V_i y_i, written as x.to(b). */
+int az_gmres_finish(const AzGmresArgs* args, az_stream_t stream);
+
 /* y = s * x with s read from device memory (azula/denoise.py:317 c_in * x_t, generic backbones). */
 int az_scale_f32(float* y, const float* x, const float* s_dev, int64_t n, az_stream_t stream);
 
