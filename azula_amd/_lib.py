@@ -145,6 +145,67 @@ class AzGmresArgs(C.Structure):
     ]
 
 
+class AzCovScaleArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("e", C.c_void_p),
+        ("u", C.c_void_p),
+        ("v", C.c_void_p),
+        ("k_dev", C.c_void_p),
+        ("rho_dev", C.c_void_p),
+        ("y", C.c_void_p),
+        ("k", C.c_double),
+        ("rho", C.c_double),
+        ("rows", C.c_int64),
+        ("n", C.c_int64),
+        ("e_len", C.c_int64),
+        ("h", C.c_int32),
+        ("x_dtype", C.c_int32),
+        ("f_dtype", C.c_int32),
+        ("out_dtype", C.c_int32),
+        ("scalar_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class AzCovLowRankArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("W", C.c_void_p),
+        ("c", C.c_void_p),
+        ("a", C.c_void_p),
+        ("d", C.c_void_p),
+        ("g", C.c_void_p),
+        ("P", C.c_void_p),
+        ("partial", C.c_void_p),
+        ("y", C.c_void_p),
+        ("d0", C.c_double),
+        ("s", C.c_double),
+        ("rows", C.c_int64),
+        ("n", C.c_int64),
+        ("r", C.c_int64),
+        ("x_dtype", C.c_int32),
+        ("f_dtype", C.c_int32),
+        ("out_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class AzCovModeArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("Q", C.c_void_p),
+        ("y", C.c_void_p),
+        ("outer", C.c_int64),
+        ("n", C.c_int64),
+        ("inner", C.c_int64),
+        ("transpose", C.c_int32),
+        ("x_dtype", C.c_int32),
+        ("f_dtype", C.c_int32),
+        ("out_dtype", C.c_int32),
+    ]
+
+
 class AzLinearGroup(C.Structure):
     _fields_ = [
         ("y", c_f32p),
@@ -303,6 +364,11 @@ PROTOTYPES: dict[str, list] = {
     "az_gmres_init": [C.POINTER(AzGmresArgs), c_stream],
     "az_gmres_arnoldi": [C.POINTER(AzGmresArgs), c_stream],
     "az_gmres_finish": [C.POINTER(AzGmresArgs), c_stream],
+    "az_cov_segments": [i64],
+    "az_cov_scale": [C.POINTER(AzCovScaleArgs), c_stream],
+    "az_cov_project": [C.POINTER(AzCovLowRankArgs), c_stream],
+    "az_cov_expand": [C.POINTER(AzCovLowRankArgs), c_stream],
+    "az_cov_mode": [C.POINTER(AzCovModeArgs), c_stream],
     "az_scale_f32": [vp, vp, vp, i64, c_stream],
     "az_silu_f32": [vp, vp, i64, c_stream],
     "az_axpby_f32": [vp, vp, vp, vp, vp, i64, i64, i32, c_stream],
@@ -376,7 +442,7 @@ PROTOTYPES: dict[str, list] = {
     "az_calib_mfma_random_bf16": [vp, i32, i32, f32, f32, c_stream],
 }
 
-RESTYPES = {"az_f16x2_weight_scale": C.c_float, "az_krylov_segments": C.c_int64}  # (everything else returns an int status)
+RESTYPES = {"az_f16x2_weight_scale": C.c_float, "az_krylov_segments": C.c_int64, "az_cov_segments": C.c_int64}  # (everything else returns an int status)
 
 _lock = threading.Lock()
 _lib = None

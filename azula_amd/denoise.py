@@ -12,6 +12,7 @@ CPU-runnable README configuration) take the reference's own op sequence in torch
 from __future__ import annotations
 
 import abc
+import ctypes as C
 import math
 
 import torch
@@ -22,7 +23,9 @@ from . import _lib
 from .nn.utils import get_module_dtype
 from .noise import Schedule
 
-__all__ = ["Posterior", "DiracPosterior", "GaussianPosterior", "Denoiser", "SimpleDenoiser", "KarrasDenoiser"]
+__all__ = [
+    "Posterior", "DiracPosterior", "GaussianPosterior", "Denoiser", "GaussianDenoiser", "SimpleDenoiser", "KarrasDenoiser",
+]
 
 
 class Posterior(abc.ABC):
@@ -63,6 +66,11 @@ class Denoiser(nn.Module):
         r"""Returns a :class:`azula_amd.sample.FusedDenoiser` if this denoiser can run inside the
         captured per-step graph, else ``None`` (generic step-by-step path)."""
         return None
+
+    def _az_fused_key(self) -> tuple:
+        r"""Identity of the state a compiled program reads that is neither a parameter nor a buffer (part of the sampler's
+        plan key)."""
+        return ()
 
 
 def _expand_like(a: Tensor, ndim: int) -> Tensor:
@@ -238,3 +246,197 @@ class SimpleDenoiser(Denoiser):
                 "c_time": torch.log(sigma_t / alpha_t)}
 
     _az_fused = KarrasDenoiser._az_fused
+
+
+# --------------------------------------------------------------------------------------------------------- Gaussian
+def _cov_key(obj) -> tuple:
+    r"""(type, address / version / shape / dtype of every tensor, value of every number) of a covariance, recursively."""
+    if torch.is_tensor(obj):
+        return ("T", obj.data_ptr(), obj._version, tuple(obj.shape), str(obj.dtype), str(obj.device))
+    if isinstance(obj, (int, float)):
+        return ("v", obj)
+    if isinstance(obj, (list, tuple)):
+        return ("seq", *(_cov_key(v) for v in obj))
+    return (type(obj).__name__, *((k, _cov_key(v)) for k, v in sorted(getattr(obj, "__dict__", {}).items())))
+
+
+def _device_scalar(v, device) -> tuple[float, Tensor | None]:
+    r"""A 0-d schedule value as the covariance kernels read it: a host float when it lives on the host (no sync), else a
+    one-element fp32 / fp64 device tensor."""
+    if not torch.is_tensor(v):
+        return float(v), None
+    if v.device.type == "cpu":
+        return float(v), None
+    v = v.reshape(1).to(device)
+    return 1.0, (v if v.dtype in (torch.float32, torch.float64) else v.to(torch.float64)).contiguous()
+
+
+class GaussianDenoiser(Denoiser):
+    r"""Analytical denoiser of a Gaussian prior :math:`X \sim \mathcal{N}(\mu_x, \Sigma_x)` (reference
+    ``azula/denoise.py:117-172``): with :math:`X_t \sim \mathcal{N}(\alpha_t X, \sigma_t^2 I)`,
+
+    .. math:: \mathbb{E}[X \mid x_t] = \mu_x + \Sigma_x (\Sigma_x + \rho_t I)^{-1} (z - \mu_x), \quad
+        z = x_t / \alpha_t, \quad \rho_t = (\sigma_t / \alpha_t)^2
+
+    Arguments:
+        mean: The mean vector :math:`\mu_x`, with shape :math:`(N_1, ..., N_d)`.
+        cov: The covariance matrix :math:`\Sigma_x` (an :class:`azula_amd.linalg.covariance.Covariance`).
+        schedule: The noise schedule.
+
+    Host tensors take the reference's op sequence.  Device tensors take the form above: the covariance applies run on the
+    kernels of ``csrc/covariance.hip`` (see :mod:`azula_amd.linalg.covariance`).  For the spectral covariances (Isotropic,
+    Diagonal, Full, Kronecker with a Diagonal ``L``) with fp32 latents and factors, a sampler runs the whole denoiser inside
+    its captured step graph: ``z - mu``, the projection, ``e / (e + rho)``, the expansion and ``+ mu``, with ``rho`` read
+    from the step's coefficient row.  ``mean`` and ``cov`` are plain attributes: a re-assignment or an in-place edit of
+    their tensors rebuilds that plan.
+    """
+
+    def __init__(self, mean: Tensor, cov, schedule: Schedule) -> None:
+        super().__init__()
+        self.mean = mean
+        self.cov = cov
+        self.schedule = schedule
+
+    def _apply(self, fn, recurse: bool = True):
+        super()._apply(fn, recurse=recurse)
+        self.mean = fn(self.mean)
+        self.cov = fn(self.cov)
+        return self
+
+    @_lib.on_device
+    def forward(self, x_t: Tensor, t: Tensor, **kwargs) -> DiracPosterior:
+        from .linalg.covariance import IsotropicCovariance
+
+        alpha_t, sigma_t = self.schedule(t)
+        if not x_t.is_cuda:  # host tensors: the reference's op sequence
+            mean_t = alpha_t * self.mean
+            cov_t = IsotropicCovariance(alpha_t**2) * self.cov + IsotropicCovariance(sigma_t**2)
+            return DiracPosterior(mean=(x_t + sigma_t**2 * cov_t.inv(mean_t - x_t)) / alpha_t)
+
+        # The reference's (x_t + sigma^2 cov_t^-1 (alpha mu - x_t)) / alpha is the same quantity, but it cancels
+        # catastrophically in fp32 as t -> 1: z = x_t / alpha grows like 1 / alpha while the mean stays O(1).
+        rho = (sigma_t / alpha_t) ** 2
+        mu = self.mean
+        d = self._centered(x_t, alpha_t)
+        y = self.cov @ ((self.cov + IsotropicCovariance(rho)).inv @ d)
+        if d.is_cuda and self._kernel_mean(x_t) and y.dtype in (torch.float32, torch.float64):
+            from .linalg.covariance import _scale
+
+            y = y.contiguous()
+            return DiracPosterior(mean=_scale(y, mu.numel(), v=mu))
+        return DiracPosterior(mean=y + mu)
+
+    def _kernel_mean(self, x_t: Tensor) -> bool:
+        mu = self.mean
+        return (torch.is_tensor(mu) and mu.device == x_t.device and mu.dtype in (torch.float32, torch.float64)
+                and x_t.dtype in (torch.float32, torch.float64) and mu.is_contiguous() and mu.numel() > 0
+                and x_t.numel() % mu.numel() == 0 and tuple(x_t.shape[x_t.ndim - mu.ndim:]) == tuple(mu.shape)
+                and not (torch.is_grad_enabled() and (x_t.requires_grad or mu.requires_grad)))
+
+    def _centered(self, x_t: Tensor, alpha_t: Tensor) -> Tensor:
+        r"""``x_t / alpha_t - mu`` (one ``az_cov_scale`` pass where the kernels take the operands)."""
+        if alpha_t.numel() == 1 and self._kernel_mean(x_t):
+            from .linalg.covariance import _scale
+
+            k, k_dev = _device_scalar(1 / alpha_t, x_t.device)
+            return _scale(x_t.contiguous(), self.mean.numel(), u=self.mean, k=k, k_dev=k_dev)
+        return x_t / alpha_t - self.mean
+
+    # -- fused sampling ---------------------------------------------------------------------------------------------
+    def host_coefficients(self, alpha_t: Tensor, sigma_t: Tensor) -> dict:
+        r"""The program's input is ``z = x_t / alpha_t`` (``c_in``), its output the mean itself (``c_skip = 0``,
+        ``c_out = 1``); ``rho = (sigma_t / alpha_t)^2`` travels in the ``c_time`` word."""
+        c_in = 1 / alpha_t
+        return {"c_in": c_in, "c_out": torch.ones_like(c_in), "c_skip": torch.zeros_like(c_in),
+                "c_time": (sigma_t / alpha_t) ** 2}
+
+    def _az_fused_key(self) -> tuple:
+        return (_cov_key(self.mean), _cov_key(self.cov))
+
+    def _az_fused(self, x: Tensor, kwargs: dict, cur_coef: Tensor):
+        from .linalg import covariance as cv
+
+        mu, cov = self.mean, self.cov
+        f32 = lambda *ts: all(torch.is_tensor(t) and t.dtype == torch.float32 and t.device == x.device and t.is_contiguous()  # noqa: E731
+                              for t in ts)
+        if x.dtype != torch.float32 or x.ndim < 2 or not f32(mu) or mu.numel() != x[0].numel():
+            return None
+        n = mu.numel()
+        B = x.numel() // n
+        rho_ptr = cur_coef.data_ptr() + 4 * _lib.COEF_FIELDS.index("c_time")
+        tape_ops: list = []
+        keep: list = []
+        x_in, out = torch.empty_like(x), torch.empty_like(x)
+
+        def scale(src: Tensor, dst: Tensor, cols: int, e: Tensor | None = None, u: Tensor | None = None,
+                  v: Tensor | None = None) -> None:
+            a = _lib.AzCovScaleArgs(x=src.data_ptr(), e=None if e is None else e.data_ptr(), u=None if u is None else u.data_ptr(),
+                                    v=None if v is None else v.data_ptr(), rho_dev=rho_ptr if e is not None else None,
+                                    y=dst.data_ptr(), k=1.0, rows=src.numel() // cols, n=cols,
+                                    e_len=0 if e is None else e.numel(), h=cv.H_POSTERIOR if e is not None else cv.H_IDENTITY)
+            tape_ops.append(("az_cov_scale", a))
+
+        if isinstance(cov, cv.IsotropicCovariance):
+            lam = cov.lmbda
+            if torch.is_tensor(lam):
+                if not (lam.dtype == torch.float32 and lam.device in (x.device, torch.device("cpu"))):
+                    return None
+                e = lam.detach().to(device=x.device).reshape(1).clone()
+            else:
+                e = torch.tensor([float(lam)], dtype=torch.float32, device=x.device)
+            keep.append(e)
+            scale(x_in, out, n, e=e, u=mu, v=mu)
+        elif isinstance(cov, cv.DiagonalCovariance):
+            if not (f32(cov.D) and cov.D.numel() == n):
+                return None
+            scale(x_in, out, n, e=cov.D, u=mu, v=mu)
+        elif isinstance(cov, cv.FullCovariance):
+            Q, L = cov.Q, cov.L
+            r = Q.shape[-1]
+            if not (f32(Q, L) and Q.numel() == n * r and L.numel() == r):
+                return None
+            d, y = torch.empty_like(x), torch.empty_like(x)
+            P, P2 = (torch.empty(B, r, dtype=torch.float32, device=x.device) for _ in range(2))
+            nseg = _lib.lib().az_cov_segments(n)
+            partial = torch.empty(nseg, B, r, dtype=torch.float32, device=x.device) if nseg > 1 else None
+            keep += [d, y, P, P2, partial]
+            scale(x_in, d, n, u=mu)
+            tape_ops.append(("az_cov_project", _lib.AzCovLowRankArgs(
+                x=d.data_ptr(), W=Q.data_ptr(), P=P.data_ptr(), partial=None if partial is None else partial.data_ptr(),
+                rows=B, n=n, r=r)))
+            scale(P, P2, r, e=L)
+            tape_ops.append(("az_cov_expand", _lib.AzCovLowRankArgs(W=Q.data_ptr(), P=P2.data_ptr(), y=y.data_ptr(), s=1.0,
+                                                                    rows=B, n=n, r=r)))
+            scale(y, out, n, v=mu)
+        elif isinstance(cov, cv.KroneckerCovariance) and isinstance(cov.L, cv.DiagonalCovariance):
+            Qs, D = cov.Qs, cov.L.D
+            shape = [Q.shape[0] for Q in Qs]
+            if not (f32(D, *Qs) and math.prod(shape) == n and D.numel() == n and all(Q.shape == (m, m) for Q, m in zip(Qs, shape))):
+                return None
+            bufs = [torch.empty_like(x) for _ in range(2)]
+            keep += bufs
+            scale(x_in, bufs[0], n, u=mu)
+            cur = 0
+            for transpose, core in ((1, True), (0, False)):
+                for i, Q in enumerate(Qs):
+                    tape_ops.append(("az_cov_mode", _lib.AzCovModeArgs(
+                        x=bufs[cur].data_ptr(), Q=Q.data_ptr(), y=bufs[1 - cur].data_ptr(), outer=B * math.prod(shape[:i]),
+                        n=shape[i], inner=math.prod(shape[i + 1:]), transpose=transpose)))
+                    cur = 1 - cur
+                if core:
+                    scale(bufs[cur], bufs[1 - cur], n, e=D)
+                    cur = 1 - cur
+            scale(bufs[cur], out, n, v=mu)
+        else:
+            return None  # the DPLR family (and anything else): the generic loop
+
+        from .engine import Tape
+        from .sample import BackboneProgram, FusedDenoiser
+
+        tape = Tape()
+        for name, a in tape_ops:
+            tape.add(name, C.byref(a), keep=[a])
+        tape.keep += [mu, cov, *keep]
+        Cc = x.shape[1] if x.ndim > 2 else 1
+        program = BackboneProgram(tape=tape, x_in=x_in, x_in_cs=0, out=out, f_channels=Cc, f_nhwc=False, wide=False)
+        return FusedDenoiser(coefficients=self.host_coefficients, programs=[program])

@@ -1,3 +1,5 @@
-r"""Linear algebra (reference ``azula/linalg``): the Krylov solvers of ``solve``, on HIP kernels for device tensors."""
+r"""Linear algebra (reference ``azula/linalg``): the Krylov solvers of ``solve`` and the structured covariances of
+``covariance``, on HIP kernels for device tensors."""
 
+from . import covariance  # noqa: F401
 from .solve import cg, gmres  # noqa: F401

@@ -58,6 +58,7 @@ class BackboneProgram:
     f_channels: int
     f_nhwc: bool
     prepare: Callable[[dict], None] | None = None  # runs before each sampling call (e.g. upload labels)
+    wide: bool = True  # False: the program is fp32 only and an fp64 clock runs the generic loop
 
 
 @dataclass
@@ -395,14 +396,19 @@ class Sampler(abc.ABC):
         wide = not (x.dtype == torch.float32 and self.dtype in (None, torch.float32))
         key = (
             tuple(x.shape), str(dev), _kwargs_signature(kwargs), self._fused_structure(), id(self.denoiser),
-            module_fingerprint(self.denoiser), str(x.dtype), wide,
+            module_fingerprint(self.denoiser), str(x.dtype), wide, getattr(self.denoiser, "_az_fused_key", tuple)(),
         )
         ent = self._fused_cache.get(key)
+        if ent is _NOT_WIDE:
+            return None  # (this configuration's program is fp32 only: decided once per key, not rebuilt per call)
         if ent is None:
             self._fused_cache = {}  # drop the stale plan first: one live plan per sampler keeps HBM use bounded
             cur = torch.zeros(COEF_WORDS, dtype=torch.float32, device=dev)
             fused = self.denoiser._az_fused(torch.empty(x.shape, dtype=torch.float32, device=dev) if wide else x, kwargs, cur)
             if fused is None:
+                return None
+            if wide and not all(p.wide for p in fused.programs):
+                self._fused_cache = {key: _NOT_WIDE}
                 return None
             if wide:
                 p0 = fused.programs[0]
@@ -414,6 +420,9 @@ class Sampler(abc.ABC):
                 ent = _FusedLoop(self, fused, x, cur)
             self._fused_cache = {key: ent}
         return ent.run(x, kwargs)
+
+
+_NOT_WIDE = object()  # plan-cache entry: the denoiser's program does not run under an fp64 clock
 
 
 def module_fingerprint(module: torch.nn.Module) -> tuple:

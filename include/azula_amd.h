@@ -208,6 +208,64 @@ int az_gmres_arnoldi(const AzGmresArgs* args, az_stream_t stream);
 /* solve.py:168-185: y = (H + eps I)^-1 B by back-substitution (into B), x = x0 + sum_i V_i y_i, written as x.to(b). */
 int az_gmres_finish(const AzGmresArgs* args, az_stream_t stream);
 
+/* ---- Covariance applies -------------------------------------------------------------------------------------------
+ * The per-step products of azula/linalg/covariance.py (Isotropic, Diagonal, Full, DPLR, DMLR, Kronecker); the setup (from_data,
+ * capacitances, the r x r eigh of inv / color, logdet) stays with the caller.  Every operand is contiguous; dtype codes are
+ * 0 = fp32, 1 = fp64, and `out_dtype` must be torch's promotion of `x_dtype` and `f_dtype` (the factors' dtype); every
+ * operand is converted to it on load.  Each output is one dot product (or one elementwise expression) evaluated in a fixed
+ * order that depends on n and r alone, so a row's result does not depend on the number of rows and repeats bit for bit.
+ * All entries are asynchronous and graph-capturable. */
+#define AZ_COV_H_IDENTITY 0  /* h(e) = e                                                                 */
+#define AZ_COV_H_SQRT 1      /* h(e) = sqrt(e)                                                           */
+#define AZ_COV_H_INV 2       /* h(e) = 1 / e                                                             */
+#define AZ_COV_H_POSTERIOR 3 /* h(e) = e / (e + rho): the spectral factor of C (C + rho I)^-1              */
+
+typedef struct AzCovScaleArgs {
+  const void* x;       /* (rows, n) x_dtype                                                                 */
+  const void* e;       /* (e_len) f_dtype, e_len = n or 1 (broadcast), or NULL for h = 1                    */
+  const void* u;       /* (n) f_dtype subtracted before the scale, or NULL                                 */
+  const void* v;       /* (n) f_dtype added after the scale, or NULL                                       */
+  const void* k_dev;   /* device scalar (scalar_dtype) multiplying x, or NULL: the host value k             */
+  const void* rho_dev; /* device scalar (scalar_dtype), or NULL: the host value rho                        */
+  void* y;             /* (rows, n) out_dtype; may alias x when the dtypes agree                            */
+  double k, rho;
+  int64_t rows, n, e_len;
+  int32_t h, x_dtype, f_dtype, out_dtype, scalar_dtype, reserved;
+} AzCovScaleArgs; /* 120 bytes */
+/* y[b, f] = (k x[b, f] - u_f) h(e_f) + v_f. */
+int az_cov_scale(const AzCovScaleArgs* args, az_stream_t stream);
+
+typedef struct AzCovLowRankArgs {
+  const void* x;     /* project: (rows, n) x_dtype; expand: the x of the diagonal term, or NULL for none    */
+  const void* W;     /* (n, r) f_dtype, row-major                                                         */
+  const void* c;     /* project: (n) f_dtype, or NULL for 1                                               */
+  const void* a;     /* expand: (n) f_dtype, or NULL for 1                                                */
+  const void* d;     /* expand: (n) f_dtype, or NULL for the constant d0                                  */
+  const void* g;     /* expand: (r) f_dtype, or NULL for 1                                                */
+  void* P;           /* (rows, r) out_dtype: the projection (project writes it, expand reads it)          */
+  void* partial;     /* project: (az_cov_segments(n), rows, r) out_dtype; may be NULL when that is one    */
+  void* y;           /* expand: (rows, n) out_dtype                                                       */
+  double d0, s;      /* expand: d_f where d is NULL; the sign of the low-rank term (+1 / -1)              */
+  int64_t rows, n, r;
+  int32_t x_dtype, f_dtype, out_dtype, reserved;
+} AzCovLowRankArgs; /* 128 bytes */
+int64_t az_cov_segments(int64_t n);
+/* P[b, j] = sum_f W[f, j] c_f x[b, f]; features in 512-element segments whose partial sums are reduced in a fixed order. */
+int az_cov_project(const AzCovLowRankArgs* args, az_stream_t stream);
+/* y[b, f] = a_f (d_f x[b, f] + s sum_j W[f, j] g_j P[b, j]).  DPLR / DMLR @: W = V, d = D, s = +1 / -1; their color:
+ * W = U, a = sqrt(D), d0 = 1, g = sqrt(1 +- L) - 1; Full @ / color: W = Q, x = NULL. */
+int az_cov_expand(const AzCovLowRankArgs* args, az_stream_t stream);
+
+typedef struct AzCovModeArgs {
+  const void* x;   /* (outer, n, inner) x_dtype                                                           */
+  const void* Q;   /* (n, n) f_dtype, row-major                                                           */
+  void* y;         /* (outer, n, inner) out_dtype; never aliases x                                        */
+  int64_t outer, n, inner;
+  int32_t transpose, x_dtype, f_dtype, out_dtype;
+} AzCovModeArgs; /* 64 bytes */
+/* One Kronecker axis: y[o, i, k] = sum_m M[i, m] x[o, m, k], M = Q (transpose = 0) or Q^T (transpose = 1). */
+int az_cov_mode(const AzCovModeArgs* args, az_stream_t stream);
+
 /* y = s * x with s read from device memory (azula/denoise.py:317 c_in * x_t, generic backbones). */
 int az_scale_f32(float* y, const float* x, const float* s_dev, int64_t n, az_stream_t stream);
 
