@@ -95,8 +95,9 @@ __global__ __launch_bounds__(256) void attention_kernel(AzAttnArgs a) {
   };
   fetch(0);  // issued before the Q rows are read: both global round trips of the prologue overlap
 
-  // ---- Q fragment: lane holds q[qi][8*jj + 4*h2 + s], pre-multiplied by scale (* rms factor)
+  // ---- Q fragment: lane holds q[qi][8*jj + 4*h2 + s], pre-multiplied by the power of two of scale log2 e (* rms factor)
   float qf[KJ][4];
+  float score_mul = 1.f;  // what is left of scale * log2 e for the scores (wave-uniform, > 0)
   {
     float ss = 0.f;
 #pragma unroll
@@ -114,7 +115,16 @@ __global__ __launch_bounds__(256) void attention_kernel(AzAttnArgs a) {
     // NOT overlap with fp32 MFMAs on a SIMD (measured, DESIGN.md section 4: the two times add), so every VALU
     // instruction removed from this loop is matrix-pipe time gained.  Parity cost measured on the golden ViT / ADM /
     // JiT vectors: below 1e-6 of the output scale (the tests' bounds are unchanged).
+    // Only the power of two of scale * log2 e goes into q (exact: q keeps its bits, and the products of the contraction are the
+    // unscaled ones -- exact wherever q k^T is); its mantissa, score_mul in [1, 2), multiplies the finished score inside the
+    // softmax's one fused multiply-add.  Scaling q by the whole factor rounded every q element and made each of the D / 2
+    // accumulation steps of a score of magnitude S round at 2^-24 S (tests/test_gpu_attention.py: ramp_big, masked_spike).
     float f = a.scale * 1.4426950408889634f;
+    if (f > 0.f && f < INFINITY) {
+      int e;
+      score_mul = 2.f * frexpf(f, &e);
+      f = ldexpf(1.f, e - 1);
+    }
     if (a.qk_rmsnorm) {
       ss += __shfl_xor(ss, 32, 64);
       f *= rsqrtf(ss / az_norm_dim<D>(a) + a.eps);
@@ -246,7 +256,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AzAttnArgs a) {
       float mt = sacc[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) mt = fmaxf(mt, sacc[r]);
-      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+      mt = fmaxf(mt, __shfl_xor(mt, 32, 64)) * score_mul;  // (m_run is in log2 units; -inf stays -inf)
       const float m_new = fmaxf(m_run, mt);
       // -inf only while every key seen so far is masked for this query: subtract 0 then (all terms are 2^(-inf) = 0)
       const float m_sub = m_new == -INFINITY ? 0.f : m_new;
@@ -254,7 +264,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AzAttnArgs a) {
       float ls = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pv = __builtin_amdgcn_exp2f(sacc[r] - m_sub);  // masked keys: 2^(-inf) = 0
+        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[r], score_mul, -m_sub));  // masked keys: 2^(-inf) = 0
         sacc[r] = pv;
         ls += pv;
       }

@@ -625,7 +625,9 @@ typedef struct AzAttnArgs {
   /* optional boolean attention mask (azula/nn/attention.py:72-104 -> scaled_dot_product_attention(attn_mask=mask)):
    * one byte per (query, key) pair, non-zero = the query may attend to the key; laid out (tokens, tokens) with a batch
    * and a head stride in bytes (0 = shared by all samples / heads).  A query whose keys are all masked yields NaN, as
-   * in the reference.  NULL = no mask.                                                                            */
+   * in the reference (its whole output row, and only that row); key tiles that are entirely masked for a query, before
+   * or after its first live key, contribute nothing.  Both behaviours and strides other than 0 are pinned by
+   * tests/test_gpu_attention.py.  NULL = no mask.                                                                  */
   const uint8_t* mask;
   int64_t mask_bstride, mask_hstride;
   /* az_attention_bf16_f32 / az_attention_f16_f32 only (0 elsewhere): 1 = q, k, v and out hold the entry's 2-byte type (the
