@@ -832,17 +832,22 @@ class Builder:
             y = self.new_act(B, x.H // 2 if pool == 1 else x.H, x.W // 2, x.C, f32=not x.half)
         else:
             y = self.new_act(B, x.H, x.W, x.C, f32=not x.half)
+        assert y.cs == x.cs, "the apply pass writes the source's channel stride: the source must be on this plan's stride"
         return self._affine_act(y, x, x1p, c0s, S.data_ptr(), T.data_ptr(), B, x.H, x.W, x.cs, act, pool, bounded=True)
 
     def row_norm(self, x: Act, kind: int, *, weight=None, scale=None, shift=None, scale_off=0, shift_off=0, bstride=0,
                  eps=1e-5):
         y = self.new_act(x.B, x.H, x.W, x.C, f32=not x.half)
+        assert y.cs == x.cs, "the row norm writes the source's channel stride: the source must be on this plan's stride"
         rows = x.B * x.H * x.W
         args = (y.ptr, x.ptr, weight.data_ptr() if weight is not None else None,
                 scale.data_ptr() + 4 * scale_off if scale is not None else None,
                 shift.data_ptr() + 4 * shift_off if shift is not None else None,
                 bstride, rows, x.H * x.W, x.C, x.cs, kind, eps)
         if x.half:  # rows in the module's 2-byte type (fp32 statistics / modulation)
+            if x.C % 8 or x.C != x.cs or x.C > 4096 or bstride % 4:  # (az_rownorm_mod_h16 would answer AZ_E_UNSUPPORTED at run time)
+                raise ValueError(f"row_norm on 2-byte rows of width {x.C} (stride {x.cs}, modulation stride {bstride}): "
+                                 "az_rownorm_mod_h16 takes widths that are multiples of 8, unpadded, at most 4096")
             self.tape.add("az_rownorm_mod_h16", *args, 2 if x.buf.dtype == torch.float16 else 1, keep=[weight, scale, shift])
         else:
             self.tape.add("az_rownorm_mod_f32", *args, keep=[weight, scale, shift])

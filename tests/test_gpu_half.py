@@ -287,7 +287,10 @@ def test_typed_groupnorm_passes(half, pool, act, two):
         assert names == (["az_groupnorm_stats_h16", "az_groupnorm_finalize_f32", "az_affine_act_h16"] if typed else
                          ["az_groupnorm_stats_f32", "az_groupnorm_finalize_f32", "az_affine_act_f32"])
         outs.append(y.buf.float().clone())
-        parts.append(bld.tape.keep)
+        ptr = bld.tape.ops[0][1][0]  # (the statistics launch's first argument: its partials)
+        parts.append(next(t for t in bld.tape.keep if isinstance(t, torch.Tensor) and t.data_ptr() == ptr).clone())
+    assert parts[0].numel() == B * groups * 4 and parts[0][0].item() == H * W * (C0 + C1) // groups  # one chunk: (n, mean, M2, 0) per group
+    assert torch.equal(parts[0], parts[1]), (parts[0] - parts[1]).abs().max().item()
     assert torch.equal(outs[1], _rt(outs[0], half)), (outs[1] - _rt(outs[0], half)).abs().max().item()
 
 

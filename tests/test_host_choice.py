@@ -214,3 +214,16 @@ def test_a_view_carries_bounded_and_only_the_moments_it_is_given(bld):
     v = y.view(1, 2 * y.H, gn_quads=(q[0], 2 * q[1], q[2]))  # (ADM's planes -> volume re-chunking)
     assert bld.fact(v, v.gn_quads) is not None
     assert not y.view(bounded=False).bounded
+
+
+@pytest.mark.parametrize("half", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("C", [12, 100, 4104])
+def test_row_norm_names_a_width_the_2_byte_kernel_refuses(half, C):
+    """az_rownorm_mod_h16 takes C % 8 == 0, C == cs, C <= 4096 and answers AZ_E_UNSUPPORTED otherwise -- at run time, from inside
+    a tape.  Builder.row_norm says so while the plan is built, with the width in the message; a width it takes goes on the tape."""
+    b = Builder(torch.device("cpu"), half=half, half_act=True)
+    with pytest.raises(ValueError, match=f"width {C} "):
+        b.row_norm(b.new_act(2, 3, 1, C), 1)
+    assert not b.tape.ops
+    b.row_norm(b.new_act(2, 3, 1, 4096), 0)
+    assert ops(b) == ["az_rownorm_mod_h16"]
