@@ -156,6 +156,39 @@ def postcondition(x_t: Tensor, out: Tensor, c_skip: Tensor, c_out: Tensor) -> Te
     return y
 
 
+def _vjp_preconditioned(den: "Denoiser", x_t: Tensor, c_in: Tensor, c_out: Tensor | None, c_skip: Tensor | None, c_time: Tensor,
+                        kwargs: dict):
+    r"""mean = c_skip x_t + c_out F(c_in x_t, c_time) and its pullback v -> c_skip v + c_in c_out J_F^T v (``c_out`` /
+    ``c_skip`` None: mean = F(c_in x_t, c_time)).  ``F``'s pullback is the backbone's ``vjp`` (HIP tapes); the elementwise parts
+    are the preconditioning kernels of the forward.  No torch fallback: a backbone without ``vjp`` is an error."""
+    backbone = den.backbone
+    if not x_t.is_cuda:
+        raise NotImplementedError(f"{type(den).__name__}: the input-gradient path runs on device tensors only")
+    vjp = getattr(backbone, "vjp", None)
+    if vjp is None:
+        raise NotImplementedError(
+            f"{type(den).__name__}: the backbone {type(backbone).__name__} has no input-gradient (vjp) path on the HIP kernels "
+            "(available: azula_amd.nn.UNet, UNetBlock and TimeModulated around them); there is no torch fallback on device tensors")
+    if get_module_dtype(backbone) not in (None, torch.float32):
+        raise NotImplementedError(f"{type(den).__name__}: the input-gradient path takes fp32 backbones only")
+    require_f32_cuda(x_t, type(den).__name__)
+    x_t = x_t.detach().contiguous()
+    x_in = precondition(x_t, c_in)
+    output, pull = vjp(x_in, c_time.to(device=x_t.device, dtype=torch.float32), **kwargs)
+    output = output.contiguous()
+    mean = output if c_out is None else postcondition(x_t, output, c_skip, c_out)
+    scale = c_in if c_out is None else c_in * c_out
+
+    def pullback(v: Tensor) -> Tensor:
+        v = v.detach().to(torch.float32).contiguous()
+        jv = pull(v).contiguous()
+        if c_skip is None:
+            return precondition(jv, scale)
+        return postcondition(v, jv, c_skip, scale)
+
+    return mean, pullback
+
+
 class KarrasDenoiser(Denoiser):
     r"""EDM-style preconditioned denoiser (reference ``azula/denoise.py:263-324``).
 
@@ -192,6 +225,17 @@ class KarrasDenoiser(Denoiser):
         output = self.backbone(x_in.to(dtype), c_time.to(device=x_t.device, dtype=dtype), **kwargs)
         output = output.to(x_t).contiguous()
         return DiracPosterior(mean=postcondition(x_t, output, c_skip.to(x_t.device), c_out.to(x_t.device)))
+
+    # -- input gradient (azula_amd internal: the guidance classes that need d mean / d x_t) ------------------
+    @torch.no_grad()
+    @_lib.on_device
+    def _az_vjp(self, x_t: Tensor, t: Tensor, **kwargs):
+        r"""``(mean, pullback)`` with ``pullback(v) = (d mean / d x_t)^T v = c_skip v + c_in c_out J_F^T v``: the backbone's
+        HIP pullback between the preconditioning kernels.  A backbone without ``vjp`` raises ``NotImplementedError``."""
+        alpha_t, sigma_t = self.schedule(t)
+        alpha_t, sigma_t = _expand_like(alpha_t, x_t.ndim), _expand_like(sigma_t, x_t.ndim)
+        c_in, c_out, c_skip, c_time = karras_coefficients(alpha_t, sigma_t)
+        return _vjp_preconditioned(self, x_t, c_in.to(x_t.device), c_out.to(x_t.device), c_skip.to(x_t.device), c_time.reshape_as(t), kwargs)
 
     # -- fused sampling -------------------------------------------------------------------------
     def host_coefficients(self, alpha_t: Tensor, sigma_t: Tensor) -> dict:
@@ -239,6 +283,16 @@ class SimpleDenoiser(Denoiser):
         x_in = precondition(x_t.contiguous(), c_in.to(x_t.device))
         output = self.backbone(x_in.to(dtype), c_time.to(device=x_t.device, dtype=dtype), **kwargs)
         return DiracPosterior(mean=output.to(x_t))
+
+    @torch.no_grad()
+    @_lib.on_device
+    def _az_vjp(self, x_t: Tensor, t: Tensor, **kwargs):
+        r"""``(mean, pullback)`` with ``pullback(v) = c_in J_F^T v`` (the Karras form with c_skip = 0, c_out = 1)."""
+        alpha_t, sigma_t = self.schedule(t)
+        alpha_t, sigma_t = _expand_like(alpha_t, x_t.ndim), _expand_like(sigma_t, x_t.ndim)
+        c_in = torch.rsqrt(alpha_t**2 + sigma_t**2).to(x_t.device)
+        c_time = torch.log(sigma_t / alpha_t).reshape_as(t)
+        return _vjp_preconditioned(self, x_t, c_in, None, None, c_time, kwargs)
 
     def host_coefficients(self, alpha_t: Tensor, sigma_t: Tensor) -> dict:
         c_in = torch.rsqrt(alpha_t**2 + sigma_t**2)

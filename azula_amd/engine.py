@@ -747,6 +747,80 @@ class Builder:
         self.tape.add("az_upsample_nearest_f32", y.ptr, x.ptr, x.B, x.H, x.W, x.cs, sh, sw, hout, wout)
         return self.wrote(y, bounded=False)
 
+    # -- input gradient (csrc/backward.hip) --------------------------------------------------------------------
+    # Every tensor below is a cotangent: it has no natural range, so every gradient Act is ``bounded=False`` and the
+    # fixed-scale f16x2 kernels never see one (choose_conv gives them the measured-scale f16x2 form or bf16x3).
+    def conv_dgrad(self, g: Act, conv, *, cin_lo: int = 0, cin_hi: int | None = None, res: Act | None = None,
+                   dst_nchw: torch.Tensor | None = None, cache: dict | None = None) -> Act | None:
+        r"""Data gradient of a stride-1 'same' convolution ``conv`` (a module holding ``weight`` of shape (cout, cin, k...)): the
+        forward convolution kernels over the cotangent ``g`` with the weight transposed (cin <-> cout) and flipped by 180 degrees,
+        for the input channels [cin_lo, cin_hi) (one source of a concatenation); ``res`` is added in the epilogue (a tensor
+        consumed twice: its cotangents add).  A strided convolution takes the zero-stuffed cotangent (:meth:`zero_stuff`).
+        The packed weight is made once per (module, channel range) and plan (``cache``)."""
+        w = conv.weight
+        cin_hi = w.shape[1] if cin_hi is None else cin_hi
+        key = (id(conv), cin_lo, cin_hi)
+        packed = None if cache is None else cache.get(key)
+        if packed is None:
+            wt = w.detach()[:, cin_lo:cin_hi].transpose(0, 1).flip(*range(2, w.ndim)).contiguous()
+            packed = self.pack_conv(wt, None)
+            if cache is not None:
+                cache[key] = packed
+        assert g.C == w.shape[0], "the cotangent has the convolution's output channels"
+        return self.conv(g, packed, cin_hi - cin_lo, res=res, dst_nchw=dst_nchw)
+
+    def channel_scale(self, x: Act, s: torch.Tensor, s_off: int, bstride: int, out: Act | None = None) -> Act:
+        r"""y = x * s[b, c] per (sample, channel): the gate of ``out = x + c * y`` on the way back."""
+        y = self.new_act(x.B, x.H, x.W, x.C) if out is None else out
+        self.tape.add("az_channel_scale_f32", y.ptr, x.ptr, s.data_ptr() + 4 * s_off, bstride, x.B, x.H * x.W, x.C, x.cs, keep=[s])
+        return self.wrote(y, bounded=False)
+
+    def silu_bwd(self, g: Act, p: Act) -> Act:
+        r"""g <- g * silu'(p) in place (``p``: the kept PRE-activation)."""
+        assert (g.B, g.H, g.W, g.cs) == (p.B, p.H, p.W, p.cs)
+        self.tape.add("az_silu_bwd_f32", g.ptr, g.ptr, p.ptr, g.B * g.H * g.W * g.cs, keep=[p.buf])
+        return self.wrote(g, bounded=False)
+
+    def silu(self, x: Act) -> Act:
+        r"""y = silu(x) as a pass of its own (the forward-keep tape keeps the pre-activation and applies SiLU behind it)."""
+        y = self.new_act(x.B, x.H, x.W, x.C)
+        self.tape.add("az_silu_f32", y.ptr, x.ptr, x.B * x.H * x.W * x.cs)
+        return self.wrote(y, bounded=False)
+
+    def group_norm_bwd(self, x: Act, g: Act, saved: dict, *, scale=None, scale_off=0, bstride=0, res: Act | None = None) -> Act:
+        r"""Pullback of ``(1 + scale) * GN(x) + shift`` w.r.t. x, plus ``res``; ``saved`` from :meth:`group_norm`."""
+        B, HW = x.B, x.H * x.W
+        nchunks = int(min(512, max(1, (HW * x.cs * 4) // 65536)))
+        bpart = self.empty(B * nchunks * saved["groups"] * 4)
+        sp = scale.data_ptr() + 4 * scale_off if scale is not None else None
+        fp, fchunks = saved["partials"], saved["nchunks"]
+        self.tape.add("az_groupnorm_bwd_stats_f32", bpart.data_ptr(), x.ptr, g.ptr, sp, bstride, fp.data_ptr(), fchunks, B, HW, x.C, x.cs,
+                      saved["groups"], nchunks, saved["eps"], keep=[fp, scale, x.buf])
+        y = self.new_act(B, x.H, x.W, x.C)
+        self.tape.add("az_groupnorm_bwd_apply_f32", y.ptr, x.ptr, g.ptr, res.ptr if res is not None else None, sp, bstride,
+                      fp.data_ptr(), fchunks, bpart.data_ptr(), nchunks, B, HW, x.C, x.cs, saved["groups"], saved["eps"])
+        return self.wrote(y, bounded=False)
+
+    def row_norm_bwd(self, x: Act, g: Act, kind: int, *, scale=None, scale_off=0, bstride=0, res: Act | None = None, eps=1e-5) -> Act:
+        r"""Pullback of ``(1 + scale) * norm(x) + shift`` over the channel axis (kind 0: layer, unbiased variance; 1: rms), plus ``res``."""
+        y = self.new_act(x.B, x.H, x.W, x.C)
+        self.tape.add("az_rownorm_bwd_f32", y.ptr, x.ptr, g.ptr, res.ptr if res is not None else None,
+                      scale.data_ptr() + 4 * scale_off if scale is not None else None, bstride, x.B * x.H * x.W, x.H * x.W, x.C, x.cs,
+                      kind, eps, keep=[scale, x.buf])
+        return self.wrote(y, bounded=False)
+
+    def zero_stuff(self, g: Act, sh: int, sw: int, H: int, W: int) -> Act:
+        r"""The cotangent of a convolution with stride (sh, sw) on the zero-filled (H, W) grid of its input."""
+        y = self.new_act(g.B, H, W, g.C)
+        self.tape.add("az_zero_stuff_f32", y.ptr, g.ptr, g.B, g.H, g.W, g.cs, sh, sw, H, W)
+        return self.wrote(y, bounded=False)
+
+    def upsample_nearest_bwd(self, g: Act, sh: int, sw: int, h: int, w: int) -> Act:
+        r"""Pullback of ``narrow(Upsample(nearest, (sh, sw)))``: (B, hn, wn) cotangent -> (B, h, w) window sums."""
+        y = self.new_act(g.B, h, w, g.C)
+        self.tape.add("az_upsample_nearest_bwd_f32", y.ptr, g.ptr, g.B, h, w, g.cs, sh, sw, g.H, g.W)
+        return self.wrote(y, bounded=False)
+
     def finish(self) -> None:
         r"""Allocates the shared split-K workspace and patches it into the recorded convs."""
         if self._ws_need and (self.workspace is None or self.workspace.numel() < self._ws_need):
@@ -780,10 +854,11 @@ class Builder:
 
     def group_norm(
         self, x: Act, groups: int, *, weight=None, bias=None, scale=None, shift=None, scale_off=0, shift_off=0,
-        bstride=0, act=0, pool=0, eps=1e-5, x1: Act | None = None, lazy: bool = False,
+        bstride=0, act=0, pool=0, eps=1e-5, x1: Act | None = None, lazy: bool = False, saved: dict | None = None,
     ) -> Act:
         r"""y = act((GN(x)*w + b) * (1 + scale) + shift), optionally 2x2 average pooled.  With ``x1`` the
-        input is the channel concatenation [x | x1], read in place (never materialised)."""
+        input is the channel concatenation [x | x1], read in place (never materialised).  ``saved``: a dict that receives what
+        :meth:`group_norm_bwd` needs (the statistics pass always runs then: its records are the saved statistics)."""
         B, HW = x.B, x.H * x.W
         x1p, c0s = None, 0
         srcs = [x] + ([x1] if x1 is not None else [])
@@ -797,7 +872,7 @@ class Builder:
         S, T = ST[: B * x.cs], ST[B * x.cs :]
         f = AzNormFinalizeArgs()
         Cg = x.C // groups
-        fused = Cg % 4 == 0 and x.C == x.cs and all(q is not None for q in src_quads) and all((c // 4) % (Cg // 4) == 0 for c in src_channels)
+        fused = saved is None and Cg % 4 == 0 and x.C == x.cs and all(q is not None for q in src_quads) and all((c // 4) % (Cg // 4) == 0 for c in src_channels)
         if fused:  # every source was produced by a convolution that left its moments of what it holds now: no statistics pass
             nchunks = src_quads[0][1]
             f.partials = src_quads[0][0].data_ptr()
@@ -813,6 +888,9 @@ class Builder:
             else:
                 self.tape.add("az_groupnorm_stats_f32", partials.data_ptr(), x.ptr, x1p, c0s, B, HW, x.C, x.cs, groups, nchunks)
             f.partials = partials.data_ptr()
+            if saved is not None:
+                assert x1 is None and not x.half
+                saved.update(partials=partials, nchunks=nchunks, groups=groups, eps=eps)
         f.S, f.T = S.data_ptr(), T.data_ptr()
         f.weight = weight.data_ptr() if weight is not None else None
         f.bias = bias.data_ptr() if bias is not None else None

@@ -121,6 +121,102 @@ class UNetBlock(nn.Module):
             bld.free(x)
         return y
 
+    # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
+    def _vjp_supported(self) -> None:
+        if self.spatial == 3 or self.periodic:
+            raise NotImplementedError("UNetBlock.vjp: spatial = 1 / 2 with zero padding only")
+        if any(p.dtype != torch.float32 for p in self.parameters()):
+            raise NotImplementedError("UNetBlock.vjp: fp32 parameters only")
+
+    def _emit_keep(self, bld: Builder, x: Act, D: int, mod_rows: int, mod_jobs: list) -> tuple[Act, dict]:
+        r"""The forward of :meth:`_emit` with what the pullback needs kept alive: the input ``x``, the GroupNorm statistics
+        and the PRE-activation ``h`` (the first convolution runs without its SiLU epilogue; SiLU is a pass of its own in
+        front of the second).  ``x`` and ``h`` are never handed back to the pool."""
+        Cc, cs = self.channels, pad4(self.channels)
+        abc, bstride = ada_zero_triple(bld, self.ada_zero, Cc, D, mod_rows, mod_jobs)
+        saved = {"x": x, "abc": abc, "bstride": bstride}
+        if self.norm_kind == "group":
+            saved["gn"] = {}
+            n_ = bld.group_norm(x, self.groups, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride, saved=saved["gn"])
+        else:
+            n_ = bld.row_norm(x, 0 if self.norm_kind == "layer" else 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
+        c0, c3 = self.ffn[0], self.ffn[3]
+        h = bld.conv(n_, bld.pack_conv(c0.weight, c0.bias), c0.out_channels)
+        bld.free(n_)
+        a1 = bld.silu(h)
+        y = bld.conv(a1, bld.pack_conv(c3.weight, c3.bias), c3.out_channels, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
+        bld.free(a1)
+        saved["h"] = h
+        return y, saved
+
+    def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict) -> Act:
+        r"""Cotangent of the block's output -> cotangent of its input: g2 = c g; g3 = dgrad(conv2)(g2); g4 = g3 silu'(h);
+        g5 = dgrad(conv1)(g4); dx = g + norm_bwd(x, gamma = 1 + a, g5)."""
+        cs = pad4(self.channels)
+        abc, bstride, x = saved["abc"], saved["bstride"], saved["x"]
+        g2 = bld.channel_scale(g, abc, 2 * cs, bstride)
+        g3 = bld.conv_dgrad(g2, self.ffn[3], cache=cache)
+        bld.free(g2)
+        bld.silu_bwd(g3, saved["h"])
+        g5 = bld.conv_dgrad(g3, self.ffn[0], cache=cache)
+        bld.free(g3)
+        if self.norm_kind == "group":
+            dx = bld.group_norm_bwd(x, g5, saved["gn"], scale=abc, scale_off=0, bstride=bstride, res=g)
+        else:
+            dx = bld.row_norm_bwd(x, g5, 0 if self.norm_kind == "layer" else 1, scale=abc, scale_off=0, bstride=bstride, res=g)
+        bld.free(g5)
+        bld.free(g)
+        return dx
+
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, mod: Tensor | None = None):
+        r"""``(out, pullback)``: ``out = self(x, mod)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``), both on the HIP
+        tapes of a gradient plan (``mod`` is a constant of the pullback).  The pullback may be called any number of times
+        until the next ``vjp`` of this module with the same shapes.  fp32, spatial = 1 / 2, zero padding."""
+        from .utils import backbone_io_dtype
+
+        self._vjp_supported()
+        backbone_io_dtype(self, x, "azula_amd.nn.UNetBlock")
+        if x.dtype != torch.float32:
+            raise NotImplementedError("UNetBlock.vjp: fp32 tensors only")
+        one_d = self.spatial == 1
+        if one_d:
+            assert x.ndim == 3
+            x = x[:, :, None]
+        assert x.ndim == 4 and x.shape[1] == self.channels
+        B, Cc, H, W = x.shape
+        D = self.mod_features
+        rows = 0
+        if D > 0:
+            assert mod is not None, "this block is modulated: pass mod"
+            rows = 1 if mod.ndim == 1 else mod.shape[0]
+            assert rows in (1, B)
+        key = ("vjp", B, H, W, rows, str(x.device))
+        versions = tuple((p.data_ptr(), p._version, p.dtype) for p in self.parameters())
+        plan = self._plans.get(key)
+        if plan is None or plan.versions != versions:
+            plan = _GradTapes(x.device, B, Cc, Cc, H, W, rows, D, versions)
+            bld = plan.bld
+            xin = bld.new_act(B, H, W, Cc, pinned=True)
+            plan.fwd.add("az_nchw_to_nhwc_f32", xin.ptr, plan.x_in.data_ptr(), None, B, Cc, H * W, xin.cs)
+            bld.wrote(xin, bounded=False)
+            jobs: list = []
+            out, saved = self._emit_keep(bld, xin, D, rows, jobs)
+            bld.tape.add("az_nhwc_to_nchw_f32", plan.out.data_ptr(), out.ptr, B, Cc, H * W, out.cs)
+            plan.end_forward(jobs)
+            g = bld.new_act(B, H, W, Cc, pinned=True)
+            bld.tape.add("az_nchw_to_nhwc_f32", g.ptr, plan.v_in.data_ptr(), None, B, Cc, H * W, g.cs)
+            bld.wrote(g, bounded=False)
+            dx = self._emit_bwd(bld, g, saved, {})
+            bld.tape.add("az_nhwc_to_nchw_f32", plan.dx.data_ptr(), dx.ptr, B, Cc, H * W, dx.cs)
+            plan.end_backward()
+            self._plans[key] = plan
+        out, pullback = plan.run(x, mod)
+        if one_d:
+            return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
+        return out, pullback
+
     def _forward_3d(self, x: Tensor, mod: Tensor | None, out_dtype) -> Tensor:
         r"""(B, C, D, H, W): one-block plan on the volume form (see ``unet3d.py``)."""
         from .unet3d import Vol, block3d
@@ -313,6 +409,164 @@ class UNetPlan:
             self.tape = pre
 
 
+class _GradTapes:
+    r"""The two tapes of a gradient plan and their static planar buffers.  *forward-keep* (``fwd``): ``x_in`` (planar) ->
+    ``out`` (planar) with every tensor the pullback reads kept alive; *backward* (``bwd``): ``v_in`` (the cotangent of the
+    output, planar) -> ``dx`` (the cotangent of the input, planar).  The backward tape only writes temporaries of its own, so it
+    runs any number of times after one forward-keep run.  Plain ``Tape.run`` on the current stream: no graph capture."""
+
+    def __init__(self, device, B: int, cin: int, cout: int, H: int, W: int, mod_rows: int, D: int, versions) -> None:
+        self.versions = versions
+        self.bld = Builder(device)
+        self.x_in = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
+        self.out = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
+        self.v_in = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
+        self.dx = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
+        self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
+        self.mod_rows, self.D = mod_rows, D
+        self.fwd = self.bld.tape  # (the builder records onto it until end_forward)
+        self.bwd: Tape | None = None
+        self.serial = 0  # forward-keep runs so far: a pullback belongs to one of them
+
+    def end_forward(self, mod_jobs: list) -> None:
+        if mod_jobs:
+            pre = mod_front_tape(self.bld, mod_jobs, self.mod, self.mod_rows, self.D)
+            pre.extend(self.fwd)
+            self.fwd = pre
+        self.bld.tape = Tape()
+
+    def end_backward(self) -> None:
+        self.bld.finish()  # (one split-K workspace for both tapes)
+        self.bwd = self.bld.tape
+        self.bwd.keep.append(self.fwd)
+
+    @property
+    def saved_bytes(self) -> int:
+        return self.bld.pool.bytes
+
+    def run(self, x: Tensor, mod: Tensor | None):
+        self.x_in.copy_(x)
+        if self.mod_rows:
+            self.mod.copy_(mod.to(torch.float32).reshape(self.mod_rows, -1))
+        self.fwd.run()
+        self.serial += 1
+        serial = self.serial
+
+        @torch.no_grad()
+        def pullback(v: Tensor) -> Tensor:
+            if serial != self.serial:
+                raise RuntimeError("this pullback belongs to an earlier vjp call on the same module and shapes: its saved "
+                                   "tensors have been overwritten")
+            if not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != tuple(self.out.shape):
+                raise ValueError(f"pullback: expected an fp32 device tensor of shape {tuple(self.out.shape)}")
+            with torch.cuda.device(self.v_in.device):
+                self.v_in.copy_(v)
+                self.bwd.run()
+                return self.dx.clone()
+
+        return self.out.clone(), pullback
+
+
+class UNetGradPlan(_GradTapes):
+    r"""Gradient plan of a :class:`UNet` for one (batch, H, W, modulation-rows) signature: the forward-keep and backward tapes
+    (see :class:`_GradTapes`).  A different plan from :class:`UNetPlan`, whose launches it leaves untouched: no lazy
+    normalisation, no convolution-epilogue moments, SiLU as a pass of its own behind the kept pre-activation."""
+
+    def __init__(self, net: "UNet", B: int, H: int, W: int, mod_rows: int, device: torch.device) -> None:
+        cin, D = net.in_channels, net.mod_features
+        super().__init__(device, B, cin, net.out_channels, H, W, mod_rows, D, net._param_versions())
+        bld = self.bld
+        L = len(net.hid_blocks)
+        stride = net.stride
+        sv = (stride, stride) if isinstance(stride, int) else tuple(stride)
+        pow2 = all(v in (1, 2, 4, 8, 16) for v in sv)
+        up = 0
+        if pow2:
+            up = stride.bit_length() - 1 if isinstance(stride, int) else tuple(v.bit_length() - 1 for v in stride)
+        mod_jobs: list[tuple] = []
+
+        # ---- forward-keep: the order of UNetPlan, nothing the pullback reads is released
+        cur = bld.new_act(B, H, W, cin, pinned=True)
+        bld.tape.add("az_nchw_to_nhwc_f32", cur.ptr, self.x_in.data_ptr(), None, B, cin, H * W, cur.cs)
+        bld.wrote(cur, bounded=False)
+        skips: list[Act] = []
+        down: list[list[dict]] = []  # per level: the saved records of its descent blocks
+        sizes: list[tuple] = []  # per level: (H, W) of its maps
+        for i in range(L):
+            first = net.descent[i][0]
+            if i > 0:
+                skips.append(cur)
+            cur = bld.conv(cur, bld.pack_conv(first.weight, first.bias), first.out_channels, stride=stride if i > 0 else 1)
+            sizes.append((cur.H, cur.W))
+            recs = []
+            for j in range(net.hid_blocks[i]):
+                cur, rec = net.descent[i][1 + j]._emit_keep(bld, cur, D, mod_rows, mod_jobs)
+                recs.append((net.descent[i][1 + j], rec))
+            down.append(recs)
+        upr: dict[int, list] = {}
+        for k in range(L):
+            i = L - 1 - k
+            mods = net.ascent[k]
+            idx = 0
+            if i + 1 < L:
+                y = skips[i]
+                conv = mods[0]
+                if not pow2:
+                    wide = bld.upsample_nearest(cur, sv[0], sv[1], y.H, y.W)
+                    bld.free(cur)
+                    cur = wide
+                merged = bld.conv(y, bld.pack_conv(conv.weight, conv.bias, cin0=y.C), conv.out_channels, src1=cur, up1=up,
+                                  hin=y.H, win=y.W)
+                bld.free(cur)  # (outputs of a level's last block: no pullback reads them)
+                bld.free(y)
+                cur = merged
+                idx = 1
+            recs = []
+            for j in range(net.hid_blocks[i]):
+                cur, rec = mods[idx + j]._emit_keep(bld, cur, D, mod_rows, mod_jobs)
+                recs.append((mods[idx + j], rec))
+            upr[i] = recs
+            idx += net.hid_blocks[i]
+            if i == 0:
+                conv = mods[idx]
+                bld.conv(cur, bld.pack_conv(conv.weight, conv.bias), conv.out_channels, dst_nchw=self.out)
+                last = conv
+        self.end_forward(mod_jobs)
+
+        # ---- backward: the same graph walked from the output to the input
+        cache: dict = {}
+        v = bld.new_act(B, H, W, net.out_channels, pinned=True)
+        bld.tape.add("az_nchw_to_nhwc_f32", v.ptr, self.v_in.data_ptr(), None, B, net.out_channels, H * W, v.cs)
+        bld.wrote(v, bounded=False)
+        g = bld.conv_dgrad(v, last, cache=cache)
+        g_skip: dict[int, Act] = {}  # level -> the skip connection's share of that level's output cotangent
+        for i in range(L):
+            for blk, rec in reversed(upr[i]):
+                g = blk._emit_bwd(bld, g, rec, cache)
+            if i + 1 < L:
+                conv = net.ascent[L - 1 - i][0]
+                c0 = net.hid_channels[i]
+                g_skip[i] = bld.conv_dgrad(g, conv, cin_lo=0, cin_hi=c0, cache=cache)
+                g_up = bld.conv_dgrad(g, conv, cin_lo=c0, cache=cache)  # on the skip's grid: the narrowed, upsampled map
+                bld.free(g)
+                g = bld.upsample_nearest_bwd(g_up, sv[0], sv[1], *sizes[i + 1])
+                bld.free(g_up)
+        for i in range(L - 1, -1, -1):
+            for blk, rec in reversed(down[i]):
+                g = blk._emit_bwd(bld, g, rec, cache)
+            first = net.descent[i][0]
+            if i > 0:
+                wide = bld.zero_stuff(g, sv[0], sv[1], *sizes[i - 1])
+                bld.free(g)
+                g = bld.conv_dgrad(wide, first, res=g_skip[i - 1], cache=cache)  # (the level's output is consumed twice: its cotangents add)
+                bld.free(wide)
+                bld.free(g_skip[i - 1])
+            else:
+                bld.conv_dgrad(g, first, dst_nchw=self.dx, cache=cache)
+                bld.free(g)
+        self.end_backward()
+
+
 class UNet(nn.Module):
     r"""Modulated U-Net (reference ``azula/nn/unet.py:119-259``), gfx950-native forward.
 
@@ -397,6 +651,44 @@ class UNet(nn.Module):
             p = UNetPlan(self, B, H, W, mod_rows, device)
             self._plans[key] = p
         return p
+
+    # -- input gradient --------------------------------------------------------------------------------------------
+    def grad_plan(self, B: int, H: int, W: int, mod_rows: int, device: torch.device) -> UNetGradPlan:
+        key = ("vjp", B, H, W, mod_rows, str(device))
+        p = self._plans.get(key)
+        if p is None or p.versions != self._param_versions():
+            p = UNetGradPlan(self, B, H, W, mod_rows, device)
+            self._plans[key] = p
+        return p
+
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, mod: Tensor | None = None):
+        r"""``(out, pullback)``: ``out = self(x, mod)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``): the input
+        gradient that ``azula.guidance`` takes from ``torch.autograd``, on HIP tapes (``UNetGradPlan``).  ``mod`` is a
+        constant of the pullback; it may be called any number of times until the next ``vjp`` with the same shapes.
+        Scope: spatial = 1 / 2, zero padding, fp32 parameters and tensors, no ``cond_channels``; anything else raises
+        ``NotImplementedError`` (the forward is not affected)."""
+        self._check_device(x)
+        if self.spatial == 3 or self.periodic or self.cond_channels:
+            raise NotImplementedError("UNet.vjp: spatial = 1 / 2, zero padding, no cond_channels")
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            raise NotImplementedError("UNet.vjp: fp32 parameters and tensors only")
+        one_d = self.spatial == 1
+        if one_d:
+            assert x.ndim == 3, "spatial = 1: expected (B, C, L)"
+            x = x[:, :, None]
+        B, Cin, H, W = x.shape
+        assert Cin == self.in_channels
+        rows = 0
+        if self.mod_features > 0:
+            assert mod is not None, "this UNet is modulated: pass mod"
+            rows = 1 if mod.ndim == 1 else mod.shape[0]
+            assert rows in (1, B)
+        out, pullback = self.grad_plan(B, H, W, rows, x.device).run(x, mod)
+        if one_d:
+            return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
+        return out, pullback
 
     def _check_device(self, x: Tensor) -> torch.dtype:
         from .utils import backbone_io_dtype

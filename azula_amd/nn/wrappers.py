@@ -79,6 +79,26 @@ class TimeModulated(nn.Module):
         self._embed(None, ct, rows, mod, hid)
         return self.net(x_t, mod[0] if c_time.ndim == 0 else mod, **kwargs)
 
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x_t: Tensor, c_time: Tensor, **kwargs):
+        r"""``(out, pullback)`` of ``forward`` with respect to ``x_t`` (``c_time`` and the embedding are constants of the
+        pullback): the wrapped net's ``vjp`` behind the same embedding kernels.  A net without ``vjp`` raises
+        ``NotImplementedError``."""
+        if not x_t.is_cuda:
+            raise RuntimeError("azula_amd backbones execute only on an AMD GPU (no CPU fallback)")
+        inner = getattr(self.net, "vjp", None)
+        if inner is None:
+            raise NotImplementedError(f"{type(self.net).__name__} has no input-gradient (vjp) path on the HIP kernels")
+        if kwargs:
+            raise NotImplementedError(f"TimeModulated.vjp: keyword arguments {sorted(kwargs)} are not supported")
+        ct = c_time.to(device=x_t.device, dtype=torch.float32).reshape(-1, 1).contiguous()
+        rows = ct.shape[0]
+        hid = torch.empty(rows, self.features, dtype=torch.float32, device=x_t.device)
+        mod = torch.empty(rows, self.features, dtype=torch.float32, device=x_t.device)
+        self._embed(None, ct, rows, mod, hid)
+        return inner(x_t, mod[0] if c_time.ndim == 0 else mod)
+
     # -- fused sampling ---------------------------------------------------------------------------
     def _az_compile(self, x: Tensor, kwargs: dict, cur_coef: Tensor):
         inner = getattr(self.net, "_az_compile_modulated", None)

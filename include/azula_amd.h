@@ -296,6 +296,44 @@ int az_nchw_to_nhwc_f32(float* dst, const float* src, const float* scale_dev, in
 int az_upsample_nearest_f32(float* dst, const float* src, int64_t B, int64_t Hin, int64_t Win, int64_t cs, int32_t sh,
                             int32_t sw, int64_t Hout, int64_t Wout, az_stream_t stream);
 
+/* ------------------------------------------------------------------ input gradient (csrc/backward.hip)
+ * The passes of a vector-Jacobian product v -> (d out / d x)^T v through the UNet that are not convolutions -- what
+ * torch.autograd records behind azula/guidance/dps.py:55-68, pgdm.py:57-67, tmpd.py:55-71 and mmps.py:69-90 for the layers of
+ * azula/nn/unet.py:85-95,186,250-257.  (The data gradients of the convolutions run on the az_conv2d_* entries with the weight
+ * transposed and flipped.)  fp32, channel-padded NHWC (stride cs, pad lanes written as zero), deterministic: fixed-order
+ * reductions, no atomics.  `scale` (NULL: none) is the modulation a of gamma = 1 + a, read at scale[b * scale_bstride + c].
+ *
+ * GroupNorm backward (torch.nn.GroupNorm's pullback, biased variance; azula/nn/unet.py:91): with xh = (x - mean) rstd and
+ * q = gamma g,  dx = res + rstd (q - mean_group(q) - xh mean_group(q xh)).  `fpart` are the FORWARD records of
+ * az_groupnorm_stats_f32 over `fchunks` pixel chunks; the stats pass writes bpart[b][chunk][group] = (sum q, sum q xh, 0, 0)
+ * over `nchunks` chunks, the apply pass folds them and adds the residual `res` (NULL: none).                                  */
+int az_groupnorm_bwd_stats_f32(float* bpart, const float* x, const float* g, const float* scale, int64_t scale_bstride,
+                               const float* fpart, int32_t fchunks, int64_t B, int64_t HW, int64_t C, int64_t cs, int32_t groups,
+                               int32_t nchunks, float eps, az_stream_t stream);
+int az_groupnorm_bwd_apply_f32(float* dx, const float* x, const float* g, const float* res, const float* scale,
+                               int64_t scale_bstride, const float* fpart, int32_t fchunks, const float* bpart, int32_t nchunks,
+                               int64_t B, int64_t HW, int64_t C, int64_t cs, int32_t groups, float eps, az_stream_t stream);
+/* Row-norm backward, one row = one pixel (azula/nn/layers.py LayerNorm with the UNBIASED variance, kind 0:
+ * dx = res + rstd (q - mean(q) - xh mean(q xh) C / (C - 1)); RMSNorm, kind 1: dx = res + rstd (q - xh mean(q xh)), xh = x rstd). */
+int az_rownorm_bwd_f32(float* dx, const float* x, const float* g, const float* res, const float* scale, int64_t scale_bstride,
+                       int64_t rows, int64_t rows_per_batch, int64_t C, int64_t cs, int32_t kind, float eps, az_stream_t stream);
+/* y = g * silu'(p), silu'(p) = s (1 + p (1 - s)), s = 1 / (1 + exp(-p)), on the PRE-activation p (the nn.SiLU between the two
+ * convolutions of azula/nn/unet.py:76-83); n % 4 == 0; y may alias g.                                                        */
+int az_silu_bwd_f32(float* y, const float* g, const float* p, int64_t n, az_stream_t stream);
+/* y[b, p, c] = x[b, p, c] * s[b * s_bstride + c] (pad lanes zero): the gate c of out = x + c * y (azula/nn/unet.py:93) applied
+ * to the cotangent; y may alias x.                                                                                            */
+int az_channel_scale_f32(float* y, const float* x, const float* s, int64_t s_bstride, int64_t B, int64_t HW, int64_t C, int64_t cs,
+                         az_stream_t stream);
+/* The cotangent g (B, h, w, cs) of a convolution with stride (sh, sw) on the zero-filled (B, H, W, cs) grid of its input:
+ * G[b, i sh, j sw, :] = g[b, i, j, :], zero elsewhere ((h - 1) sh <= H - 1, (w - 1) sw <= W - 1).  A stride-1 convolution of G with
+ * the transposed, flipped weight is the data gradient of the strided convolution (azula/nn/unet.py:159-186).                 */
+int az_zero_stuff_f32(float* G, const float* g, int64_t B, int64_t h, int64_t w, int64_t cs, int32_t sh, int32_t sw, int64_t H,
+                      int64_t W, az_stream_t stream);
+/* Pullback of az_upsample_nearest_f32 (Upsample(nearest) + narrow, azula/nn/unet.py:186,250-255): dx[b, i, j, :] = the sum of
+ * g[b, i sh + di, j sw + dj, :] over the sh x sw window clipped to the narrowed (hn, wn) map; dx is (B, h, w, cs).            */
+int az_upsample_nearest_bwd_f32(float* dx, const float* g, int64_t B, int64_t h, int64_t w, int64_t cs, int32_t sh, int32_t sw,
+                                int64_t hn, int64_t wn, az_stream_t stream);
+
 int az_nhwc_to_nchw_f32(float* dst, const float* src, int64_t B, int64_t C, int64_t HW, int64_t cs,
                         az_stream_t stream);
 
