@@ -98,6 +98,24 @@ class AzRepaintArgs(C.Structure):
     ]
 
 
+class AzTdsProposeArgs(C.Structure):
+    _fields_ = [
+        ("x_t", c_f32p),
+        ("x_hat", c_f32p),
+        ("score", c_f32p),
+        ("z", c_f32p),
+        ("ancestors", C.c_void_p),
+        ("log_p", c_f32p),
+        ("coef", c_f32p),
+        ("x_s", c_f32p),
+        ("log_w_next", c_f32p),
+        ("workspace", C.c_void_p),
+        ("K", C.c_int64),
+        ("N", C.c_int64),
+        ("chunks", C.c_int64),
+    ]
+
+
 class AzCgArgs(C.Structure):
     _fields_ = [
         ("r0", C.c_void_p),
@@ -358,6 +376,9 @@ PROTOTYPES: dict[str, list] = {
     "az_transition_f32": [C.POINTER(AzTransitionArgs), c_stream],
     "az_multistep_f32": [C.POINTER(AzMultistepArgs), c_stream],
     "az_repaint_f32": [C.POINTER(AzRepaintArgs), c_stream],
+    "az_tds_chunks": [i64, i64],
+    "az_tds_resample_f32": [vp, vp, vp, vp, vp, i64, c_stream],
+    "az_tds_propose_f32": [C.POINTER(AzTdsProposeArgs), c_stream],
     "az_krylov_segments": [i64],
     "az_cg_init": [C.POINTER(AzCgArgs), c_stream],
     "az_cg_step": [C.POINTER(AzCgArgs), c_stream],
@@ -449,7 +470,8 @@ PROTOTYPES: dict[str, list] = {
     "az_calib_mfma_random_bf16": [vp, i32, i32, f32, f32, c_stream],
 }
 
-RESTYPES = {"az_f16x2_weight_scale": C.c_float, "az_krylov_segments": C.c_int64, "az_cov_segments": C.c_int64}  # (everything else returns an int status)
+RESTYPES = {"az_f16x2_weight_scale": C.c_float, "az_krylov_segments": C.c_int64, "az_cov_segments": C.c_int64,
+            "az_tds_chunks": C.c_int64}  # (everything else returns an int status)
 
 _lock = threading.Lock()
 _lib = None

@@ -1,6 +1,7 @@
 r"""Guidance (reference ``azula/guidance``): classifier-free guidance, RePaint inpainting, DiffPIR restoration, JFPS
-posterior sampling and the gradient-based methods DPS / PGDM / TMPD / MMPS (the network part of their gradients is the HIP
-input-gradient pass of the UNet) on the HIP path."""
+posterior sampling, the gradient-based methods DPS / PGDM / TMPD / MMPS (the network part of their gradients is the HIP
+input-gradient pass of the UNet) and the twisted SMC sampler TDS (the same pass, then fused resample / proposal kernels) on
+the HIP path."""
 
 from .cfg import CFGDenoiser  # noqa: F401
 from .diffpir import DiffPIRDenoiser  # noqa: F401
@@ -9,4 +10,5 @@ from .jfps import JFPSDenoiser  # noqa: F401
 from .mmps import MMPSDenoiser  # noqa: F401
 from .pgdm import PGDMSampler  # noqa: F401
 from .repaint import RePaintSampler  # noqa: F401
+from .tds import TDSSampler  # noqa: F401
 from .tmpd import TMPDenoiser  # noqa: F401

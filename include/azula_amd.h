@@ -147,6 +147,45 @@ typedef struct AzRepaintArgs {
 } AzRepaintArgs; /* 72 bytes */
 int az_repaint_f32(const AzRepaintArgs* args, az_stream_t stream);
 
+/* ---- Twisted diffusion sampler: resample and proposal -------------------------------------------------------------
+ * The non-network part of TDSSampler.step (azula/guidance/tds.py:70-102) for K particles of N elements each.
+ *
+ * az_tds_resample_f32 replaces tds.py:70-78: log_w = log_p (+ log_w_prev, NULL on the first step), w = softmax(log_w) and
+ * ancestors[j] = min{ i : c_i > u_j } (clamped to K - 1) with c the inclusive prefix sum of w -- multinomial sampling with
+ * replacement by inverse CDF on the caller's uniforms u[K] in [0, 1); it does not reproduce torch.multinomial's stream.  One
+ * workgroup; maximum, sums and the CDF in fp64 in a fixed order (two runs give the same bits); 1 <= K <= 65536 (else
+ * AZ_E_SHAPE).  A log-weight of -inf gives weight 0 and is never chosen.  If any log-weight is NaN or +inf, or all are -inf
+ * (the reference raises inside torch.multinomial), w = NaN and ancestors[j] = j.  Pointers: natural alignment.
+ *
+ * az_tds_propose_f32 replaces tds.py:80-102 in one pass over five K x N streams.  With k = ancestors[j] and `coef` a DEVICE
+ * pointer to [a_t, a_s, c_s = sigma_t^2 / alpha_t, k_x = sigma_s sqrt(tau) / sigma_t, scale = sigma_s sqrt(1 - tau), 1 / scale],
+ * tau = (alpha_t / alpha_s * sigma_s / sigma_t)^2 (tds.py:85):
+ *   m = x_hat[k] + c_s * score[k],   x_s[j] = a_s m + k_x (x_t[k] - a_t m) + scale z[j]
+ *   log_w_next[j] = -sum_i (z g + g^2 / 2) - log_p[k],   g = (a_s - k_x a_t) c_s score[k] / scale
+ * which is log q_s(x_s) - log q_{s|y}(x_s) - log_p[k] (tds.py:99-102) without the difference of two sums of log-densities.
+ * Each term is rounded once to fp32, summed in fp32 chains of at most 5 dependent adds, then in fp64 (csrc/tds.hip); the error
+ * of log_w_next is within 8 * 2^-24 * (sum_i |z g + g^2 / 2| + |log_p[k]|).  x_t, x_hat, score and log_p are NOT gathered by
+ * the caller.  x_s must not overlap x_t, x_hat, score or z (AZ_E_SHAPE).  `workspace` holds K * az_tds_chunks(K, N) doubles and
+ * `chunks` is that count; K <= 65536.  The K x N tensors and the workspace are 16-byte aligned.  scale == 0: x_s is the mean,
+ * log_w_next is not finite.  An ancestor outside [0, K) reads nothing and gives NaN for that particle.                       */
+int64_t az_tds_chunks(int64_t K, int64_t N);
+int az_tds_resample_f32(const float* log_p, const float* log_w_prev, const float* u, int64_t* ancestors, float* w, int64_t K,
+                        az_stream_t stream);
+typedef struct AzTdsProposeArgs {
+  const float* x_t;         /* (K, N), un-gathered                     */
+  const float* x_hat;       /* (K, N), un-gathered                     */
+  const float* score;       /* (K, N), un-gathered                     */
+  const float* z;           /* (K, N) standard normal                  */
+  const int64_t* ancestors; /* (K)                                     */
+  const float* log_p;       /* (K), un-gathered                        */
+  const float* coef;        /* DEVICE pointer, 6 floats                */
+  float* x_s;               /* (K, N)                                  */
+  float* log_w_next;        /* (K)                                     */
+  double* workspace;        /* K * chunks doubles                      */
+  int64_t K, N, chunks;
+} AzTdsProposeArgs; /* 104 bytes */
+int az_tds_propose_f32(const AzTdsProposeArgs* args, az_stream_t stream);
+
 /* ---- Krylov solvers: CG and GMRES ---------------------------------------------------------------------------------
  * Replace the per-iteration tensor arithmetic of azula/linalg/solve.py; the operator calls A(.) stay with the caller.  b is
  * (rows, dim) contiguous: one independent system per row (the reference's "...i,...i" dot products reduce over the last
