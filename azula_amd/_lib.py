@@ -366,6 +366,30 @@ class AzAttnArgs(C.Structure):
     ]
 
 
+class AzAttnBwdArgs(C.Structure):
+    _fields_ = [
+        ("q", c_f32p),
+        ("k", c_f32p),
+        ("v", c_f32p),
+        ("out", c_f32p),
+        ("dout", c_f32p),
+        ("dq", c_f32p),
+        ("dk", c_f32p),
+        ("dv", c_f32p),
+        ("workspace", c_f32p),
+        ("mask", c_f32p),
+        ("mask_bstride", C.c_int64),
+        ("mask_hstride", C.c_int64),
+        ("batch", C.c_int32),
+        ("heads", C.c_int32),
+        ("tokens", C.c_int32),
+        ("head_dim", C.c_int32),
+        *[(f"{n}_{s}stride", C.c_int64) for n in ("q", "k", "v", "o", "do", "dq", "dk", "dv") for s in "bth"],
+        ("scale", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
 # name -> argtypes.  Every symbol listed here MUST be exported by the shared object
@@ -402,6 +426,9 @@ PROTOTYPES: dict[str, list] = {
     "az_rownorm_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, f32, c_stream],
     "az_silu_bwd_f32": [vp, vp, vp, i64, c_stream],
     "az_channel_scale_f32": [vp, vp, vp, i64, i64, i64, i64, i64, c_stream],
+    "az_act_f32": [vp, vp, i64, i32, c_stream],
+    "az_act_bwd_f32": [vp, vp, vp, i64, i32, c_stream],
+    "az_swiglu_bwd_f32": [vp, vp, vp, i64, i64, i64, i64, c_stream],
     "az_zero_stuff_f32": [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, c_stream],
     "az_upsample_nearest_bwd_f32": [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, c_stream],
     "az_linear_small_f32": [vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, i32, c_stream],
@@ -450,6 +477,10 @@ PROTOTYPES: dict[str, list] = {
     "az_attention_f16x2_f32": [C.POINTER(AzAttnArgs), c_stream],
     "az_attention_bf16_f32": [C.POINTER(AzAttnArgs), c_stream],
     "az_attention_f16_f32": [C.POINTER(AzAttnArgs), c_stream],
+    "az_qk_prep_f32": [vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, f32, vp, vp, c_stream],
+    "az_qk_prep_bwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, f32, vp, vp,
+                           c_stream],
+    "az_attention_bwd_f32": [C.POINTER(AzAttnBwdArgs), c_stream],
     "az_swiglu_f32": [vp, vp, i64, i64, i64, i64, c_stream],
     "az_patchify_f32": [vp, vp, vp, i64, i64, i64, i64, i64, i64, c_stream],
     "az_unpatchify_f32": [vp, vp, i64, i64, i64, i64, i64, i64, c_stream],

@@ -7,6 +7,7 @@
 //                        (the (n, mean, M2, 0) records of az_groupnorm_stats_f32), so nothing but those records is saved
 //   row norm backward  : LayerNorm (unbiased variance) / RMSNorm over the channel axis, one wave per pixel row
 //   SiLU backward      : y = g * silu'(p) on the PRE-activation p
+//   FFN activations    : silu / relu / relu^2 as passes of their own and their pullbacks; the SwiGLU pullback (DiT block)
 //   channel scale      : y = x * s[b, c] (the gate c of out = x + c * y, applied to the cotangent)
 //   zero stuffing      : the cotangent of a strided convolution on the zero-filled grid of its input
 //   nearest upsampling backward : clipped window sums
@@ -249,6 +250,59 @@ __global__ __launch_bounds__(256) void silu_bwd_kernel(float* __restrict__ y, co
   }
 }
 
+// FFN activations of the DiT block as passes of their own and their derivatives on the pre-activation p.  kind 1: silu,
+// 2: relu, 3: relu(p)^2.
+__device__ __forceinline__ float act_val(float p, int kind) {
+  if (kind == 1) return az_silu(p);
+  const float r = fmaxf(p, 0.f);
+  return kind == 2 ? r : r * r;
+}
+__device__ __forceinline__ float act_grad(float p, int kind) {
+  if (kind == 1) return silu_grad(p);
+  if (kind == 2) return p > 0.f ? 1.f : 0.f;
+  return 2.f * fmaxf(p, 0.f);
+}
+
+__global__ __launch_bounds__(256) void act_kernel(float* __restrict__ y, const float* __restrict__ x, int64_t n4, int kind) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const float4 v = reinterpret_cast<const float4*>(x)[i];
+    reinterpret_cast<float4*>(y)[i] = make_float4(act_val(v.x, kind), act_val(v.y, kind), act_val(v.z, kind), act_val(v.w, kind));
+  }
+}
+
+__global__ __launch_bounds__(256) void act_bwd_kernel(float* __restrict__ y, const float* __restrict__ g, const float* __restrict__ p,
+                                                      int64_t n4, int kind) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    const float4 pv = reinterpret_cast<const float4*>(p)[i];
+    reinterpret_cast<float4*>(y)[i] = make_float4(gv.x * act_grad(pv.x, kind), gv.y * act_grad(pv.y, kind),
+                                                  gv.z * act_grad(pv.z, kind), gv.w * act_grad(pv.w, kind));
+  }
+}
+
+// One thread per two input pairs (a float4 of x): dx[2c] = g silu(x[2c+1]), dx[2c+1] = g x[2c] silu'(x[2c+1]); lanes past 2 cout zero.
+__global__ __launch_bounds__(256) void swiglu_bwd_kernel(float* __restrict__ dx, const float* __restrict__ g,
+                                                         const float* __restrict__ x, int64_t rows, int cout, int64_t xs, int64_t gs) {
+  const int q = (int)(xs / 4);
+  const int64_t total = rows * q;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+    const int64_t r = i / q;
+    const int c = 2 * (int)(i % q);
+    const float4 v = *reinterpret_cast<const float4*>(x + r * xs + 2 * c);
+    const float g0 = c < cout ? g[r * gs + c] : 0.f;
+    const float g1 = c + 1 < cout ? g[r * gs + c + 1] : 0.f;
+    float4 o;
+    o.x = c < cout ? g0 * az_silu(v.y) : 0.f;
+    o.y = c < cout ? g0 * v.x * silu_grad(v.y) : 0.f;
+    o.z = c + 1 < cout ? g1 * az_silu(v.w) : 0.f;
+    o.w = c + 1 < cout ? g1 * v.z * silu_grad(v.w) : 0.f;
+    *reinterpret_cast<float4*>(dx + r * xs + 2 * c) = o;
+  }
+}
+
 // y[b, p, c] = x[b, p, c] * s[b * bstride + c]; grid.y = sample.
 __global__ __launch_bounds__(256) void channel_scale_kernel(float* __restrict__ y, const float* __restrict__ x,
                                                             const float* __restrict__ s, int64_t bstride, int64_t HW, int C, int cs) {
@@ -381,6 +435,32 @@ int az_silu_bwd_f32(float* y, const float* g, const float* p, int64_t n, az_stre
   AZ_REQUIRE(n > 0 && n % 4 == 0, AZ_E_SHAPE);
   AZ_REQUIRE(AZ_ALIGNED16(y) && AZ_ALIGNED16(g) && AZ_ALIGNED16(p), AZ_E_ALIGN);
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(az_stream_grid(n / 4, 256)), dim3(256), 0, az_s(stream), y, g, p, n / 4);
+  return az_launch_status();
+}
+
+int az_act_f32(float* y, const float* x, int64_t n, int32_t kind, az_stream_t stream) {
+  AZ_REQUIRE(y && x, AZ_E_NULL);
+  AZ_REQUIRE(n > 0 && n % 4 == 0 && kind >= 1 && kind <= 3, AZ_E_SHAPE);
+  AZ_REQUIRE(AZ_ALIGNED16(y) && AZ_ALIGNED16(x), AZ_E_ALIGN);
+  hipLaunchKernelGGL(act_kernel, dim3(az_stream_grid(n / 4, 256)), dim3(256), 0, az_s(stream), y, x, n / 4, (int)kind);
+  return az_launch_status();
+}
+
+int az_act_bwd_f32(float* y, const float* g, const float* p, int64_t n, int32_t kind, az_stream_t stream) {
+  AZ_REQUIRE(y && g && p, AZ_E_NULL);
+  AZ_REQUIRE(n > 0 && n % 4 == 0 && kind >= 1 && kind <= 3, AZ_E_SHAPE);
+  AZ_REQUIRE(AZ_ALIGNED16(y) && AZ_ALIGNED16(g) && AZ_ALIGNED16(p), AZ_E_ALIGN);
+  hipLaunchKernelGGL(act_bwd_kernel, dim3(az_stream_grid(n / 4, 256)), dim3(256), 0, az_s(stream), y, g, p, n / 4, (int)kind);
+  return az_launch_status();
+}
+
+int az_swiglu_bwd_f32(float* dx, const float* g, const float* x, int64_t rows, int64_t cout, int64_t xs, int64_t gs,
+                      az_stream_t stream) {
+  AZ_REQUIRE(dx && g && x, AZ_E_NULL);
+  AZ_REQUIRE(rows > 0 && cout > 0 && cout < (1ll << 30) && xs >= 2 * cout && gs >= cout && xs % 4 == 0, AZ_E_SHAPE);
+  AZ_REQUIRE(AZ_ALIGNED16(dx) && AZ_ALIGNED16(x), AZ_E_ALIGN);
+  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(az_stream_grid(rows * (xs / 4), 256)), dim3(256), 0, az_s(stream), dx, g, x, rows,
+                     (int)cout, xs, gs);
   return az_launch_status();
 }
 

@@ -821,6 +821,113 @@ class Builder:
         self.tape.add("az_upsample_nearest_bwd_f32", y.ptr, g.ptr, g.B, h, w, g.cs, sh, sw, g.H, g.W)
         return self.wrote(y, bounded=False)
 
+    # -- input gradient through attention (csrc/attention_bwd.hip) and the DiT block's FFN activations -----------------
+    def act(self, x: Act, kind: int) -> Act:
+        r"""y = act(x) as a pass of its own (kind 1: silu, 2: relu, 3: relu^2) behind a kept pre-activation."""
+        y = self.new_act(x.B, x.H, x.W, x.C)
+        self.tape.add("az_act_f32", y.ptr, x.ptr, x.B * x.H * x.W * x.cs, kind)
+        return self.wrote(y, bounded=False)
+
+    def act_bwd(self, g: Act, p: Act, kind: int) -> Act:
+        r"""g <- g * act'(p) in place (``p``: the kept PRE-activation; kinds of :meth:`act`)."""
+        assert (g.B, g.H, g.W, g.cs) == (p.B, p.H, p.W, p.cs)
+        self.tape.add("az_act_bwd_f32", g.ptr, g.ptr, p.ptr, g.B * g.H * g.W * g.cs, kind, keep=[p.buf])
+        return self.wrote(g, bounded=False)
+
+    def swiglu(self, x: Act) -> Act:
+        r"""y[c] = x[2c] * silu(x[2c+1]) as a pass of its own (``x``: the kept pre-activation)."""
+        y = self.new_act(x.B, x.H, x.W, x.C // 2)
+        self.tape.add("az_swiglu_f32", y.ptr, x.ptr, x.B * x.H * x.W, x.C // 2, x.cs, y.cs)
+        return self.wrote(y, bounded=False)
+
+    def swiglu_bwd(self, g: Act, p: Act) -> Act:
+        r"""Cotangent of the SwiGLU output -> cotangent of its (twice as wide) kept pre-activation ``p``."""
+        assert (g.B, g.H, g.W, 2 * g.C) == (p.B, p.H, p.W, p.C)
+        y = self.new_act(p.B, p.H, p.W, p.C)
+        self.tape.add("az_swiglu_bwd_f32", y.ptr, g.ptr, p.ptr, p.B * p.H * p.W, g.C, p.cs, g.cs, keep=[p.buf])
+        return self.wrote(y, bounded=False)
+
+    def _attn_mask(self, mask: torch.Tensor, B: int, heads: int, L: int) -> tuple:
+        r"""(byte mask on the device, batch stride, head stride) of a boolean mask as :meth:`attention` reads it."""
+        m = mask[None, None] if mask.ndim == 2 else mask
+        if m.ndim != 4 or m.shape[-2:] != (L, L) or m.shape[0] not in (1, B) or m.shape[1] not in (1, heads):
+            raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast to ({B}, {heads}, {L}, {L})")
+        m8 = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        self.tape.keep.append(m8)
+        return m8, (m8.stride(0) if m.shape[0] > 1 else 0), (m8.stride(1) if m.shape[1] > 1 else 0)
+
+    def attention_keep(self, qkv: Act, heads: int, qk_rmsnorm: bool, scale: float, eps: float = 1e-5, rope: tuple | None = None,
+                       mask: torch.Tensor | None = None, norm_dim: int = 0) -> tuple[Act, dict]:
+        r"""The forward of :meth:`attention` ('(n H C)' order, fp32) with what :meth:`attention_bwd` reads kept: q^ | k^ =
+        rope(rms_norm(q | k)) go out of place into a buffer of their own (``az_qk_prep_f32``), then the forward attention entry
+        :func:`choose_attention` picks runs on (q^, k^, v) with no norm and no tables.  Returns (out, record); ``qkv``, q^ | k^
+        and ``out`` must stay alive for the pullback (the caller does not free them)."""
+        from ._lib import AzAttnArgs
+
+        Cq = qkv.C // 3
+        dim = Cq // heads
+        assert qkv.cs == qkv.C and dim * heads == Cq and not qkv.half and self.half is None
+        assert dim in ATTN_GRAD_HEAD_DIMS, dim
+        B, L = qkv.B, qkv.H * qkv.W
+        cos, sin = rope if rope is not None else (None, None)
+        qk = self.new_act(B, qkv.H, qkv.W, 2 * Cq, pinned=True)
+        self.tape.add("az_qk_prep_f32", qk.ptr, qk.ptr + 4 * Cq, qkv.ptr, qkv.ptr + 4 * Cq, B, L, heads, dim, L * qkv.cs, qkv.cs, dim,
+                      L * qk.cs, qk.cs, dim, int(qk_rmsnorm), norm_dim, eps, cos.data_ptr() if cos is not None else None,
+                      sin.data_ptr() if sin is not None else None, keep=[qkv.buf, cos, sin])
+        self.wrote(qk, bounded=False)
+        out = self.new_act(B, qkv.H, qkv.W, Cq)
+        a = AzAttnArgs()
+        a.q, a.k, a.v, a.out = qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 8 * Cq, out.ptr
+        a.batch, a.heads, a.tokens, a.head_dim = B, heads, L, dim
+        a.q_bstride, a.q_tstride, a.q_hstride = L * qk.cs, qk.cs, dim
+        a.k_bstride, a.k_tstride, a.k_hstride = L * qk.cs, qk.cs, dim
+        a.v_bstride, a.v_tstride, a.v_hstride = L * qkv.cs, qkv.cs, dim
+        a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
+        a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, 0, eps, 0
+        rec = dict(qkv=qkv, qk=qk, out=out, heads=heads, dim=dim, scale=scale, eps=eps, rms=bool(qk_rmsnorm), norm_dim=norm_dim,
+                   rope=rope, mask=None)
+        if mask is not None:
+            m8, mb, mh = rec["mask"] = self._attn_mask(mask, B, heads, L)
+            a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
+        kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, None) if qk_rmsnorm else (math.inf, math.inf)
+        a._flops = 4 * B * heads * L * L * dim
+        self.tape.add(choose_attention(dim, kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX, None), C.byref(a), keep=[a, qk.buf])
+        return self.wrote(out, bounded=False), rec
+
+    def attention_bwd(self, g: Act, rec: dict) -> Act:
+        r"""Cotangent ``g`` of the attention output -> cotangent of the fused q | k | v token tensor: ``az_attention_bwd_f32``
+        (dq^ | dk^ into a temporary, dv straight into its third) and ``az_qk_prep_bwd_f32`` (the q and k thirds)."""
+        from ._lib import AzAttnBwdArgs
+
+        qkv, qk, out, heads, dim = rec["qkv"], rec["qk"], rec["out"], rec["heads"], rec["dim"]
+        Cq = heads * dim
+        B, L = qkv.B, qkv.H * qkv.W
+        assert (g.B, g.H, g.W, g.C) == (out.B, out.H, out.W, out.C)
+        dqk = self.new_act(B, qkv.H, qkv.W, 2 * Cq)
+        dqkv = self.new_act(B, qkv.H, qkv.W, 3 * Cq)
+        a = AzAttnBwdArgs()
+        a.q, a.k, a.v, a.out, a.dout = qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 8 * Cq, out.ptr, g.ptr
+        a.dq, a.dk, a.dv = dqk.ptr, dqk.ptr + 4 * Cq, dqkv.ptr + 8 * Cq
+        a.workspace = self.empty(2 * B * heads * L).data_ptr()
+        a.batch, a.heads, a.tokens, a.head_dim, a.scale = B, heads, L, dim, rec["scale"]
+        for n, t in (("q", qk), ("k", qk), ("v", qkv), ("o", out), ("do", g), ("dq", dqk), ("dk", dqk), ("dv", dqkv)):
+            setattr(a, n + "_bstride", L * t.cs)
+            setattr(a, n + "_tstride", t.cs)
+            setattr(a, n + "_hstride", dim)
+        if rec["mask"] is not None:
+            m8, mb, mh = rec["mask"]
+            a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
+        a._flops = 16 * B * heads * L * L * dim
+        self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qk.buf, qkv.buf, out.buf, rec["mask"]])
+        self.wrote(dqk, bounded=False)
+        cos, sin = rec["rope"] if rec["rope"] is not None else (None, None)
+        self.tape.add("az_qk_prep_bwd_f32", dqkv.ptr, dqkv.ptr + 4 * Cq, dqk.ptr, dqk.ptr + 4 * Cq, qkv.ptr, qkv.ptr + 4 * Cq, B, L, heads,
+                      dim, L * dqk.cs, dqk.cs, dim, L * qkv.cs, qkv.cs, dim, L * dqkv.cs, dqkv.cs, dim, int(rec["rms"]), rec["norm_dim"],
+                      rec["eps"], cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None,
+                      keep=[cos, sin])
+        self.free(dqk)
+        return self.wrote(dqkv, bounded=False)
+
     def finish(self) -> None:
         r"""Allocates the shared split-K workspace and patches it into the recorded convs."""
         if self._ws_need and (self.workspace is None or self.workspace.numel() < self._ws_need):
@@ -1051,6 +1158,25 @@ def transition_args(**kw) -> AzTransitionArgs:
 # projection with d' - d zero input columns per head; the scale stays 1 / sqrt(d), the q / k RMS norm averages over d
 # (AzAttnArgs.norm_dim), padded RoPE pairs do not turn (theta = 0) and padded gains are 1.  (G24: 24, 48, 96.)
 ATTN_HEAD_DIMS = (16, 32, 64, 80, 128)
+
+
+# The attention backward kernels (csrc/attention_bwd.hip) are instantiated for these four: a gradient plan pads to the next of THEM
+# (80 -> 128), through the same zero-padded packing -- the padded gradient rows meet zero weight columns in the data-gradient GEMM.
+ATTN_GRAD_HEAD_DIMS = (16, 32, 64, 128)
+
+
+def attn_grad_padded_dim(d: int) -> int:
+    for v in ATTN_GRAD_HEAD_DIMS:
+        if d <= v:
+            return v
+    raise NotImplementedError(f"attention head size {d}: the gfx950 attention backward kernels go up to 128 channels per head")
+
+
+class LinearView:
+    r"""A linear layer's (possibly head-padded) weight as the (cout, cin, 1, 1) ``.weight`` :meth:`Builder.conv_dgrad` takes."""
+
+    def __init__(self, weight: torch.Tensor) -> None:
+        self.weight = weight.detach().reshape(weight.shape[0], -1)[:, :, None, None]
 
 
 def attn_padded_dim(d: int, half=None) -> int:

@@ -415,13 +415,16 @@ class _GradTapes:
     output, planar) -> ``dx`` (the cotangent of the input, planar).  The backward tape only writes temporaries of its own, so it
     runs any number of times after one forward-keep run.  Plain ``Tape.run`` on the current stream: no graph capture."""
 
-    def __init__(self, device, B: int, cin: int, cout: int, H: int, W: int, mod_rows: int, D: int, versions) -> None:
+    def __init__(self, device, B: int, cin: int, cout: int, H: int, W: int, mod_rows: int, D: int, versions, tokens: bool = False) -> None:
         self.versions = versions
         self.bld = Builder(device)
-        self.x_in = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
-        self.out = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
-        self.v_in = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
-        self.dx = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
+        if tokens:  # (B, L, C) token plans: the four buffers are views of the plan's own activations (DiTGradPlan / vit.py)
+            self.x_in = self.out = self.v_in = self.dx = None
+        else:
+            self.x_in = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
+            self.out = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
+            self.v_in = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
+            self.dx = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
         self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
         self.mod_rows, self.D = mod_rows, D
         self.fwd = self.bld.tape  # (the builder records onto it until end_forward)

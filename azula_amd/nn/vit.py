@@ -14,6 +14,9 @@ implicit GEMM with ksize = 1):
 * RMSNorm + modulation is one row-norm pass; q/k RMSNorm and the 1/sqrt(C) scale are folded
   into the attention kernel's operand loads; ``y + y_proj(att)``, SiLU and ``x + c * ffn`` are
   GEMM epilogues.
+
+Input gradient (``vjp``): forward-keep and backward tapes on the attention backward kernels (``csrc/attention_bwd.hip``),
+:class:`DiTGradPlan`; DESIGN.md section 9.
 """
 
 from __future__ import annotations
@@ -26,7 +29,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _lib, engine
-from ..engine import Act, Builder, Tape, ada_zero_triple, mod_front_tape, pad4
+from ..engine import Act, Builder, LinearView, Tape, ada_zero_triple, mod_front_tape, pad4
+from .unet import _GradTapes
 
 __all__ = ["DiT", "DiTBlock", "MultiheadSelfAttention", "ViT"]
 
@@ -93,6 +97,59 @@ class MultiheadSelfAttention(nn.Module):
         out = bld.conv(att, bld.pack_conv(self.y_proj.weight, None), C_, res=res)
         bld.free(att)
         return out
+
+    # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
+    def _emit_keep(self, bld: Builder, y: Act, pos_h: Tensor | None, mask: Tensor | None, res: Act | None = None) -> tuple[Act, dict]:
+        r"""The forward of :meth:`_emit` with what the pullback reads kept: the raw ``qkv``, q^ | k^ and the attention output
+        in front of ``y_proj`` (``Builder.attention_keep``).  The projection runs without the q / k epilogue; head sizes other
+        than 16 / 32 / 64 / 128 run zero-padded to the next of these (``engine.attn_grad_padded_dim``)."""
+        C_ = self.qkv_proj.in_features
+        d = C_ // self.heads
+        dp = engine.attn_grad_padded_dim(d)
+        theta = None
+        if self.theta_proj is not None:
+            if pos_h is None:
+                raise ValueError("this attention layer uses RoPE: pass pos")
+            theta = torch.nn.functional.linear(pos_h.to(torch.float32).cpu(), self.theta_proj.weight.detach().float().cpu())
+        wq, bq, wy = self.qkv_proj.weight, self.qkv_proj.bias, self.y_proj.weight
+        if dp != d:
+            if theta is not None:
+                theta = engine.pad_head_table(theta, self.heads, d // 2, dp // 2)
+            wq, bq = engine.pad_qkv_heads(wq, bq, self.heads, d, dp, "nHC")
+            wy = engine.pad_proj_heads(wy, self.heads, d, dp)
+        rope = None if theta is None else (bld.const(torch.cos(theta)), bld.const(torch.sin(theta)))
+        qkv = bld.conv(y, bld.pack_conv(wq, bq), 3 * self.heads * dp)
+        att, rec = bld.attention_keep(qkv, self.heads, self.qk_norm, 1.0 / math.sqrt(d), rope=rope, mask=mask,
+                                      norm_dim=d if dp != d else 0)
+        out = bld.conv(att, bld.pack_conv(wy, None), C_, res=res)
+        return out, {"attn": rec, "wq": LinearView(wq), "wy": LinearView(wy)}
+
+    def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict, res: Act | None = None) -> Act:
+        r"""Cotangent of the layer's output -> cotangent of its input (+ ``res`` in the epilogue of the qkv data-gradient GEMM)."""
+        g_att = bld.conv_dgrad(g, saved["wy"], cache=cache)
+        dqkv = bld.attention_bwd(g_att, saved["attn"])
+        bld.free(g_att)
+        gy = bld.conv_dgrad(dqkv, saved["wq"], res=res, cache=cache)
+        bld.free(dqkv)
+        return gy
+
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, pos: Tensor | None = None, mask: Tensor | None = None):
+        r"""``(out, pullback)``: ``out = self(x, pos, mask)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``) on the HIP
+        tapes of a gradient plan.  The pullback may be called any number of times until the next ``vjp`` of this module with
+        the same signature.  fp32 parameters and tensors, head sizes up to 128; anything else raises ``NotImplementedError``."""
+        _vjp_scope(self, x, "MultiheadSelfAttention")
+
+        def build(plan, xin, pos_h):
+            bld = plan.bld
+            out, saved = self._emit_keep(bld, xin, pos_h, mask)
+            plan.set_output(out)
+            plan.end_forward([])
+            g = plan.cotangent(out.C)
+            plan.set_dx(self._emit_bwd(bld, g, saved, {}))
+
+        return _token_grad_plan(self, x, pos, mask, 0, None, build).run(x, None)
 
     @torch.no_grad()
     @_lib.on_device
@@ -200,6 +257,85 @@ def _token_plan(module, x: Tensor, pos, mask, D: int, emit, mod: Tensor | None =
     return plan
 
 
+def _vjp_scope(module: nn.Module, x: Tensor, name: str) -> None:
+    r"""The input-gradient tapes take fp32 parameters and fp32 device tensors, and head sizes the backward kernels reach."""
+    from .utils import backbone_io_dtype
+
+    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in module.parameters()):
+        raise NotImplementedError(f"{name}.vjp: fp32 parameters and tensors only")
+    backbone_io_dtype(module, x, f"azula_amd.nn.{name}")
+    for m in module.modules():
+        if isinstance(m, MultiheadSelfAttention):
+            engine.attn_grad_padded_dim(m.qkv_proj.in_features // m.heads)  # (raises NotImplementedError above 128)
+
+
+class _TokenGradTapes(_GradTapes):
+    r""":class:`_GradTapes` on (B, L, C) token tensors: ``x_in`` / ``out`` / ``v_in`` / ``dx`` are views of the plan's own
+    (channel-padded) activations, so nothing is rearranged on the way in or out."""
+
+    def __init__(self, device, B: int, L: int, cin: int, mod_rows: int, D: int, versions) -> None:
+        super().__init__(device, B, cin, cin, L, 1, mod_rows, D, versions, tokens=True)
+        self.B, self.L = B, L
+
+    def _pinned(self, channels: int) -> Act:
+        a = self.bld.new_act(self.B, self.L, 1, channels, pinned=True)
+        a.buf.zero_()  # (the pad lanes stay zero: only the real channels are ever copied in)
+        return self.bld.wrote(a, bounded=False)
+
+    def _view(self, a: Act) -> Tensor:
+        return a.buf.view(self.B, self.L, a.cs)[..., : a.C]
+
+    def token_input(self, channels: int) -> Act:
+        a = self._pinned(channels)
+        self.x_in = self._view(a)
+        return a
+
+    def cotangent(self, channels: int) -> Act:
+        a = self._pinned(channels)
+        self.v_in = self._view(a)
+        return a
+
+    def set_output(self, out: Act) -> None:
+        out.pinned = True
+        self.out = self._view(out)
+
+    def set_dx(self, dx: Act) -> None:
+        dx.pinned = True
+        self.dx = self._view(dx)
+        self.end_backward()
+
+    def run(self, x: Tensor, mod: Tensor | None):
+        lead = tuple(x.shape[:-2])  # (standalone modules take (*, L, C))
+        out, pull = super().run(x.reshape(self.B, self.L, -1), mod)
+        if lead == (self.B,):
+            return out, pull
+        return out.reshape(*lead, self.L, -1), lambda v: pull(v.reshape(self.B, self.L, -1)).reshape(*lead, self.L, -1)
+
+
+def _token_grad_plan(module, x: Tensor, pos, mask, D: int, mod: Tensor | None, build) -> _TokenGradTapes:
+    r"""Gradient-plan cache of a standalone token module, keyed on shapes, the content of positions and mask, and parameter
+    versions.  ``build(plan, x_in, pos_h)`` emits both tapes."""
+    assert x.ndim >= 2, "expected (*, L, C) tokens"
+    L, Cin = x.shape[-2], x.shape[-1]
+    B = x.numel() // (L * Cin)
+    rows = 0
+    if D > 0:
+        assert mod is not None, "this block is modulated: pass mod"
+        rows = 1 if mod.ndim == 1 else mod.numel() // mod.shape[-1]
+        assert rows in (1, B), "mod must be (D) or (*, D) with the leading shape of x"
+    pos_h = None if pos is None else pos.detach().to("cpu", torch.float32).reshape(L, -1)
+    content = (None if pos_h is None else pos_h.numpy().tobytes(),
+               None if mask is None else (tuple(mask.shape), mask.detach().cpu().numpy().tobytes()))
+    key = ("vjp", B, L, Cin, rows, str(x.device), content)
+    versions = _versions(module)
+    plan = module._plans.get(key)
+    if plan is None or plan.versions != versions:
+        plan = _TokenGradTapes(x.device, B, L, Cin, rows, D, versions)
+        build(plan, plan.token_input(Cin), pos_h)
+        module._plans[key] = plan
+    return plan
+
+
 class DiTBlock(nn.Module):
     r"""Parameter holder of a modulated DiT block (reference ``azula/nn/dit.py:24-93``)."""
 
@@ -257,6 +393,69 @@ class DiTBlock(nn.Module):
         if not keep_input:
             bld.free(x)
         return out
+
+    # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
+    _ACT_KIND = {"silu": 1, "relu": 2, "relu2": 3}
+
+    def _emit_keep(self, bld: Builder, x: Act, pos_h, mask, D: int, mod_rows: int, mod_jobs: list) -> tuple[Act, dict]:
+        r"""The forward of :meth:`_emit` with what the pullback reads kept alive: the block input ``x``, the attention layer's
+        record (raw qkv, q^ | k^, attention output) and the FFN PRE-activation ``h`` (``ffn[0]`` runs without its activation
+        epilogue; the activation is a pass of its own behind it).  The modulated norm output and ``y2`` are only read by
+        weight gradients, which an input gradient does not need: they go back to the pool."""
+        C_, cs = self.channels, pad4(self.channels)
+        abc, bstride = ada_zero_triple(bld, self.ada_zero, C_, D, mod_rows, mod_jobs)
+        y = bld.row_norm(x, 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
+        y2, msa = self.msa._emit_keep(bld, y, pos_h, mask, res=y)
+        bld.free(y)
+        f0, f3 = self.ffn[0], self.ffn[3]
+        h = bld.conv(y2, bld.pack_conv(f0.weight, f0.bias), f0.out_features)
+        bld.free(y2)
+        a1 = bld.swiglu(h) if self.ffn_activation == "swiglu" else bld.act(h, self._ACT_KIND[self.ffn_activation])
+        out = bld.conv(a1, bld.pack_conv(f3.weight, f3.bias), C_, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
+        bld.free(a1)
+        return out, {"x": x, "abc": abc, "bstride": bstride, "msa": msa, "h": h, "f0": LinearView(f0.weight), "f3": LinearView(f3.weight)}
+
+    def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict) -> Act:
+        r"""Cotangent of the block's output -> cotangent of its input: g_f = c g; g_y2 = ffn^T g_f; g_y = g_y2 + msa^T g_y2 (the
+        add in the qkv data-gradient GEMM's epilogue); dx = g + norm^T g_y (``az_rownorm_bwd_f32`` with ``res = g``)."""
+        cs = pad4(self.channels)
+        abc, bstride = saved["abc"], saved["bstride"]
+        g2 = bld.channel_scale(g, abc, 2 * cs, bstride)
+        g3 = bld.conv_dgrad(g2, saved["f3"], cache=cache)
+        bld.free(g2)
+        if self.ffn_activation == "swiglu":
+            g4 = bld.swiglu_bwd(g3, saved["h"])
+            bld.free(g3)
+        else:
+            g4 = bld.act_bwd(g3, saved["h"], self._ACT_KIND[self.ffn_activation])
+        g5 = bld.conv_dgrad(g4, saved["f0"], cache=cache)
+        bld.free(g4)
+        gy = self.msa._emit_bwd(bld, g5, saved["msa"], cache, res=g5)
+        bld.free(g5)
+        dx = bld.row_norm_bwd(saved["x"], gy, 1, scale=abc, scale_off=0, bstride=bstride, res=g)
+        bld.free(gy)
+        bld.free(g)
+        return dx
+
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, mod: Tensor | None = None, pos: Tensor | None = None, mask: Tensor | None = None):
+        r"""``(out, pullback)``: ``out = self(x, mod, pos, mask)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``; ``mod`` is
+        a constant of the pullback), both on the HIP tapes of a gradient plan.  Callable any number of times until the next
+        ``vjp`` of this module with the same signature.  fp32 parameters and tensors, head sizes up to 128."""
+        _vjp_scope(self, x, "DiTBlock")
+        D = self.mod_features
+
+        def build(plan, xin, pos_h):
+            bld = plan.bld
+            jobs: list = []
+            out, saved = self._emit_keep(bld, xin, pos_h, mask, D, plan.mod_rows, jobs)
+            plan.set_output(out)
+            plan.end_forward(jobs)
+            g = plan.cotangent(out.C)
+            plan.set_dx(self._emit_bwd(bld, g, saved, {}))
+
+        return _token_grad_plan(self, x, pos, mask, D, mod, build).run(x, mod)
 
     @torch.no_grad()
     @_lib.on_device
@@ -342,6 +541,48 @@ class DiTPlan:
             pre = mod_front_tape(bld, mod_jobs, self.mod, mod_rows, D)
             pre.extend(self.tape)
             self.tape = pre
+
+
+class DiTGradPlan(_TokenGradTapes):
+    r"""Gradient plan of a :class:`DiT` for one (batch, tokens, positions, modulation rows) signature, alongside
+    ``UNetGradPlan``: the forward-keep tape (the order of :class:`DiTPlan`, nothing the pullback reads released) and the
+    backward tape (``out_proj`` data gradient, the blocks in reverse, ``in_proj`` data gradient; the positional table is a
+    constant).  Plain ``Tape.run``, no graph capture; ``saved_bytes`` reports the pool."""
+
+    def __init__(self, net: "DiT", B: int, L: int, pos: Tensor, mod_rows: int, device) -> None:
+        D, C_ = net.mod_features, net.hid_channels
+        cin, cout = net.in_proj.in_features, net.out_proj.out_features
+        super().__init__(device, B, L, cin, mod_rows, D, net._param_versions())
+        bld = self.bld
+        tokens = self.token_input(cin)
+        enc = host_sine_encoding(pos.to(torch.float32).cpu(), C_, omega=1e2).flatten(-2)  # (L, P*C), as DiTPlan
+        pb = Builder(device)
+        enc_act = Act(enc.to(device).contiguous().reshape(-1), 1, L, 1, enc.shape[1], enc.shape[1], True)
+        ptab = pb.conv(enc_act, pb.pack_conv(net.pos_embedding[2].weight, None), C_)
+        pb.finish()
+        pb.tape.run()
+        ptab.pinned = True
+        bld.tape.keep.extend([pb, enc_act, ptab])
+
+        x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=_bcast(ptab))
+        mod_jobs: list[tuple] = []
+        recs = []
+        for blk in net.blocks:
+            x, rec = blk._emit_keep(bld, x, pos, None, D, mod_rows, mod_jobs)
+            recs.append((blk, rec))
+        self.set_output(bld.conv(x, bld.pack_conv(net.out_proj.weight, net.out_proj.bias), cout))
+        bld.free(x)  # (the last block's output: no pullback reads it)
+        self.end_forward(mod_jobs)
+
+        cache: dict = {}
+        wo, wi = LinearView(net.out_proj.weight), LinearView(net.in_proj.weight)
+        bld.tape.keep.extend([wo, wi])
+        g = bld.conv_dgrad(self.cotangent(cout), wo, cache=cache)
+        for blk, rec in reversed(recs):
+            g = blk._emit_bwd(bld, g, rec, cache)
+        dx = bld.conv_dgrad(g, wi, cache=cache)
+        bld.free(g)
+        self.set_dx(dx)
 
 
 class _Bcast:
@@ -437,6 +678,29 @@ class DiT(nn.Module):
         o = plan.out_tokens
         return o.buf.view(B, L, o.cs)[..., : o.C].to(out_dtype, copy=True)
 
+    # -- input gradient --------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, mod: Tensor | None = None, pos: Tensor | None = None, cond: Tensor | None = None):
+        r"""``(out, pullback)``: ``out = self(x, mod, pos)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``): the input
+        gradient that ``azula.guidance`` takes from ``torch.autograd``, on HIP tapes (:class:`DiTGradPlan`).  ``mod`` and the
+        positions are constants of the pullback; it may be called any number of times until the next ``vjp`` with the same
+        signature.  Scope: fp32 parameters and tensors, no ``cond_channels`` / ``cond``, head sizes up to 128; anything else
+        raises ``NotImplementedError`` (the forward is not affected)."""
+        if self.cond_channels or cond is not None:
+            raise NotImplementedError("DiT.vjp: cond_channels / cond are not supported")
+        _vjp_scope(self, x, "DiT")
+        assert x.ndim == 3, "DiT.vjp expects (B, L, C) tokens"
+        B, L, _ = x.shape
+        rows = self._mod_rows(mod, B)
+        if pos is None:
+            pos_h, pkey = torch.arange(L, dtype=torch.float32)[:, None], None
+        else:
+            pos_h = pos.detach().to("cpu", torch.float32).reshape(L, -1)
+            pkey = pos_h.numpy().tobytes()
+        plan = self._get_plan(("vjp", B, L, rows, pkey, str(x.device)), lambda: DiTGradPlan(self, B, L, pos_h, rows, x.device))
+        return plan.run(x, mod)
+
 
 def _patchify_nd(x: Tensor, patch: Sequence[int]) -> Tensor:
     r"""'B Z (A a) (B b) ... -> B A B ... (Z a b ...)'."""
@@ -495,6 +759,11 @@ class ViT(DiT):
         self.patch_size, self.unpatch_size = patch_size[0], unpatch_size[0]
         self.image_in, self.image_out, self.image_cond = in_channels, out_channels, cond_channels
         self.spatial = spatial
+
+    # The token network's pullback is DiT.vjp; a ViT also needs the patchify / unpatchify pullbacks around it.  That follow-up
+    # flips tests/test_guidance_vjp_host.py::test_backbone_error_names_the_backbone and
+    # tests/test_gpu_tds.py::test_vit_backbone_is_an_error; until then a ViT has no input-gradient path.
+    vjp = None
 
     def _vit_plan(self, B: int, H: int, W: int, rows: int, device) -> DiTPlan:
         p = self.patch_size

@@ -363,6 +363,15 @@ int az_silu_bwd_f32(float* y, const float* g, const float* p, int64_t n, az_stre
  * to the cotangent; y may alias x.                                                                                            */
 int az_channel_scale_f32(float* y, const float* x, const float* s, int64_t s_bstride, int64_t B, int64_t HW, int64_t C, int64_t cs,
                          az_stream_t stream);
+/* FFN activations of the DiT block (azula/nn/dit.py:74-85, azula/nn/layers.py:71-110) as passes of their own -- the forward-keep
+ * tape keeps the PRE-activation p -- and their pullbacks.  kind 1: silu, 2: relu, 3: relu(p)^2 (derivative 0 at p <= 0).
+ * n % 4 == 0; y may alias x / g.  8 B / element forward, 12 B / element backward: HBM-bound.                                  */
+int az_act_f32(float* y, const float* x, int64_t n, int32_t kind, az_stream_t stream);
+int az_act_bwd_f32(float* y, const float* g, const float* p, int64_t n, int32_t kind, az_stream_t stream);
+/* Pullback of az_swiglu_f32 (y[r, c] = x[r, 2c] * silu(x[r, 2c+1]), azula/nn/layers.py:107-110) on the kept pre-activation x:
+ * dx[r, 2c] = g[r, c] silu(x[r, 2c+1]), dx[r, 2c+1] = g[r, c] x[r, 2c] silu'(x[r, 2c+1]); dx has x's row stride xs (lanes past
+ * 2 cout written as zero), g the row stride gs.  xs % 4 == 0.  16 B per input pair: HBM-bound.                             */
+int az_swiglu_bwd_f32(float* dx, const float* g, const float* x, int64_t rows, int64_t cout, int64_t xs, int64_t gs, az_stream_t stream);
 /* The cotangent g (B, h, w, cs) of a convolution with stride (sh, sw) on the zero-filled (B, H, W, cs) grid of its input:
  * G[b, i sh, j sw, :] = g[b, i, j, :], zero elsewhere ((h - 1) sh <= H - 1, (w - 1) sw <= W - 1).  A stride-1 convolution of G with
  * the transposed, flipped weight is the data gradient of the strided convolution (azula/nn/unet.py:159-186).                 */
@@ -732,6 +741,64 @@ int az_attention_x3_f32(const AzAttnArgs* args, az_stream_t stream);
 int az_attention_f16x2_f32(const AzAttnArgs* args, az_stream_t stream);
 int az_attention_bf16_f32(const AzAttnArgs* args, az_stream_t stream);
 int az_attention_f16_f32(const AzAttnArgs* args, az_stream_t stream);
+
+/* ------------------------------------------------------------------ attention input gradient (csrc/attention_bwd.hip)
+ * The pullback torch.autograd records behind azula/nn/attention.py:89-108,112-156 (per-head q / k RMSNorm, RoPE,
+ * scaled_dot_product_attention), in three entries.  All fp32; all strides multiples of 4 floats, pointers 16-byte aligned;
+ * head_dim in {16, 32, 64, 128} (else AZ_E_UNSUPPORTED; other sizes run zero-padded to the next of these, norm_dim = the real size).
+ *
+ * az_qk_prep_f32 (forward-keep side): q^ = rope(rms_norm(q)), k^ = rope(rms_norm(k)) out of place, from the fused q | k | v token
+ * tensor (element (b, t, h, c) at b * in_bstride + t * in_tstride + h * in_hstride + c) into a second buffer (out_* strides).
+ * rms_norm averages over norm_dim channels (0 = head_dim) with eps; qk_rmsnorm = 0: no norm.  rope_cos / rope_sin: the
+ * (tokens, heads, head_dim / 2) tables of AzAttnArgs; NULL = no rotation.  The forward attention entries then run on (q^, k^, v)
+ * with qk_rmsnorm = 0 and no tables.  One row per D / 4 lanes; 8 B / element: HBM-bound.                                    */
+int az_qk_prep_f32(float* q_hat, float* k_hat, const float* q, const float* k, int64_t batch, int64_t tokens, int32_t heads,
+                   int32_t head_dim, int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride,
+                   int64_t out_tstride, int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
+                   const float* rope_sin, az_stream_t stream);
+/* Its pullback: the rotation's transpose (pairs (2i, 2i+1) turned by -theta) on dq^ / dk^ (g_* strides), then the RMS-norm
+ * pullback per head row, dx = r (g - xh mean(g xh)), r = rsqrt(mean(x^2) + eps) recomputed from the kept raw q / k (in_* strides),
+ * means over norm_dim; writes the q and k thirds of the dqkv token tensor (out_* strides).  12 B / element: HBM-bound.   */
+int az_qk_prep_bwd_f32(float* dq, float* dk, const float* dq_hat, const float* dk_hat, const float* q, const float* k, int64_t batch,
+                       int64_t tokens, int32_t heads, int32_t head_dim, int64_t g_bstride, int64_t g_tstride, int64_t g_hstride,
+                       int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride, int64_t out_tstride,
+                       int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
+                       const float* rope_sin, az_stream_t stream);
+/* az_attention_bwd_f32: with P = softmax(scale q^ k^T + mask), out = P v and dout the cotangent of out,
+ *   Delta_t = sum_c dout_tc out_tc,  dv = P^T dout,  dP = dout v^T,  dS = P o (dP - Delta),  dq^ = scale dS k^,  dk^ = scale dS^T q^.
+ * Three launches: row statistics (the log-sum-exp is recomputed by online softmax -- the forward entries do not export it -- and
+ * Delta) into `workspace` (2 * batch * heads * tokens floats), then dk^ / dv (a wave owns 32 keys and walks the queries), then dq^
+ * (a wave owns 32 queries and walks the keys).  Eight contractions (8 * 2 * tokens^2 * head_dim FLOP per (batch, head) against the
+ * forward's 2 * 2 * ...), on v_mfma_f32_32x32x2_f32 with fp32 accumulation; exp via exp2 in fp32; P is never stored.
+ * Expected to be matrix-pipe bound (not measured).  Deterministic: no atomics, every element summed by one wave in a fixed order and stored once.  No tensor
+ * takes a half-precision form (a cotangent has no range).  `mask` as in AzAttnArgs: masked pairs contribute exactly zero, tiles
+ * without a live pair are skipped; a query without a live key is outside the contract (the forward is NaN there).  The outputs
+ * must not overlap the inputs.                                                                                             */
+typedef struct AzAttnBwdArgs {
+  const float* q; /* q^ */
+  const float* k; /* k^ */
+  const float* v;
+  const float* out;
+  const float* dout;
+  float* dq;
+  float* dk;
+  float* dv;
+  float* workspace;
+  const uint8_t* mask;
+  int64_t mask_bstride, mask_hstride;
+  int32_t batch, heads, tokens, head_dim;
+  int64_t q_bstride, q_tstride, q_hstride;
+  int64_t k_bstride, k_tstride, k_hstride;
+  int64_t v_bstride, v_tstride, v_hstride;
+  int64_t o_bstride, o_tstride, o_hstride;
+  int64_t do_bstride, do_tstride, do_hstride;
+  int64_t dq_bstride, dq_tstride, dq_hstride;
+  int64_t dk_bstride, dk_tstride, dk_hstride;
+  int64_t dv_bstride, dv_tstride, dv_hstride;
+  float scale;
+  int32_t reserved;
+} AzAttnBwdArgs;
+int az_attention_bwd_f32(const AzAttnBwdArgs* args, az_stream_t stream);
 
 /* y[r, c] = x[r, 2c] * silu(x[r, 2c+1]), c < cout (SwiGLU, azula/nn/layers.py:89-110); xs / ys = row strides. */
 int az_swiglu_f32(float* y, const float* x, int64_t rows, int64_t cout, int64_t xs, int64_t ys, az_stream_t stream);
