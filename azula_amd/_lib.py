@@ -431,6 +431,13 @@ PROTOTYPES: dict[str, list] = {
     "az_swiglu_bwd_f32": [vp, vp, vp, i64, i64, i64, i64, c_stream],
     "az_zero_stuff_f32": [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, c_stream],
     "az_upsample_nearest_bwd_f32": [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, c_stream],
+    "az_norm_affine_bwd_stats_f32": [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i64, i64, i64, i64, i64, i32, i32, i32, i32, f32,
+                                     c_stream],
+    "az_norm_affine_bwd_apply_f32": [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, i64, i64, i64, i64, i64,
+                                     i32, i32, i32, f32, c_stream],
+    "az_avgpool_bwd_f32": [vp, vp, vp, i64, i64, i64, i64, i32, c_stream],
+    "az_adm_precond_bwd_out_f32": [vp, vp, vp, vp, i32, i64, i64, i64, i64, f32, f32, c_stream],
+    "az_adm_precond_bwd_in_f32": [vp, vp, vp, vp, vp, vp, i32, i64, i64, f32, f32, c_stream],
     "az_linear_small_f32": [vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, i32, c_stream],
     "az_gather_rows_f32": [vp, vp, vp, i64, i64, i64, c_stream],
     "az_gather_step_row_f32": [vp, vp, vp, i32, i64, i64, c_stream],

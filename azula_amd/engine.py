@@ -751,7 +751,7 @@ class Builder:
     # Every tensor below is a cotangent: it has no natural range, so every gradient Act is ``bounded=False`` and the
     # fixed-scale f16x2 kernels never see one (choose_conv gives them the measured-scale f16x2 form or bf16x3).
     def conv_dgrad(self, g: Act, conv, *, cin_lo: int = 0, cin_hi: int | None = None, res: Act | None = None,
-                   dst_nchw: torch.Tensor | None = None, cache: dict | None = None) -> Act | None:
+                   dst_nchw: torch.Tensor | None = None, cache: dict | None = None, winograd=None) -> Act | None:
         r"""Data gradient of a stride-1 'same' convolution ``conv`` (a module holding ``weight`` of shape (cout, cin, k...)): the
         forward convolution kernels over the cotangent ``g`` with the weight transposed (cin <-> cout) and flipped by 180 degrees,
         for the input channels [cin_lo, cin_hi) (one source of a concatenation); ``res`` is added in the epilogue (a tensor
@@ -767,7 +767,7 @@ class Builder:
             if cache is not None:
                 cache[key] = packed
         assert g.C == w.shape[0], "the cotangent has the convolution's output channels"
-        return self.conv(g, packed, cin_hi - cin_lo, res=res, dst_nchw=dst_nchw)
+        return self.conv(g, packed, cin_hi - cin_lo, res=res, dst_nchw=dst_nchw, winograd=winograd)
 
     def channel_scale(self, x: Act, s: torch.Tensor, s_off: int, bstride: int, out: Act | None = None) -> Act:
         r"""y = x * s[b, c] per (sample, channel): the gate of ``out = x + c * y`` on the way back."""
@@ -857,11 +857,13 @@ class Builder:
         return m8, (m8.stride(0) if m.shape[0] > 1 else 0), (m8.stride(1) if m.shape[1] > 1 else 0)
 
     def attention_keep(self, qkv: Act, heads: int, qk_rmsnorm: bool, scale: float, eps: float = 1e-5, rope: tuple | None = None,
-                       mask: torch.Tensor | None = None, norm_dim: int = 0) -> tuple[Act, dict]:
+                       mask: torch.Tensor | None = None, norm_dim: int = 0, order: str = "3HC", skip_prep: bool = False) -> tuple[Act, dict]:
         r"""The forward of :meth:`attention` ('(n H C)' order, fp32) with what :meth:`attention_bwd` reads kept: q^ | k^ =
         rope(rms_norm(q | k)) go out of place into a buffer of their own (``az_qk_prep_f32``), then the forward attention entry
         :func:`choose_attention` picks runs on (q^, k^, v) with no norm and no tables.  Returns (out, record); ``qkv``, q^ | k^
-        and ``out`` must stay alive for the pullback (the caller does not free them)."""
+        and ``out`` must stay alive for the pullback (the caller does not free them).  ``order``: the token layout of ``qkv`` as in
+        :meth:`attention` ("3HC" / "nHC", or "H3C": guided-diffusion's legacy order).  ``skip_prep``: without RMS norm and RoPE
+        q^ = q and k^ = k, so the copy is skipped and the kernels read q and k where they lie (they take any strides)."""
         from ._lib import AzAttnArgs
 
         Cq = qkv.C // 3
@@ -869,29 +871,45 @@ class Builder:
         assert qkv.cs == qkv.C and dim * heads == Cq and not qkv.half and self.half is None
         assert dim in ATTN_GRAD_HEAD_DIMS, dim
         B, L = qkv.B, qkv.H * qkv.W
+        if order in ("nHC", "3HC"):
+            offs, hs = (0, Cq, 2 * Cq), dim
+        elif order == "H3C":
+            offs, hs = (0, dim, 2 * dim), 3 * dim
+        else:
+            raise ValueError(order)
         cos, sin = rope if rope is not None else (None, None)
-        qk = self.new_act(B, qkv.H, qkv.W, 2 * Cq, pinned=True)
-        self.tape.add("az_qk_prep_f32", qk.ptr, qk.ptr + 4 * Cq, qkv.ptr, qkv.ptr + 4 * Cq, B, L, heads, dim, L * qkv.cs, qkv.cs, dim,
-                      L * qk.cs, qk.cs, dim, int(qk_rmsnorm), norm_dim, eps, cos.data_ptr() if cos is not None else None,
-                      sin.data_ptr() if sin is not None else None, keep=[qkv.buf, cos, sin])
-        self.wrote(qk, bounded=False)
+        prep = not (skip_prep and not qk_rmsnorm and rope is None)
+        qk = None
+        if prep:
+            qk = self.new_act(B, qkv.H, qkv.W, 2 * Cq, pinned=True)
+            self.tape.add("az_qk_prep_f32", qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0], qkv.ptr + 4 * offs[1], B, L, heads, dim,
+                          L * qkv.cs, qkv.cs, hs, L * qk.cs, qk.cs, dim, int(qk_rmsnorm), norm_dim, eps,
+                          cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None, keep=[qkv.buf, cos, sin])
+            self.wrote(qk, bounded=False)
         out = self.new_act(B, qkv.H, qkv.W, Cq)
         a = AzAttnArgs()
-        a.q, a.k, a.v, a.out = qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 8 * Cq, out.ptr
+        a.v, a.out = qkv.ptr + 4 * offs[2], out.ptr
         a.batch, a.heads, a.tokens, a.head_dim = B, heads, L, dim
-        a.q_bstride, a.q_tstride, a.q_hstride = L * qk.cs, qk.cs, dim
-        a.k_bstride, a.k_tstride, a.k_hstride = L * qk.cs, qk.cs, dim
-        a.v_bstride, a.v_tstride, a.v_hstride = L * qkv.cs, qkv.cs, dim
+        if prep:
+            a.q, a.k = qk.ptr, qk.ptr + 4 * Cq
+            a.q_bstride, a.q_tstride, a.q_hstride = L * qk.cs, qk.cs, dim
+            a.k_bstride, a.k_tstride, a.k_hstride = L * qk.cs, qk.cs, dim
+        else:
+            a.q, a.k = qkv.ptr + 4 * offs[0], qkv.ptr + 4 * offs[1]
+            a.q_bstride, a.q_tstride, a.q_hstride = L * qkv.cs, qkv.cs, hs
+            a.k_bstride, a.k_tstride, a.k_hstride = L * qkv.cs, qkv.cs, hs
+        a.v_bstride, a.v_tstride, a.v_hstride = L * qkv.cs, qkv.cs, hs
         a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
         a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, 0, eps, 0
         rec = dict(qkv=qkv, qk=qk, out=out, heads=heads, dim=dim, scale=scale, eps=eps, rms=bool(qk_rmsnorm), norm_dim=norm_dim,
-                   rope=rope, mask=None)
+                   rope=rope, mask=None, offs=offs, hs=hs)
         if mask is not None:
             m8, mb, mh = rec["mask"] = self._attn_mask(mask, B, heads, L)
             a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
         kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, None) if qk_rmsnorm else (math.inf, math.inf)
         a._flops = 4 * B * heads * L * L * dim
-        self.tape.add(choose_attention(dim, kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX, None), C.byref(a), keep=[a, qk.buf])
+        self.tape.add(choose_attention(dim, kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX, None), C.byref(a),
+                      keep=[a, qk.buf if prep else qkv.buf])
         return self.wrote(out, bounded=False), rec
 
     def attention_bwd(self, g: Act, rec: dict) -> Act:
@@ -901,19 +919,23 @@ class Builder:
 
         qkv, qk, out, heads, dim = rec["qkv"], rec["qk"], rec["out"], rec["heads"], rec["dim"]
         Cq = heads * dim
+        offs, hs = rec.get("offs", (0, Cq, 2 * Cq)), rec.get("hs", dim)
         B, L = qkv.B, qkv.H * qkv.W
         assert (g.B, g.H, g.W, g.C) == (out.B, out.H, out.W, out.C)
-        dqk = self.new_act(B, qkv.H, qkv.W, 2 * Cq)
         dqkv = self.new_act(B, qkv.H, qkv.W, 3 * Cq)
+        if qk is None:  # (attention_keep(skip_prep=True): q^ = q, k^ = k -- all three cotangents go straight into their places)
+            return self._attention_bwd_in_place(g, rec, dqkv)
+        dqk = self.new_act(B, qkv.H, qkv.W, 2 * Cq)
         a = AzAttnBwdArgs()
-        a.q, a.k, a.v, a.out, a.dout = qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 8 * Cq, out.ptr, g.ptr
-        a.dq, a.dk, a.dv = dqk.ptr, dqk.ptr + 4 * Cq, dqkv.ptr + 8 * Cq
+        a.q, a.k, a.v, a.out, a.dout = qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 4 * offs[2], out.ptr, g.ptr
+        a.dq, a.dk, a.dv = dqk.ptr, dqk.ptr + 4 * Cq, dqkv.ptr + 4 * offs[2]
         a.workspace = self.empty(2 * B * heads * L).data_ptr()
         a.batch, a.heads, a.tokens, a.head_dim, a.scale = B, heads, L, dim, rec["scale"]
-        for n, t in (("q", qk), ("k", qk), ("v", qkv), ("o", out), ("do", g), ("dq", dqk), ("dk", dqk), ("dv", dqkv)):
+        for n, t, h in (("q", qk, dim), ("k", qk, dim), ("v", qkv, hs), ("o", out, dim), ("do", g, dim), ("dq", dqk, dim), ("dk", dqk, dim),
+                        ("dv", dqkv, hs)):
             setattr(a, n + "_bstride", L * t.cs)
             setattr(a, n + "_tstride", t.cs)
-            setattr(a, n + "_hstride", dim)
+            setattr(a, n + "_hstride", h)
         if rec["mask"] is not None:
             m8, mb, mh = rec["mask"]
             a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
@@ -921,12 +943,118 @@ class Builder:
         self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qk.buf, qkv.buf, out.buf, rec["mask"]])
         self.wrote(dqk, bounded=False)
         cos, sin = rec["rope"] if rec["rope"] is not None else (None, None)
-        self.tape.add("az_qk_prep_bwd_f32", dqkv.ptr, dqkv.ptr + 4 * Cq, dqk.ptr, dqk.ptr + 4 * Cq, qkv.ptr, qkv.ptr + 4 * Cq, B, L, heads,
-                      dim, L * dqk.cs, dqk.cs, dim, L * qkv.cs, qkv.cs, dim, L * dqkv.cs, dqkv.cs, dim, int(rec["rms"]), rec["norm_dim"],
+        self.tape.add("az_qk_prep_bwd_f32", dqkv.ptr + 4 * offs[0], dqkv.ptr + 4 * offs[1], dqk.ptr, dqk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0],
+                      qkv.ptr + 4 * offs[1], B, L, heads,
+                      dim, L * dqk.cs, dqk.cs, dim, L * qkv.cs, qkv.cs, hs, L * dqkv.cs, dqkv.cs, hs, int(rec["rms"]), rec["norm_dim"],
                       rec["eps"], cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None,
                       keep=[cos, sin])
         self.free(dqk)
         return self.wrote(dqkv, bounded=False)
+
+    def _attention_bwd_in_place(self, g: Act, rec: dict, dqkv: Act) -> Act:
+        from ._lib import AzAttnBwdArgs
+
+        qkv, out, heads, dim, offs, hs = rec["qkv"], rec["out"], rec["heads"], rec["dim"], rec["offs"], rec["hs"]
+        B, L = qkv.B, qkv.H * qkv.W
+        a = AzAttnBwdArgs()
+        a.q, a.k, a.v = (qkv.ptr + 4 * o for o in offs)
+        a.dq, a.dk, a.dv = (dqkv.ptr + 4 * o for o in offs)
+        a.out, a.dout = out.ptr, g.ptr
+        a.workspace = self.empty(2 * B * heads * L).data_ptr()
+        a.batch, a.heads, a.tokens, a.head_dim, a.scale = B, heads, L, dim, rec["scale"]
+        for n, t, h in (("q", qkv, hs), ("k", qkv, hs), ("v", qkv, hs), ("o", out, dim), ("do", g, dim), ("dq", dqkv, hs), ("dk", dqkv, hs),
+                        ("dv", dqkv, hs)):
+            setattr(a, n + "_bstride", L * t.cs)
+            setattr(a, n + "_tstride", t.cs)
+            setattr(a, n + "_hstride", h)
+        if rec["mask"] is not None:
+            m8, mb, mh = rec["mask"]
+            a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
+        a._flops = 16 * B * heads * L * L * dim
+        self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qkv.buf, out.buf, rec["mask"]])
+        return self.wrote(dqkv, bounded=False)
+
+    # -- input gradient of the ADM norm pass (csrc/backward_adm.hip) ------------------------------------------------------
+    def group_norm_keep(self, x: Act, groups: int, *, weight=None, bias=None, scale=None, shift=None, scale_off=0, shift_off=0,
+                        bstride=0, act=0, pool=0, eps=1e-5, x1: Act | None = None) -> tuple[Act, dict]:
+        r"""The forward of :meth:`group_norm` (``y = pool(act((GN(x | x1) w + b) (1 + scale) + shift))``, the sources read in
+        place) with what :meth:`group_norm_keep_bwd` reads kept: the statistics pass always runs over ``x | x1`` and its records,
+        the ``S | T`` tables, ``x`` and ``x1`` stay alive.  No pre-activation is kept: the pullback recomputes ``act'`` from x."""
+        assert not x.half and self.half is None
+        B, HW = x.B, x.H * x.W
+        x1p, c0s, C_, cs = None, 0, x.C, x.cs
+        if x1 is not None:
+            assert x.C == x.cs and x1.C == x1.cs and (x1.B, x1.H, x1.W) == (x.B, x.H, x.W)
+            x1p, c0s, C_, cs = x1.ptr, x.cs, x.C + x1.C, x.cs + x1.cs
+        ST = self.empty(2 * B * cs)
+        S, T = ST[: B * cs], ST[B * cs :]
+        nchunks = int(min(512, max(1, (HW * cs * 4) // 65536)))
+        partials = self.empty(B * nchunks * groups * 4)
+        self.tape.add("az_groupnorm_stats_f32", partials.data_ptr(), x.ptr, x1p, c0s, B, HW, C_, cs, groups, nchunks)
+        f = AzNormFinalizeArgs()
+        f.partials, f.S, f.T = partials.data_ptr(), S.data_ptr(), T.data_ptr()
+        f.weight = weight.data_ptr() if weight is not None else None
+        f.bias = bias.data_ptr() if bias is not None else None
+        f.scale = scale.data_ptr() + 4 * scale_off if scale is not None else None
+        f.shift = shift.data_ptr() + 4 * shift_off if shift is not None else None
+        f.scale_bstride = bstride
+        f.B, f.C, f.cs, f.groups, f.nchunks, f.eps = B, C_, cs, groups, nchunks, eps
+        self.tape.add("az_groupnorm_finalize_f32", C.byref(f), keep=[f, weight, bias, scale, shift])
+        y = self.new_act(B, x.H // 2 if pool == 1 else x.H, x.W // 2 if pool else x.W, C_)
+        assert y.cs == cs
+        self.tape.add("az_affine_act_f32", y.ptr, x.ptr, x1p, c0s, S.data_ptr(), T.data_ptr(), B, x.H, x.W, cs, act, pool)
+        rec = dict(x=x, x1=x1, c0s=c0s, C=C_, cs=cs, ST=ST, partials=partials, nchunks=nchunks, groups=groups, eps=eps, weight=weight,
+                   scale=scale, scale_off=scale_off, bstride=bstride, act=act, pool=pool)
+        return self.wrote(y, bounded=True), rec
+
+    def group_norm_keep_bwd(self, g: Act, rec: dict, *, res0: Act | None = None, res1: Act | None = None) -> tuple[Act, Act | None]:
+        r"""Cotangent ``g`` of :meth:`group_norm_keep`'s output (on the pooled grid) -> the cotangents of ``x`` and ``x1``, plus
+        ``res0`` / ``res1`` (a tensor consumed twice: its cotangents add): ``az_norm_affine_bwd_{stats,apply}_f32``."""
+        x, x1, cs, groups = rec["x"], rec["x1"], rec["cs"], rec["groups"]
+        B, HW = x.B, x.H * x.W
+        assert g.cs == cs and g.B == B
+        nchunks = int(min(256, max(1, HW // 32)))
+        bpart = self.empty(B * nchunks * groups * 4)
+        ST, fp = rec["ST"], rec["partials"]
+        S, T = ST.data_ptr(), ST.data_ptr() + 4 * B * cs
+        w, sc = rec["weight"], rec["scale"]
+        wp = w.data_ptr() if w is not None else None
+        sp = sc.data_ptr() + 4 * rec["scale_off"] if sc is not None else None
+        x1p = x1.ptr if x1 is not None else None
+        self.tape.add("az_norm_affine_bwd_stats_f32", bpart.data_ptr(), x.ptr, x1p, rec["c0s"], g.ptr, S, T, wp, sp, rec["bstride"],
+                      fp.data_ptr(), rec["nchunks"], B, x.H, x.W, rec["C"], cs, groups, nchunks, rec["act"], rec["pool"], rec["eps"],
+                      keep=[ST, fp, w, sc, x.buf, x1.buf if x1 is not None else None])
+        dx0 = self.new_act(B, x.H, x.W, x.C)
+        dx1 = self.new_act(B, x.H, x.W, x1.C) if x1 is not None else None
+        self.tape.add("az_norm_affine_bwd_apply_f32", dx0.ptr, dx1.ptr if dx1 is not None else None,
+                      res0.ptr if res0 is not None else None, res1.ptr if res1 is not None else None, x.ptr, x1p, rec["c0s"], g.ptr, S, T,
+                      wp, sp, rec["bstride"], fp.data_ptr(), rec["nchunks"], bpart.data_ptr(), nchunks, B, x.H, x.W, rec["C"], cs, groups,
+                      rec["act"], rec["pool"], rec["eps"])
+        self.wrote(dx0, bounded=False)
+        if dx1 is not None:
+            self.wrote(dx1, bounded=False)
+        return dx0, dx1
+
+    def add(self, a: Act, b: Act) -> Act:
+        r"""a + b (two cotangents of one tensor) as a tensor of its own."""
+        assert (a.B, a.H, a.W, a.cs) == (b.B, b.H, b.W, b.cs)
+        y = self.new_act(a.B, a.H, a.W, a.C)
+        one = self.const(torch.ones(1))
+        self.tape.add("az_axpby_f32", y.ptr, one.data_ptr(), a.ptr, one.data_ptr(), b.ptr, 1, a.B * a.H * a.W * a.cs, 0, keep=[one])
+        return self.wrote(y, bounded=False)
+
+    def avgpool(self, x: Act, pool: int) -> Act:
+        r"""The pooling-only pass of ADMPlan (``az_affine_act_f32`` with S = 1, T = 0)."""
+        B = x.B
+        y = self.new_act(B, x.H // 2 if pool == 1 else x.H, x.W // 2, x.C)
+        ones, zeros = self.const(torch.ones(B * x.cs)), self.const(torch.zeros(B * x.cs))
+        return self._affine_act(y, x, None, 0, ones.data_ptr(), zeros.data_ptr(), B, x.H, x.W, x.cs, 0, pool, bounded=False)
+
+    def avgpool_bwd(self, g: Act, pool: int, H: int, W: int, res: Act | None = None) -> Act:
+        r"""Pullback of :meth:`avgpool` onto the (H, W) grid, plus ``res``."""
+        y = self.new_act(g.B, H, W, g.C)
+        self.tape.add("az_avgpool_bwd_f32", y.ptr, g.ptr, res.ptr if res is not None else None, g.B, H, W, g.cs, pool)
+        return self.wrote(y, bounded=False)
 
     def finish(self) -> None:
         r"""Allocates the shared split-K workspace and patches it into the recorded convs."""

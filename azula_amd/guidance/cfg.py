@@ -60,6 +60,13 @@ class CFGDenoiser(Denoiser):
         return DiracPosterior(mean=mean)
 
     # -- fused sampling ---------------------------------------------------------------------------
+    def _az_vjp(self, x_t: Tensor, t: Tensor, **kwargs):
+        r"""Out of scope: the guided mean needs the pullbacks of two evaluations of the same backbone, and a gradient plan holds
+        the saved tensors of one forward per signature."""
+        raise NotImplementedError(
+            "CFGDenoiser has no input-gradient path: classifier-free guidance (CFG) needs two live gradient plans of the same "
+            "backbone per step; run the gradient-based guidance on the inner denoiser")
+
     def _az_fused(self, x: Tensor, kwargs: dict, cur_coef: Tensor):
         from ..sample import FusedDenoiser
 

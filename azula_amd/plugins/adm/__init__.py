@@ -140,6 +140,58 @@ class AblatedDenoiser(Denoiser):
             var = c_var.to(dev)
         return GaussianPosterior(mean=mean, var=var)
 
+    # -- input gradient (azula_amd internal: the guidance classes that need d mean / d x_t) ------------------------
+    @torch.no_grad()
+    @_lib.on_device
+    def _az_vjp(self, x_t: Tensor, t: Tensor, label: Tensor | None = None):
+        r"""``(mean, pullback)`` with ``pullback(v) = (d mean / d x_t)^T v = c_skip m v + c_in J_F^T [c_out m v | 0]``, ``m`` the
+        mask of the elements the clip left alone: the backbone's HIP pullback (``UNetModel.vjp``) between the two
+        preconditioning kernels ``az_adm_precond_bwd_{out,in}_f32``.  A learned log-variance does not enter the mean: its
+        channels take a zero cotangent.  ``t``: a scalar or one time per sample."""
+        bb = self.backbone
+        if not x_t.is_cuda:
+            raise NotImplementedError("AblatedDenoiser: the input-gradient path runs on device tensors only")
+        vjp = getattr(bb, "vjp", None)
+        if vjp is None:
+            raise NotImplementedError(f"AblatedDenoiser: the backbone {type(bb).__name__} has no input-gradient (vjp) path on the HIP kernels")
+        require_f32_cuda(x_t, "AblatedDenoiser")
+        from ...denoise import postcondition, precondition
+
+        dev = x_t.device
+        alpha_t, sigma_t = self.schedule(t)
+        sig = self.sigmas if self.sigmas.device == alpha_t.device else self.sigmas.to(alpha_t.device)
+        c_in, c_out, c_skip, c_time, _ = adm_coefficients(alpha_t.reshape(-1), sigma_t.reshape(-1), sig)
+        c_in, c_out, c_skip = (c.to(device=dev, dtype=torch.float32).contiguous() for c in (c_in, c_out, c_skip))
+        per = int(c_in.numel() > 1)
+        x_t = x_t.detach().contiguous()
+        B, Cc = x_t.shape[0], x_t.shape[1]
+        assert c_in.numel() in (1, B)
+        inner = x_t.numel() // (B * Cc)
+        x_in = precondition(x_t, c_in)
+        output, pull = vjp(x_in, c_time.to(dev), y=label)
+        output = output.contiguous()
+        Fc = output.shape[1]
+        lo, hi = self._clip()
+        mean = postcondition(x_t, output[:, :Cc].contiguous(), c_skip, c_out)
+        if lo > -math.inf:
+            mean = torch.clip(mean, min=lo, max=hi)
+        mean = mean.contiguous()
+
+        def pullback(v: Tensor) -> Tensor:
+            v = v.detach().to(torch.float32).contiguous()
+            assert v.shape == x_t.shape
+            with torch.cuda.device(dev):
+                gF = torch.empty_like(output)
+                _lib.call("az_adm_precond_bwd_out_f32", gF.data_ptr(), v.data_ptr(), mean.data_ptr(), c_out.data_ptr(), per, B, Cc, Fc,
+                          inner, lo, hi, _lib.stream_ptr())
+                g = pull(gF).contiguous()
+                dx = torch.empty_like(x_t)
+                _lib.call("az_adm_precond_bwd_in_f32", dx.data_ptr(), g.data_ptr(), v.data_ptr(), mean.data_ptr(), c_in.data_ptr(),
+                          c_skip.data_ptr(), per, B, Cc * inner, lo, hi, _lib.stream_ptr())
+            return dx
+
+        return mean, pullback
+
     # -- fused sampling -------------------------------------------------------------------------------
     def host_coefficients(self, alpha_t: Tensor, sigma_t: Tensor) -> dict:
         c_in, c_out, c_skip, idx, _ = adm_coefficients(alpha_t, sigma_t, self.sigmas.detach().cpu())

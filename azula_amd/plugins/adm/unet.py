@@ -31,6 +31,7 @@ from torch import Tensor
 
 from ... import _lib, engine
 from ...engine import Act, Builder, pad8
+from ...nn.unet import _GradTapes
 
 __all__ = ["UNetModel"]
 
@@ -401,6 +402,317 @@ class ADMPlan:
         self.tape = bld.tape
 
 
+class ADMGradPlan(_GradTapes):
+    r"""Gradient plan of a :class:`UNetModel` for one (batch, H, W, embedding rows) signature: the forward-keep and backward tapes
+    of :class:`azula_amd.nn.unet._GradTapes`, mirroring :class:`ADMPlan`'s walk.  A different plan from :class:`ADMPlan`, whose
+    launches it leaves untouched.  The forward-keep tape keeps, per norm pass, its input and its statistics (``Builder.
+    group_norm_keep``) -- no pre-activation, no SiLU pass of its own: the pullback recomputes ``silu'`` from the input --, per
+    attention block q | k | v and the attention output; the embedding (time, label, FiLM tables) is a constant of the pullback.
+    ``dims`` 1 and 2, fp32."""
+
+    def __init__(self, net: "UNetModel", B: int, H: int, W: int, emb_rows: int, device, frac: bool = False) -> None:
+        super().__init__(device, B, net.in_channels, net.out_channels, H, W, 0, 0, net._param_versions())
+        bld = self.bld
+        mc, E = net.model_channels, 4 * net.model_channels
+        cin = net.in_channels
+        one_d = net.dims == 1
+        assert net.dims in (1, 2) and (not one_d or H == 1)
+        up2 = (0, 1) if one_d else 1
+        down2 = (1, 2) if one_d else 2
+        pool2 = 2 if one_d else 1
+        sh, sw = (1, 2) if one_d else (2, 2)
+        wino = False if one_d else None
+        cache: dict = {}
+        self._views: list = []  # LinearView objects (Builder.conv_dgrad keys its packed weights by their identity)
+
+        def packed(conv, **kw):
+            w = conv.weight
+            if w.ndim == 3 and w.shape[-1] == 3:
+                w2 = torch.zeros(*w.shape[:2], 3, 3, dtype=w.dtype, device=w.device)
+                w2[:, :, 1, :] = w.detach()
+                w = w2
+            return bld.pack_conv(w, conv.bias, **kw)
+
+        def dgrad(g: Act, conv, **kw):
+            return bld.conv_dgrad(g, conv, cache=cache, winograd=wino, **kw)
+
+        # ---- embedding (a constant of the pullback): ADMPlan's launches
+        self.table = bld.const(timestep_embedding_table(net.table_steps, mc))
+        self.t_idx = torch.zeros(emb_rows, dtype=torch.int64, device=device)
+        self.t_frac = torch.zeros(emb_rows, dtype=torch.float32, device=device) if frac else None
+        self.labels = torch.zeros(B, dtype=torch.int64, device=device) if net.num_classes is not None else None
+        temb = bld.empty(emb_rows, mc)
+        row0 = torch.zeros(B, dtype=torch.int64, device=device)
+        bld.tape.keep.append(row0)
+        if frac:
+            assert mc % 2 == 0, "odd model_channels with fractional timesteps"
+            bld.tape.add("az_timestep_embedding_f32", temb.data_ptr(), mc, self.t_frac.data_ptr(), 1, emb_rows, mc // 2, 10000.0)
+        else:
+            bld.tape.add("az_gather_rows_f32", temb.data_ptr(), self.table.data_ptr(), self.t_idx.data_ptr(), emb_rows, mc, net.table_steps)
+        te0, te2 = net.time_embed[0], net.time_embed[2]
+        hid = bld.empty(emb_rows, E)
+        emb = bld.empty(emb_rows, E)
+        bld.linear_small(hid, E, temb, mc, bld.const(te0.weight), bld.const(te0.bias), emb_rows, E, mc, 0, 1)
+        if net.num_classes is None:
+            bld.linear_small(emb, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), emb_rows, E, E, 0, 0)
+        else:
+            tbase = bld.empty(emb_rows, E)
+            bld.linear_small(tbase, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), emb_rows, E, E, 0, 0)
+            lab = bld.empty(B, E)
+            lw = bld.const(net.label_emb.weight)
+            bld.tape.add("az_gather_rows_f32", lab.data_ptr(), lw.data_ptr(), self.labels.data_ptr(), B, E, net.num_classes)
+            ones = bld.const(torch.ones(1))
+            assert emb_rows == B
+            bld.tape.add("az_axpby_f32", emb.data_ptr(), ones.data_ptr(), tbase.data_ptr(), ones.data_ptr(), lab.data_ptr(), 1, B * E, 0)
+        film_at = len(bld.tape.ops)
+        film_jobs: list[tuple] = []
+
+        # ---- forward-keep layers: (output, record); nothing a pullback reads is handed back to the pool
+        def resblock(rb: ResBlock, x: Act, x1: Act | None):
+            oc, ocs = rb.out_channels, bld.pad(rb.out_channels)
+            gi, ci = rb.in_layers[0], rb.in_layers[2]
+            go, co = rb.out_layers[0], rb.out_layers[3]
+            lin = rb.emb_layers[1]
+            nf = 2 if rb.use_scale_shift_norm else 1
+            w = torch.zeros(nf * ocs, E, dtype=torch.float32, device=device)
+            b_ = torch.zeros(nf * ocs, dtype=torch.float32, device=device)
+            for n in range(nf):
+                w[n * ocs : n * ocs + oc] = lin.weight.detach()[n * oc : (n + 1) * oc]
+                b_[n * ocs : n * ocs + oc] = lin.bias.detach()[n * oc : (n + 1) * oc]
+            film = bld.empty(emb_rows, nf * ocs)
+            film_jobs.append((film, bld.const(w), bld.const(b_), nf * ocs))
+            fbs = nf * ocs if emb_rows > 1 else 0
+            n1, r1 = bld.group_norm_keep(x, 32, weight=bld.const(gi.weight), bias=bld.const(gi.bias), act=1,
+                                         pool=pool2 if rb.down else 0, x1=x1)
+            h = bld.conv(n1, packed(ci), oc, up0=up2 if rb.up else 0, winograd=wino)
+            bld.free(n1)
+            if rb.use_scale_shift_norm:
+                n2, r2 = bld.group_norm_keep(h, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), scale=film, shift=film,
+                                             scale_off=0, shift_off=ocs, bstride=fbs, act=1)
+            else:  # SiLU(GN(h + emb_out)): the kept tensor is the sum
+                eb = film
+                if emb_rows == 1 and B > 1:
+                    eb = bld.empty(B, ocs)
+                    bld.tape.add("az_gather_rows_f32", eb.data_ptr(), film.data_ptr(), row0.data_ptr(), B, ocs, 1)
+                he = bld.new_act(B, h.H, h.W, oc)
+                bld._affine_act(he, h, None, 0, bld.const(torch.ones(B * ocs)).data_ptr(), eb.data_ptr(), B, h.H, h.W, ocs, 0, 0,
+                                bounded=False)
+                bld.free(h)
+                n2, r2 = bld.group_norm_keep(he, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
+            if rb.down:
+                xs = bld.avgpool(x, pool2)
+                out = bld.conv(n2, packed(co), oc, res=xs, winograd=wino)
+                bld.free(xs)
+            elif rb.up:
+                out = bld.conv(n2, packed(co), oc, res=x, res_up=1, winograd=wino)
+            elif isinstance(rb.skip_connection, nn.Identity):
+                out = bld.conv(n2, packed(co), oc, res=x, winograd=wino)
+            else:
+                skip = bld.conv(x, packed(rb.skip_connection, cin0=x.C if x1 is not None else None), oc, src1=x1)
+                out = bld.conv(n2, packed(co), oc, res=skip, winograd=wino)
+                bld.free(skip)
+            bld.free(n2)
+            return out, dict(kind="res", rb=rb, r1=r1, r2=r2, x=x, x1=x1)
+
+        def attention(ab: AttentionBlock, x: Act):
+            Cc = ab.channels
+            n_, rn = bld.group_norm_keep(x, 32, weight=bld.const(ab.norm.weight), bias=bld.const(ab.norm.bias))
+            L = x.H * x.W
+            tok = n_.view(B, L, 1, Cc)
+            ch = Cc // ab.num_heads
+            chp = engine.attn_grad_padded_dim(ch)
+            order = "3HC" if ab.new_order else "H3C"
+            wq, bq, wp = ab.qkv.weight, ab.qkv.bias, ab.proj_out.weight
+            if chp != ch:  # zero-padded heads: the cotangents of the pad lanes meet zero weight columns in the data gradient
+                wq, bq = engine.pad_qkv_heads(wq, bq, ab.num_heads, ch, chp, order)
+                wp = engine.pad_proj_heads(wp, ab.num_heads, ch, chp)
+            vq, vp_ = engine.LinearView(wq), engine.LinearView(wp)
+            self._views += [vq, vp_]
+            qkv = bld.conv(tok, bld.pack_conv(wq, bq), 3 * ab.num_heads * chp)
+            bld.free(n_)
+            att, ra = bld.attention_keep(qkv, ab.num_heads, False, 1.0 / math.sqrt(ch), norm_dim=ch, order=order, skip_prep=True)
+            o = bld.conv(att, bld.pack_conv(wp, ab.proj_out.bias), Cc, res=x.view(B, L, 1, Cc))
+            return o.view(B, x.H, x.W, pinned=False), dict(kind="attn", rn=rn, ra=ra, vq=vq, vp=vp_, x=x)
+
+        def run(block, h: Act, h1: Act | None):
+            recs = []
+            for layer in block:
+                if isinstance(layer, (nn.Conv1d, nn.Conv2d)):
+                    nh, rec = bld.conv(h, packed(layer), layer.out_channels, winograd=wino), dict(kind="stem", conv=layer)
+                elif isinstance(layer, ResBlock):
+                    nh, rec = resblock(layer, h, h1)
+                elif isinstance(layer, Downsample):
+                    if layer.use_conv:
+                        nh = bld.conv(h, packed(layer.op), layer.out_channels, stride=down2)
+                    else:
+                        nh = bld.avgpool(h, pool2)
+                    rec = dict(kind="down", layer=layer, hw=(h.H, h.W))
+                elif isinstance(layer, Upsample):
+                    if layer.use_conv:
+                        nh = bld.conv(h, packed(layer.conv), layer.out_channels, up0=up2, winograd=wino)
+                    else:
+                        eye = torch.eye(h.C, dtype=torch.float32, device=device)
+                        nh = bld.conv(h, bld.pack_conv(eye, None), h.C, up0=up2)
+                    rec = dict(kind="up", layer=layer, hw=(h.H, h.W))
+                else:
+                    nh, rec = attention(layer, h)
+                recs.append(rec)
+                h, h1 = nh, None
+            return h, recs
+
+        cur = bld.new_act(B, H, W, cin, pinned=True)
+        bld.tape.add("az_nchw_to_nhwc_f32", cur.ptr, self.x_in.data_ptr(), None, B, cin, H * W, cur.cs)
+        bld.wrote(cur, bounded=False)
+        hs: list[Act] = []
+        in_recs, out_recs = [], []
+        h = cur
+        for block in net.input_blocks:
+            h, recs = run(block, h, None)
+            hs.append(h)
+            in_recs.append(recs)
+        h, mid_recs = run(net.middle_block, h, None)
+        skips = list(hs)
+        for block in net.output_blocks:
+            h, recs = run(block, h, skips.pop())
+            out_recs.append(recs)
+        go, co = net.out[0], net.out[2]
+        n_, r_head = bld.group_norm_keep(h, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
+        bld.conv(n_, packed(co), net.out_channels, dst_nchw=self.out, winograd=wino)
+        bld.free(n_)
+        if film_jobs:
+            from ..._lib import AzLinearGroup, lib
+
+            nj = len(film_jobs)
+            groups = (AzLinearGroup * nj)()
+            for i, (film, w, b_, n_out) in enumerate(film_jobs):
+                g = groups[i]
+                g.y, g.x, g.W, g.bias = film.data_ptr(), emb.data_ptr(), w.data_ptr(), b_.data_ptr()
+                g.ldy, g.ldx, g.N, g.K = n_out, E, n_out, E
+            gdev = torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(device)
+            bld.tape.keep.append(gdev)
+            bld.tape.ops.insert(film_at, (
+                lib().az_linear_small_grouped_f32, (gdev.data_ptr(), nj, max(j[3] for j in film_jobs), emb_rows, 1, 0),
+                "az_linear_small_grouped_f32",
+            ))
+        self.end_forward([])
+
+        # ---- backward: the same graph from the output to the input.  `extra`: the cotangent a second consumer of the layer's
+        # input left (a skip connection), added where the layer's own input cotangent is written
+        def plus(a: Act, extra: Act | None) -> Act:
+            if extra is None:
+                return a
+            y = bld.add(a, extra)
+            bld.free(a)
+            return y
+
+        def resblock_bwd(g: Act, rec: dict, extra: Act | None):
+            rb, x, x1 = rec["rb"], rec["x"], rec["x1"]
+            ci, co = rb.in_layers[2], rb.out_layers[3]
+            g_n2 = dgrad(g, co)
+            g_h, _ = bld.group_norm_keep_bwd(g_n2, rec["r2"])
+            bld.free(g_n2)
+            g_n1 = dgrad(g_h, ci)  # (an `up` block: on the upsampled grid)
+            bld.free(g_h)
+            if rb.up:
+                t = bld.upsample_nearest_bwd(g_n1, sh, sw, x.H, x.W)
+                bld.free(g_n1)
+                g_n1 = t
+            res0, res1, own = None, None, True
+            if rb.down:
+                res0 = bld.avgpool_bwd(g, pool2, x.H, x.W, res=extra)
+            elif rb.up:
+                res0 = plus(bld.upsample_nearest_bwd(g, sh, sw, x.H, x.W), extra)
+            elif isinstance(rb.skip_connection, nn.Identity):
+                res0, own = (g, False) if extra is None else (bld.add(g, extra), True)
+            else:
+                sc = rb.skip_connection
+                res0 = dgrad(g, sc, cin_lo=0, cin_hi=x.C, res=extra)
+                if x1 is not None:
+                    res1 = dgrad(g, sc, cin_lo=x.C)
+            dx0, dx1 = bld.group_norm_keep_bwd(g_n1, rec["r1"], res0=res0, res1=res1)
+            bld.free(g_n1)
+            if own:
+                bld.free(res0)
+            if res1 is not None:
+                bld.free(res1)
+            return dx0, dx1
+
+        def attention_bwd(g: Act, rec: dict, extra: Act | None):
+            x = rec["x"]
+            L = x.H * x.W
+            gt = g.view(B, L, 1, g.C)
+            g_att = dgrad(gt, rec["vp"])
+            g_qkv = bld.attention_bwd(g_att, rec["ra"])
+            bld.free(g_att)
+            g_tok = dgrad(g_qkv, rec["vq"])
+            bld.free(g_qkv)
+            dx, _ = bld.group_norm_keep_bwd(g_tok.view(B, x.H, x.W), rec["rn"], res0=g)
+            bld.free(g_tok)
+            return plus(dx, extra), None
+
+        def layer_bwd(g: Act, rec: dict, extra: Act | None):
+            kind = rec["kind"]
+            if kind == "res":
+                return resblock_bwd(g, rec, extra)
+            if kind == "attn":
+                return attention_bwd(g, rec, extra)
+            hh, ww = rec.get("hw", (0, 0))
+            if kind == "down":
+                if rec["layer"].use_conv:
+                    wide = bld.zero_stuff(g, sh, sw, hh, ww)
+                    dx = dgrad(wide, rec["layer"].op, res=extra)
+                    bld.free(wide)
+                    return dx, None
+                return bld.avgpool_bwd(g, pool2, hh, ww, res=extra), None
+            assert kind == "up"
+            if rec["layer"].use_conv:
+                gu = dgrad(g, rec["layer"].conv)
+                dx = bld.upsample_nearest_bwd(gu, sh, sw, hh, ww)
+                bld.free(gu)
+            else:
+                dx = bld.upsample_nearest_bwd(g, sh, sw, hh, ww)
+            return plus(dx, extra), None
+
+        def block_bwd(g: Act, recs: list, extra: Act | None):
+            r"""-> (cotangent of the block's input, cotangent of its skip source or None)."""
+            d1 = None
+            for i in range(len(recs) - 1, -1, -1):
+                ng, d1 = layer_bwd(g, recs[i], extra if i == 0 else None)
+                if ng is not g:
+                    bld.free(g)
+                g = ng
+            return g, d1
+
+        v = bld.new_act(B, H, W, net.out_channels, pinned=True)
+        bld.tape.add("az_nchw_to_nhwc_f32", v.ptr, self.v_in.data_ptr(), None, B, net.out_channels, H * W, v.cs)
+        bld.wrote(v, bounded=False)
+        g = dgrad(v, co)
+        t, _ = bld.group_norm_keep_bwd(g, r_head)
+        bld.free(g)
+        g = t
+        g_skip: dict[int, Act] = {}  # index into hs -> the skip connection's share of that tensor's cotangent
+        for j in range(len(out_recs) - 1, -1, -1):  # (the decoder popped hs[n - 1] first: output block j read hs[n - 1 - j])
+            g, g_skip[len(hs) - 1 - j] = block_bwd(g, out_recs[j], None)
+        g, _ = block_bwd(g, mid_recs, g_skip[len(hs) - 1])
+        bld.free(g_skip[len(hs) - 1])
+        for i in range(len(in_recs) - 1, 0, -1):
+            g, _ = block_bwd(g, in_recs[i], g_skip[i - 1])
+            bld.free(g_skip[i - 1])
+        bld.conv_dgrad(g, in_recs[0][0]["conv"], dst_nchw=self.dx, cache=cache, winograd=wino)
+        bld.free(g)
+        self.end_backward()
+
+    def run_adm(self, x: Tensor, timesteps: Tensor, y: Tensor | None):
+        rows = self.t_idx.numel()
+        if self.t_frac is not None:
+            self.t_frac.copy_(timesteps.to(torch.float32).expand(rows) if timesteps.numel() == 1 else timesteps.to(torch.float32))
+        else:
+            self.t_idx.copy_(timesteps.to(torch.int64).expand(rows) if timesteps.numel() == 1 else timesteps.to(torch.int64))
+        if y is not None:
+            self.labels.copy_(y.to(torch.int64))
+        return self.run(x, None)
+
+
 class UNetModel(nn.Module):
     r"""guided-diffusion ``UNetModel`` (reference ``_src/unet.py:387-634``), gfx950-native forward.
 
@@ -496,6 +808,44 @@ class UNetModel(nn.Module):
             p = ADMPlan(self, B, H, W, emb_rows, device, x_in=x_in, coef_ptr=coef_ptr, frac=frac, D=D)
             self._plans[key] = p
         return p
+
+    # -- input gradient --------------------------------------------------------------------------------------------
+    def grad_plan(self, B, H, W, emb_rows, device, frac=False) -> ADMGradPlan:
+        key = ("vjp", B, H, W, emb_rows, str(device), frac)
+        p = self._plans.get(key)
+        if p is None or p.versions != self._param_versions():
+            p = ADMGradPlan(self, B, H, W, emb_rows, device, frac=frac)
+            self._plans[key] = p
+        return p
+
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, timesteps: Tensor, y: Tensor | None = None):
+        r"""``(out, pullback)``: ``out = self(x, timesteps, y)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``): the input
+        gradient that ``azula.guidance`` takes from ``torch.autograd``, on HIP tapes (:class:`ADMGradPlan`).  The embedding is a
+        constant of the pullback; it may be called any number of times until the next ``vjp`` with the same shapes.  Scope:
+        ``dims`` 1 and 2, fp32 parameters and device tensors; anything else raises ``NotImplementedError`` (the forward is not
+        affected)."""
+        if self.dims == 3:
+            raise NotImplementedError("UNetModel.vjp: dims = 1 and 2 only (dims = 3 volumes have no input-gradient plan)")
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            raise NotImplementedError("UNetModel.vjp: fp32 parameters and tensors only (half-precision modules have no input-gradient plan)")
+        if not x.is_cuda:
+            raise NotImplementedError("UNetModel.vjp: device tensors only (CPU tensors have no input-gradient path)")
+        assert (y is not None) == (self.num_classes is not None), "must specify y if and only if the model is class-conditional"
+        assert x.ndim == self.dims + 2, f"dims={self.dims}: expected a {self.dims + 2}-d input, got {tuple(x.shape)}"
+        one_d = self.dims == 1
+        x = x.contiguous()
+        if one_d:
+            x = x[:, :, None, :]
+        B, _, H, W = x.shape
+        timesteps = timesteps.reshape(-1)
+        frac = torch.is_floating_point(timesteps)
+        rows = B if (timesteps.numel() > 1 or self.num_classes is not None) else 1
+        out, pullback = self.grad_plan(B, H, W, rows, x.device, frac=frac).run_adm(x, timesteps, y)
+        if one_d:
+            return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
+        return out, pullback
 
     @torch.no_grad()
     @_lib.on_device

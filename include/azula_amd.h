@@ -382,6 +382,44 @@ int az_zero_stuff_f32(float* G, const float* g, int64_t B, int64_t h, int64_t w,
 int az_upsample_nearest_bwd_f32(float* dx, const float* g, int64_t B, int64_t h, int64_t w, int64_t cs, int32_t sh, int32_t sw,
                                 int64_t hn, int64_t wn, az_stream_t stream);
 
+/* ------------------------------------------------------------------ input gradient of the ADM UNet (csrc/backward_adm.hip)
+ * Pullback of the ADM norm pass y = pool(act(S[b,c] x + T[b,c])) -- az_groupnorm_finalize_f32's tables applied by
+ * az_affine_act_f32: GroupNorm, its affine gamma / beta, FiLM (1 + scale) and shift, SiLU (act = 1) and the 2x2 (pool = 1) or 1x2
+ * (pool = 2) average pool (plugins/adm/_src/unet.py:227-247) -- w.r.t. x.  With S = r_g m_c, m_c = gamma_c (1 + scale[b, c]),
+ * xh = (x - mean_g) r_g and the cotangent g of y on the POOLED grid (B, H', W', cs):
+ *     u = pool^T(g) act'(S x + T);  s1 = sum_group m u;  s2 = sum_group m u xh;  dx = r_g (m u - s1 / N - xh s2 / N) [+ res]
+ * act' is recomputed from x, S, T: only x and the forward statistics are kept.  The input is x0 (B, H, W, cs), or the channel
+ * concatenation x0 | x1 read in place as in az_groupnorm_stats_f32 (x0 of stride c0s, x1 of stride cs - c0s, C == cs; groups may
+ * straddle the boundary; any C / groups); dx0 / dx1 (and the optional residuals res0 / res1 that are added) have their source's
+ * layout.  `weight` = gamma (NULL: 1), `scale` read at scale[b * scale_bstride + c] (NULL: 0).  `fpart`: the forward records of
+ * az_groupnorm_stats_f32 over `fchunks` chunks (mean and r_g are folded from them); the stats pass writes
+ * bpart[b][chunk][group] = (s1, s2, 0, 0) over `nchunks` pixel chunks, the apply pass folds them in a fixed order.  Pad lanes
+ * [C, cs) of dx0 are written as zero.  Deterministic, no atomics.                                                            */
+int az_norm_affine_bwd_stats_f32(float* bpart, const float* x0, const float* x1, int64_t c0s, const float* g, const float* S,
+                                 const float* T, const float* weight, const float* scale, int64_t scale_bstride, const float* fpart,
+                                 int32_t fchunks, int64_t B, int64_t H, int64_t W, int64_t C, int64_t cs, int32_t groups,
+                                 int32_t nchunks, int32_t act, int32_t pool, float eps, az_stream_t stream);
+int az_norm_affine_bwd_apply_f32(float* dx0, float* dx1, const float* res0, const float* res1, const float* x0, const float* x1,
+                                 int64_t c0s, const float* g, const float* S, const float* T, const float* weight, const float* scale,
+                                 int64_t scale_bstride, const float* fpart, int32_t fchunks, const float* bpart, int32_t nchunks,
+                                 int64_t B, int64_t H, int64_t W, int64_t C, int64_t cs, int32_t groups, int32_t act, int32_t pool,
+                                 float eps, az_stream_t stream);
+/* Pullback of the pooling-only pass (AvgPool2d(2, 2): pool = 1; AvgPool1d(2) on a one-row image: pool = 2): dx (B, H, W, cs) =
+ * res + g[b, h / 2 (pool 1) or h, w / 2, :] / 4 (or / 2); g is (B, H', W', cs); res NULL: none.                                  */
+int az_avgpool_bwd_f32(float* dx, const float* g, const float* res, int64_t B, int64_t H, int64_t W, int64_t cs, int32_t pool,
+                       az_stream_t stream);
+/* Pullback of the ADM posterior mean = clip(c_skip x_t + c_out eps, lo, hi), eps = F(c_in x_t)[:, :C] (plugins/adm/__init__.py:
+ * 109-123), planar tensors: with the KEPT clipped `mean` (B, C, inner), mask = lo < mean < hi (a clipped element sits on a bound)
+ * and the cotangent v of the mean,
+ *   ..._out: gF (B, F, inner) = c_out mask v on the first C channels, ZERO on the other F - C (a learned log-variance does not
+ *            enter the mean);
+ *   ..._in : dx = c_in g + c_skip mask v, g (B, C, inner) the backbone's pullback of gF.
+ * Coefficients are device scalars, or one per sample (per_sample != 0).  lo = -inf, hi = +inf: no clipping.                      */
+int az_adm_precond_bwd_out_f32(float* gF, const float* v, const float* mean, const float* c_out, int32_t per_sample, int64_t B,
+                               int64_t C, int64_t F, int64_t inner, float lo, float hi, az_stream_t stream);
+int az_adm_precond_bwd_in_f32(float* dx, const float* g, const float* v, const float* mean, const float* c_in, const float* c_skip,
+                              int32_t per_sample, int64_t B, int64_t n, float lo, float hi, az_stream_t stream);
+
 int az_nhwc_to_nchw_f32(float* dst, const float* src, int64_t B, int64_t C, int64_t HW, int64_t cs,
                         az_stream_t stream);
 
