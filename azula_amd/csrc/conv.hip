@@ -2905,6 +2905,7 @@ static int conv2d_direct(const AzConvArgs* a, az_stream_t stream, int half) {
  * the host (U = G g G^T laid out [chunk][cout block][16][32][8], see azula_amd/engine.py).  Only
  * ksize = 3, stride = 1, pad = 1. */
 static int wino_prepare(const AzConvArgs* a, int wk, int64_t ustage_bytes, WinoP& p, int& splitk);
+static void wino_order(WinoP& p, int wk);
 
 int az_conv2d_winograd_f32(const AzConvArgs* a, az_stream_t stream) {
   WinoP p;
@@ -2945,12 +2946,122 @@ int az_conv2d_winograd_x3_f32(const AzConvArgs* a, az_stream_t stream) { return 
 /* The f16x2 form of the same kernel (include/azula_amd.h): `weight` = az_winograd_pack_filter_f16x2_f32 output, `w_scale` its scale. */
 int az_conv2d_winograd_f16x2_f32(const AzConvArgs* a, az_stream_t stream) { return winograd_x3_entry(a, stream, true); }
 
+// ---- Block shape of the x3 / f16x2 kernel (wino_x3.hip: RECT).  A block's 64 tiles are either runs of horizontally adjacent
+// tiles (64 x 1: a run of n tiles stages 4 (2 n + 2) pixel slots per step) or a rectangle of rect_w x rect_h tiles of one image
+// that stages one window of (2 rect_h + 2) (2 rect_w + 2) slots.  Per launch the shape with the fewest staged slots summed over
+// all blocks wins (masked tiles of ragged rectangles count: their slots are staged like any other); ties go to the run form.
+// Two restrictions, both a priori: a rectangle shape may not need MORE blocks than the run form (a block streams its whole
+// filter chunk and issues all its matrix instructions whatever part of its tiles is masked -- that costs more than staging can
+// save), and with GroupNorm moments in the epilogue every rectangle must be whole (a record covers 1024 values).
+constexpr int X3_NSHAPES = 5;
+constexpr int X3_SHAPES[X3_NSHAPES][2] = {{64, 1}, {32, 2}, {16, 4}, {8, 8}, {4, 16}};
+constexpr bool X3_RECT_BLOCKS = true;  // (false: the run form everywhere -- tools/ablate.py wx3_norect)
+
+static bool x3_shape_ok(int rw, int rh) {
+  for (int i = 0; i < X3_NSHAPES; ++i)
+    if (X3_SHAPES[i][0] == rw && X3_SHAPES[i][1] == rh) return true;
+  return false;
+}
+
+// staged slots of the run form, all blocks: block tb starts at tile column (64 tb) % tiles_w (tile rows follow each other
+// seamlessly across images), periodic in tb with period tiles_w / gcd(64, tiles_w), and stages 8 (64 + its segments) slots
+static int64_t x3_run_slots(int64_t ntiles, int tiles_w) {
+  const int64_t nb = (ntiles + WT - 1) / WT;
+  int g = WT, r = tiles_w;
+  while (r) { const int x = g % r; g = r; r = x; }
+  const int period = tiles_w / g;
+  int64_t total = 0;
+  for (int i = 0; i < period && i < nb; ++i) {
+    const int tw0 = (int)(((int64_t)i * WT) % tiles_w);
+    const int nseg = (WT - 1 + tw0) / tiles_w + 1;
+    total += (nb / period + (i < nb % period ? 1 : 0)) * 8 * (WT + nseg);
+  }
+  return total;
+}
+
+// whole: every rectangle must lie inside the map (GroupNorm moments).  Returns the staged slots of the chosen shape.
+static int64_t x3_choose_block(int batch, int tiles_h, int tiles_w, bool whole, int& rw, int& rh, int64_t& run_slots) {
+  const int64_t ntiles = (int64_t)batch * tiles_h * tiles_w;
+  const int64_t run_blocks = (ntiles + WT - 1) / WT;
+  run_slots = x3_run_slots(ntiles, tiles_w);
+  int64_t best = run_slots;
+  rw = WT, rh = 1;
+  if (!X3_RECT_BLOCKS) return best;
+  for (int i = 1; i < X3_NSHAPES; ++i) {
+    const int w = X3_SHAPES[i][0], h = X3_SHAPES[i][1];
+    if (whole && (tiles_w % w || tiles_h % h)) continue;
+    const int64_t blocks = (int64_t)batch * x3_rect_blocks_per_image(tiles_h, tiles_w, w, h);
+    if (blocks > run_blocks) continue;
+    const int64_t slots = blocks * (2 * w + 2) * (2 * h + 2);
+    if (slots < best) best = slots, rw = w, rh = h;
+  }
+  return best;
+}
+
+/* Host only (no device is touched): the launcher's choice of block shape for a (batch, hin, win) map -- `whole` as for a launch
+ * with gn_quads and splitk 1 -- with the staged pixel slots per K step of that choice and of the run form, summed over all blocks. */
+int az_winograd_x3_choose_block(int32_t batch, int32_t hin, int32_t win, int32_t whole, int32_t* rect_w, int32_t* rect_h,
+                                int64_t* slots, int64_t* slots_run) {
+  AZ_REQUIRE(rect_w && rect_h && slots && slots_run, AZ_E_NULL);
+  AZ_REQUIRE(batch > 0 && hin > 0 && win > 0 && (int64_t)batch * hin * win < (1ll << 31), AZ_E_SHAPE);
+  int rw, rh;
+  int64_t run;
+  *slots = x3_choose_block(batch, (hin + 1) / 2, (win + 1) / 2, whole != 0, rw, rh, run);
+  *rect_w = rw, *rect_h = rh, *slots_run = run;
+  return AZ_OK;
+}
+
+/* Host only: the staging geometry of tile block `block` of a (batch, hin, win) map cut into rect_w x rect_h rectangles (rect_h > 1),
+ * computed by the functions the kernel's prologue runs (conv_shared.h: X3RectGeom).  slot_pix: 512 x (image, row, column) of the
+ * input pixel every staged slot holds, (-1, -1, -1) for a slot that stages zeros; tile_info: 64 x (image or -1 for a masked tile,
+ * tile row, tile column, slot of the patch's first pixel: patch (r, c) = that slot + r * (2 rect_w + 2) + c).  Returns the number of
+ * slots of the block's window (<= 512), or AZ_E_*. */
+int az_winograd_x3_block_geometry(int32_t batch, int32_t hin, int32_t win, int32_t pad_mode, int32_t rect_w, int32_t rect_h,
+                                  int32_t block, int32_t* slot_pix, int32_t* tile_info) {
+  AZ_REQUIRE(slot_pix && tile_info, AZ_E_NULL);
+  AZ_REQUIRE(batch > 0 && hin > 0 && win > 0 && (int64_t)batch * hin * win < (1ll << 31), AZ_E_SHAPE);
+  AZ_REQUIRE(rect_h > 1 && x3_shape_ok(rect_w, rect_h), AZ_E_UNSUPPORTED);
+  const int tiles_h = (hin + 1) / 2, tiles_w = (win + 1) / 2;
+  AZ_REQUIRE(block >= 0 && block < (int64_t)batch * x3_rect_blocks_per_image(tiles_h, tiles_w, rect_w, rect_h), AZ_E_SHAPE);
+  const X3RectGeom g = x3_rect_geom(block, tiles_h, tiles_w, rect_w, rect_h);
+  for (int s = 0; s < 512; ++s) {
+    int ih, iw;
+    const bool ok = x3_rect_slot_pixel(g, s, hin, win, pad_mode, ih, iw);
+    slot_pix[3 * s] = ok ? g.b : -1, slot_pix[3 * s + 1] = ok ? ih : -1, slot_pix[3 * s + 2] = ok ? iw : -1;
+  }
+  for (int j = 0; j < WT; ++j) {
+    int th, tw, ps;
+    const bool ok = x3_rect_tile(g, j, tiles_h, tiles_w, th, tw, ps);
+    tile_info[4 * j] = ok ? g.b : -1, tile_info[4 * j + 1] = th, tile_info[4 * j + 2] = tw, tile_info[4 * j + 3] = ps;
+  }
+  return g.nslots;
+}
+
 static int winograd_x3_entry(const AzConvArgs* a, az_stream_t stream, bool h2) {
   WinoP p;
   int splitk = 1;
   const int prc = wino_prepare(a, 16, 16ll * WC * 16 * 3 * 2, p, splitk);
   if (prc != AZ_OK) return prc;
   AZ_REQUIRE(p.tiles_w >= 2, AZ_E_UNSUPPORTED);  // (the kernel stages <= 32 tile-row segments per 64-tile block: maps >= 3 pixels wide)
+  {
+    const bool whole = p.a.gn_quads != nullptr;  // (split-K > 1 has dropped the pointer: the combine kernel produces the moments)
+    int rw, rh;
+    int64_t run_slots;
+    x3_choose_block(a->batch, p.tiles_h, p.tiles_w, whole, rw, rh, run_slots);
+    // AZ_X3_BLOCK="w,h" forces a shape (A/B runs and the bit-equality tests; "64,1" = the run form), read per call
+    if (const char* e = az_ab_env("AZ_X3_BLOCK")) {
+      int ew = 0, eh = 0;
+      if (sscanf(e, "%d,%d", &ew, &eh) == 2) {
+        AZ_REQUIRE(x3_shape_ok(ew, eh) && !(whole && eh > 1 && (p.tiles_w % ew || p.tiles_h % eh)), AZ_E_UNSUPPORTED);
+        rw = ew, rh = eh;
+      }
+    }
+    if (rh > 1) {
+      p.rect_w = rw, p.rect_h = rh;
+      p.tblocks = a->batch * x3_rect_blocks_per_image(p.tiles_h, p.tiles_w, rw, rh);
+      wino_order(p, 16);
+    }
+  }
   if (h2) AZ_REQUIRE(conv_pow2(a->w_scale), AZ_E_SHAPE);
   p.out_scale = h2 ? 1.f / a->w_scale : 1.f;
   if (h2) AZ_REQUIRE(AZ_ALIGNED16(a->in_absmax0) && AZ_ALIGNED16(a->in_absmax1) && (a->in_absmax0 || !a->in_absmax1), AZ_E_ALIGN);
@@ -2965,6 +3076,22 @@ static int winograd_x3_entry(const AzConvArgs* a, az_stream_t stream, bool h2) {
     rc = launch_splitk_reduce(cp, st);
   }
   return rc;
+}
+
+/* Workgroup order of the Winograd kernels, from p.cblocks / p.tblocks (wk = input channels per K step: 8 / 16). */
+static void wino_order(WinoP& p, int wk) {
+  // workgroup order (see the kernel): rectangles of gt x gc = 32 workgroups when both grid sides divide, cout blocks fastest
+  // otherwise (gt = 1, gc = cblocks).  AZ_WINO_RECT="gt,gc" overrides (A/B runs); "1,0" = cout fastest everywhere.
+  int env_gt = 0, env_gc = 0;  // (read per call like the other A/B switches: no unsynchronised static)
+  if (const char* e = az_ab_env("AZ_WINO_RECT")) sscanf(e, "%d,%d", &env_gt, &env_gc);
+  // (the x3 kernel's filter chunks are 1.5 x the fp32 stream's -- 6 B per value: two cout blocks per XCD keep a layer's chunks in its
+  //  4 MB L2 where four thrash it: 16 x 2 measured 1 - 2 % ahead of 8 x 4 on the 256- and 512-channel layers, tools/wx3_rect_ab.sh)
+  int gt = env_gt > 0 ? env_gt : 8, gc = env_gt > 0 ? (env_gc > 0 ? env_gc : p.cblocks) : (wk == 16 ? 2 : 4);
+  while (gc > 1 && p.cblocks % gc) gc >>= 1;
+  if (env_gt <= 0) gt = 32 / gc;
+  while (gt > 1 && p.tblocks % gt) gt >>= 1;
+  if (p.cblocks % gc || p.tblocks % gt) gt = 1, gc = p.cblocks;
+  p.gt = gt, p.gc = gc;
 }
 
 /* Validation and launch geometry shared by the two Winograd entries; wk = input channels per K step (8 / 16). */
@@ -3039,20 +3166,8 @@ static int wino_prepare(const AzConvArgs* a, int wk, int64_t ustage_bytes, WinoP
   if (splitk > 1) p.a.gn_quads = nullptr;  // (the slabs carry no moments: the combine kernel produces them)
   p.cblocks = (a->cout_s + WC - 1) / WC;
   p.tblocks = (p.ntiles + WT - 1) / WT;
-  {
-    // workgroup order (see the kernel): rectangles of gt x gc = 32 workgroups when both grid sides divide, cout blocks fastest
-    // otherwise (gt = 1, gc = cblocks).  AZ_WINO_RECT="gt,gc" overrides (A/B runs); "1,0" = cout fastest everywhere.
-    int env_gt = 0, env_gc = 0;  // (read per call like the other A/B switches: no unsynchronised static)
-    if (const char* e = az_ab_env("AZ_WINO_RECT")) sscanf(e, "%d,%d", &env_gt, &env_gc);
-    // (the x3 kernel's filter chunks are 1.5 x the fp32 stream's -- 6 B per value: two cout blocks per XCD keep a layer's chunks in its
-    //  4 MB L2 where four thrash it: 16 x 2 measured 1 - 2 % ahead of 8 x 4 on the 256- and 512-channel layers, tools/wx3_rect_ab.sh)
-    int gt = env_gt > 0 ? env_gt : 8, gc = env_gt > 0 ? (env_gc > 0 ? env_gc : p.cblocks) : (wk == 16 ? 2 : 4);
-    while (gc > 1 && p.cblocks % gc) gc >>= 1;
-    if (env_gt <= 0) gt = 32 / gc;
-    while (gt > 1 && p.tblocks % gt) gt >>= 1;
-    if (p.cblocks % gc || p.tblocks % gt) gt = 1, gc = p.cblocks;
-    p.gt = gt, p.gc = gc;
-  }
+  p.rect_w = WT, p.rect_h = 1;
+  wino_order(p, wk);
   AZ_REQUIRE((int64_t)p.nk * p.cblocks * ustage_bytes <= (1ll << 31), AZ_E_SHAPE);
   return AZ_OK;
 }

@@ -39,7 +39,7 @@ constexpr unsigned OOB = 0x80000000u;
 
 // Circular ("periodic") padding -- azula/nn/unet.py:175-180, torch padding_mode="circular": an out-of-range tap
 // coordinate wraps around the map instead of reading zero.  Only in the per-(tap, source) address setup, never in a K loop.
-__device__ __forceinline__ int wrap_coord(int i, int n, int mode) {
+__host__ __device__ __forceinline__ int wrap_coord(int i, int n, int mode) {
   if (mode) {
     i %= n;
     if (i < 0) i += n;
@@ -376,6 +376,70 @@ __device__ __forceinline__ void epilogue_store(const AzConvArgs& a, int n, int c
   epilogue_store_b<IO>(a, n, n / (a.hout * a.wout), co, v);
 }
 
+// ---- Rectangular tile blocks of the x3 / f16x2 Winograd kernel (wino_x3.hip; WinoP.rect_w x rect_h tiles, rect_h > 1).  The
+// kernel's prologue and az_winograd_x3_block_geometry (host only: tests/test_wino_rect_geometry.py) run the SAME functions.
+// A block holds rect_w x rect_h tiles of ONE image: the blocks tile each image's tiles_h x tiles_w grid row by row (tiles past
+// the edge are masked), tile j of a block is (row j / rect_w, column j % rect_w) of its rectangle, and the block stages ONE
+// window of (2 rect_h + 2) x (2 rect_w + 2) pixels, slot s = window row * ws + window column, each pixel once.
+
+// floor(x / d) for 0 <= x < 2^23, d > 0, without the integer-division expansion (host: the same correction on an exact quotient)
+__host__ __device__ __forceinline__ int az_fdiv(int x, int d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int q = (int)((float)x * __builtin_amdgcn_rcpf((float)d));
+#else
+  int q = (int)((float)x / (float)d);
+#endif
+  const int r = x - q * d;
+  q += r >= d ? 1 : (r < 0 ? -1 : 0);
+  return q;
+}
+
+struct X3RectGeom {
+  int rw, rh;    // the block's shape in tiles
+  int ws;        // pixels per row of the staged window: 2 rw + 2
+  int nslots;    // (2 rh + 2) * ws
+  int b, rb;     // the block's image, its index among the image's blocks
+  int th0, tw0;  // its first tile row / column
+};
+
+__host__ __device__ __forceinline__ int x3_rect_blocks_per_image(int tiles_h, int tiles_w, int rw, int rh) {
+  return az_fdiv(tiles_h + rh - 1, rh) * az_fdiv(tiles_w + rw - 1, rw);
+}
+
+__host__ __device__ __forceinline__ X3RectGeom x3_rect_geom(int tb, int tiles_h, int tiles_w, int rw, int rh) {
+  X3RectGeom g;
+  g.rw = rw, g.rh = rh;
+  g.ws = 2 * rw + 2;
+  g.nslots = (2 * rh + 2) * g.ws;
+  const int bw = az_fdiv(tiles_w + rw - 1, rw);
+  const int bpi = az_fdiv(tiles_h + rh - 1, rh) * bw;
+  g.b = az_fdiv(tb, bpi);
+  g.rb = tb - g.b * bpi;
+  const int by = az_fdiv(g.rb, bw);
+  g.th0 = by * rh;
+  g.tw0 = (g.rb - by * bw) * rw;
+  return g;
+}
+
+// Staged slot s: the input pixel (ih, iw) it holds -- wrapped under circular padding; false: the slot stages zeros (padding, a
+// ragged edge, a slot behind the window).
+__host__ __device__ __forceinline__ bool x3_rect_slot_pixel(const X3RectGeom& g, int s, int hin, int win, int pad_mode, int& ih, int& iw) {
+  const int r = az_fdiv(s, g.ws);
+  ih = wrap_coord(2 * g.th0 - 1 + r, hin, pad_mode);
+  iw = wrap_coord(2 * g.tw0 - 1 + (s - r * g.ws), win, pad_mode);
+  return s < g.nslots && (unsigned)ih < (unsigned)hin && (unsigned)iw < (unsigned)win;
+}
+
+// Tile j of the block: its tile coordinates and the slot of its patch's (row 0, column 0) -- patch (r, c) = slot pslot + r ws + c;
+// false: the tile lies past the image's edge (masked).
+__host__ __device__ __forceinline__ bool x3_rect_tile(const X3RectGeom& g, int j, int tiles_h, int tiles_w, int& th, int& tw, int& pslot) {
+  const int jy = az_fdiv(j, g.rw), jx = j - jy * g.rw;
+  th = g.th0 + jy;
+  tw = g.tw0 + jx;
+  pslot = 2 * jy * g.ws + 2 * jx;
+  return th < tiles_h && tw < tiles_w;
+}
+
 
 }  // namespace
 
@@ -390,5 +454,6 @@ struct WinoP {
   int cblocks;         // ceil(cout_s / WC)
   int tblocks;         // ceil(ntiles / WT)
   int gt, gc;          // workgroup order: rectangles of gt tile blocks x gc cout blocks, tile block fastest inside (1, cblocks: cout fastest)
+  int rect_w, rect_h;  // x3 kernel: a block's tiles as a rectangle of rect_w x rect_h = 64 tiles of one image; 64 x 1: runs of adjacent tiles across rows and images
   float out_scale;     // f16x2 form of the x3 kernel: 1 / w_scale; the accumulators are multiplied by out_scale / (the activation scale) behind the K loop
 };

@@ -27,6 +27,10 @@
 //     pixels instead of 16 n.  The pixels' 16 channels of the step (64 B) go global -> registers -> LDS as 16-byte lane slots
 //     (bounds-checked buffer loads: padding / ragged tiles land as zeros; upsampling, two sources, circular padding are
 //     offsets); then thread (tile tid >> 3, channel pair tid & 7) reads its 4x4 patch with 16 ds_read_b64.
+//     Where an image holds them, the launcher makes the block a RECTANGLE of tiles instead (template parameter RECT below; 8 x 8
+//     on the UNet's maps): patches overlap by two rows as well, one window of 18 x 18 = 324 pixels is staged instead of the
+//     520 - 576 of the runs (3 instead of 5 - 6 lane slots per thread and step), the patch read is the same code at another
+//     row stride, and a wave's eight tiles stay neighbours along a row, so its bank pattern is the run form's.
 //   * Epilogue: every wave applies the nu side of A^T M A to its two frequencies in registers, the k = 1 waves hand their partial
 //     to the k = 0 waves through LDS, which park Z[xi][px] as [xi][tile][px][cout]; all 8 waves read rows back applying the xi
 //     side; bias / SiLU / gate / residual / split-K slabs / GroupNorm moments of the output as in the fp32 kernel.
@@ -72,7 +76,14 @@ static_assert(X_LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 //   (ul h + uh h + (uh / 2^11) l) instead of six bf16 ones: 12 matrix instructions per phase, 56 instead of 88 vector
 //   instructions of splitting per phase and wave, 8 fragment registers fewer.  The accumulators are multiplied by
 //   p.out_scale = 1 / (AZ_F16X2_IN_SCALE * w_scale) (a power of two) behind the K loop; everything else is the same code.
-template <int AFF, bool TAIL, bool H2 = false>
+// RECT: the block's 64 tiles are a rectangle of p.rect_w x p.rect_h tiles of ONE image (conv_shared.h: X3RectGeom) instead of
+//   runs: ONE window of (2 rect_h + 2) x (2 rect_w + 2) pixels is staged per step, so vertically adjacent tile rows share their
+//   two overlapping pixel rows too -- 8 x 8 tiles: 18 x 18 = 324 slots (3 staging pieces per thread) where a run of 64 tiles
+//   stages 520 (5).  Only the prologue's geometry (block -> image / tiles, slot -> pixel, tile -> patch address) and the tile
+//   table of the epilogue differ: the K loop, the V layout and every output's accumulation order are the run form's, so the
+//   outputs are bit-identical; a GroupNorm record covers the rectangle.  The launcher picks the shape per launch (conv.hip:
+//   x3_choose_block); RECT = false is the run form, token for token what it was.
+template <int AFF, bool TAIL, bool H2 = false, bool RECT = false>
 __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   extern __shared__ __attribute__((aligned(16))) float wsm[];
   char* const smem = reinterpret_cast<char*>(wsm);
@@ -99,7 +110,9 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   const int cb = (rect - rrow * rcols) * p.gc + rin_c;
   const int t0 = tb * XT;
   const int tiles_img = p.tiles_h * p.tiles_w;
-  const int b_first = t0 / tiles_img;
+  X3RectGeom rg = {};
+  if constexpr (RECT) rg = x3_rect_geom(tb, p.tiles_h, p.tiles_w, p.rect_w, p.rect_h);
+  const int b_first = RECT ? rg.b : t0 / tiles_img;
 
   const int kt_begin = blockIdx.y * p.kps;
   const int kt_end = min(p.nk, kt_begin + p.kps);
@@ -123,7 +136,16 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   const int vq = tid & 7;
   int v_b = -1, v_ih0 = 0, v_iw0 = 0;
   bool v_dok = true;
-  {
+  int v_pslot = 0;  // (RECT: slot of the patch's first pixel)
+  if constexpr (RECT) {
+    int th, tw;
+    if (x3_rect_tile(rg, vj, p.tiles_h, p.tiles_w, th, tw, v_pslot)) {
+      v_b = 0;
+      v_ih0 = 2 * th - 1;
+      v_iw0 = 2 * tw - 1;
+      (void)az_depth_plane(a, rg.b, v_dok);
+    }
+  } else {
     const int t = t0 + vj;
     if (t < p.ntiles) {
       const int b = t / tiles_img;
@@ -140,8 +162,8 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   // RS = 2 len + 2 pixels from slot S = 8 (js + g) on: slot(j, r, c) = S + r RS + 2 (j - js) + c.  Slots of the block: 8 (64 + G).
   const int tw0 = (t0 % tiles_img) % p.tiles_w;
   const int nseg = (XT - 1 + tw0) / p.tiles_w + 1;
-  const int nslots = 8 * (XT + nseg);
-  const int ndma = (4 * nslots + 511) >> 9;  // staging pieces per thread and step (one 16-byte lane slot each): 5 or 6 (nslots <= 768)
+  const int nslots = RECT ? rg.nslots : 8 * (XT + nseg);
+  const int ndma = (4 * nslots + 511) >> 9;  // staging pieces per thread and step (one 16-byte lane slot each): 5 or 6 (nslots <= 768); RECT: 3 or 4 (the host checks nslots <= 512)
   auto seg_of = [&](int g, int& js, int& len) {
     js = max(0, g * p.tiles_w - tw0);
     len = min(XT, (g + 1) * p.tiles_w - tw0) - js;
@@ -164,6 +186,14 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     for (int m = 0; m < 6; ++m) {
       const int L = m * 512 + tid;
       const int s = L >> 2;
+      if constexpr (RECT) {
+        bool dok = true;
+        const int bs = az_depth_plane(a, rg.b, dok) - b_base;
+        int ih, iw;
+        const bool ok = x3_rect_slot_pixel(rg, s, a.hin, a.win, a.pad_mode, ih, iw) && dok;
+        doff[m] = ok ? (unsigned)((((bs * hs + (ih >> up)) * ws + (iw >> up)) * cs + (L & 3) * 4) * 4) : OOB;
+        continue;
+      }
       const int g = fdiv((s >> 3) + tw0, p.tiles_w + 1);
       int js, len;
       seg_of(g, js, len);
@@ -200,8 +230,8 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   // the thread's own patch: LDS address of (row 0, column 0), row stride; validity of its 16 positions (in_affine keeps padding at zero)
   int pj_s, pj_len;
   seg_of(fdiv(vj + tw0, p.tiles_w), pj_s, pj_len);
-  const int prow = (2 * pj_len + 2) * X_SLOT;
-  const char* const patch = smem + X_STAGE + (8 * (pj_s + fdiv(vj + tw0, p.tiles_w)) + 2 * (vj - pj_s)) * X_SLOT + vq * 8;
+  const int prow = RECT ? rg.ws * X_SLOT : (2 * pj_len + 2) * X_SLOT;
+  const char* const patch = smem + X_STAGE + (RECT ? v_pslot : 8 * (pj_s + fdiv(vj + tw0, p.tiles_w)) + 2 * (vj - pj_s)) * X_SLOT + vq * 8;
   unsigned vmask = 0;
   if constexpr (AFF != 0) {
 #pragma unroll
@@ -219,7 +249,7 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   // buffer_load ... lds costs the issuing wave 100 - 180 cycles beside MFMAs: profiles/r05_wx3_timeline_v3.txt.)
   float4 gq[6];
   auto gl = [&](int kt, int m) __attribute__((always_inline)) {
-    if (m < 5 || m < ndma) {  // (uniform; a block always has at least 520 slots = 4.06 pieces per thread)
+    if (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma) {  // (uniform; a block always has at least 520 slots = 4.06 pieces per thread; RECT: 324 .. 512 slots)
       const bool src1 = kt >= p.nkc0;
       const int kc = src1 ? kt - p.nkc0 : kt;
       const __amdgpu_buffer_rsrc_t r = src1 ? rs1 : rs0;
@@ -229,7 +259,7 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     }
   };
   auto gs = [&](int m) __attribute__((always_inline)) {
-    if (m < 5 || m < ndma) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];
+    if (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];
   };
   auto patch_rows = [&](int kt, int r0, int r1) __attribute__((always_inline)) {  // rows [r0, r1) of the staged patch -> rv
 #pragma unroll
@@ -585,7 +615,14 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     const int tl = wave * 32 + l31;
     const int t = t0 + tl;
     int n00 = -1, fl = 0, b = 0;
-    if (t < p.ntiles) {
+    if constexpr (RECT) {
+      int th, tw, ps;
+      if (x3_rect_tile(rg, tl, p.tiles_h, p.tiles_w, th, tw, ps)) {
+        b = rg.b;
+        n00 = (b * a.hout + 2 * th) * a.wout + 2 * tw;
+        fl = (2 * th + 1 < a.hout ? 1 : 0) | (2 * tw + 1 < a.wout ? 2 : 0);
+      }
+    } else if (t < p.ntiles) {
       b = t / tiles_img;
       const int rr = t - b * tiles_img;
       const int th = rr / p.tiles_w;
@@ -627,7 +664,7 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     return;
   }
   // ---- GroupNorm statistics of the OUTPUT (see conv_winograd_kernel: one partial per (image, tile block, channel quad); the host
-  // enables this only when the 64 tiles of a workgroup lie in one image, whole 2 x 2 tiles, cout_s % 64 == 0)
+  // enables this only when the 64 tiles of a workgroup lie in one image, whole 2 x 2 tiles, cout_s % 64 == 0; RECT: whole rectangles)
   float mom[3] = {0.f, 0.f, 0.f};
   epilogue_store_batch<8, true>(a, on, ob, co, ov, (int64_t)blockIdx.y * p.npix, mom);
   float am = mom[0] + mom[1] * (1.f / 32.f);
@@ -657,7 +694,7 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     for (int o = 1; o < 8; o <<= 1, hn *= 2.f)
 #pragma unroll
       for (int k = 0; k < 8; k += 2 * o) chan(wm[k], w2[k], wm[k + o], w2[k + o], hn);
-    const int chunk = (t0 - b_first * tiles_img) / XT;
+    const int chunk = RECT ? rg.rb : (t0 - b_first * tiles_img) / XT;
     float* out = a.gn_quads + ((((int64_t)b_first * a.gn_chunks + chunk) * (a.cout_s / 4)) + (cb * (XC / 4) + tid)) * 4;
     out[0] = 1024.f;
     out[1] = wm[0];
@@ -669,31 +706,35 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
 }  // namespace
 
 // Launch (host side of az_conv2d_winograd_x3_f32, conv.hip validates the descriptor and fills `p` in 16-channel steps).
-template <int AFF, bool TAIL, bool H2>
+template <int AFF, bool TAIL, bool H2, bool RECT>
 static int launch_x3(const WinoP& p, unsigned splitk, hipStream_t st) {
   static std::atomic<uint64_t> lds_set{0};  // (one per instantiation, one bit per device: common.h)
-  hipError_t e = az_max_dynamic_lds((const void*)conv_winograd_x3_kernel<AFF, TAIL, H2>, X_LDS_BYTES, lds_set);
+  hipError_t e = az_max_dynamic_lds((const void*)conv_winograd_x3_kernel<AFF, TAIL, H2, RECT>, X_LDS_BYTES, lds_set);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((conv_winograd_x3_kernel<AFF, TAIL, H2>), dim3((unsigned)((int64_t)p.cblocks * p.tblocks), splitk), dim3(512), X_LDS_BYTES,
+  hipLaunchKernelGGL((conv_winograd_x3_kernel<AFF, TAIL, H2, RECT>), dim3((unsigned)((int64_t)p.cblocks * p.tblocks), splitk), dim3(512), X_LDS_BYTES,
                      st, p);
   return az_launch_status();
 }
 
-template <bool H2>
+template <bool H2, bool RECT>
 static int launch_x3_mode(const WinoP& p, unsigned splitk, hipStream_t st) {
   const bool tail = (p.a.c0s % XK) != 0 || (p.a.c1s % XK) != 0;
   const int aff = !p.a.in_affine ? 0 : (p.a.in_act == 0 ? 1 : 2);
   switch (aff * 2 + (tail ? 1 : 0)) {
-    case 0: return launch_x3<0, false, H2>(p, splitk, st);
-    case 1: return launch_x3<0, true, H2>(p, splitk, st);
-    case 2: return launch_x3<1, false, H2>(p, splitk, st);
-    case 3: return launch_x3<1, true, H2>(p, splitk, st);
-    case 4: return launch_x3<2, false, H2>(p, splitk, st);
-    default: return launch_x3<2, true, H2>(p, splitk, st);
+    case 0: return launch_x3<0, false, H2, RECT>(p, splitk, st);
+    case 1: return launch_x3<0, true, H2, RECT>(p, splitk, st);
+    case 2: return launch_x3<1, false, H2, RECT>(p, splitk, st);
+    case 3: return launch_x3<1, true, H2, RECT>(p, splitk, st);
+    case 4: return launch_x3<2, false, H2, RECT>(p, splitk, st);
+    default: return launch_x3<2, true, H2, RECT>(p, splitk, st);
   }
 }
 
 // h2: the f16x2 form (p.out_scale set by the caller)
 __attribute__((visibility("hidden"))) int azi_winograd_x3_launch(const WinoP& p, unsigned splitk, hipStream_t st, bool h2) {
-  return h2 ? launch_x3_mode<true>(p, splitk, st) : launch_x3_mode<false>(p, splitk, st);
+  if (p.rect_h > 1) {  // rectangular tile blocks (validated by the caller: rect_w * rect_h == 64, one window <= 512 slots)
+    if (p.rect_w * p.rect_h != XT || (2 * p.rect_w + 2) * (2 * p.rect_h + 2) > 512) return AZ_E_SHAPE;
+    return h2 ? launch_x3_mode<true, true>(p, splitk, st) : launch_x3_mode<false, true>(p, splitk, st);
+  }
+  return h2 ? launch_x3_mode<true, false>(p, splitk, st) : launch_x3_mode<false, false>(p, splitk, st);
 }

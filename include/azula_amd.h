@@ -661,6 +661,20 @@ int az_conv2d_winograd_suggest_splitk(int64_t batch, int32_t hout, int32_t wout,
  * the epilogue, split-K and gn_quads as az_conv2d_winograd_f32.  Inputs are assumed finite (an Inf operand splits into NaN
  * pieces).                                                                                                                  */
 int az_conv2d_winograd_x3_f32(const AzConvArgs* args, az_stream_t stream);
+/* Block shape of az_conv2d_winograd_x3_f32 / az_conv2d_winograd_f16x2_f32 (host arithmetic only: no device is touched).  A
+ * workgroup's 64 tiles are runs of horizontally adjacent tiles (64 x 1) or a rectangle of rect_w x rect_h tiles of one image, one
+ * of 32 x 2, 16 x 4, 8 x 8, 4 x 16, which stages each pixel of its (2 rect_h + 2) x (2 rect_w + 2) window once per K step.
+ * az_winograd_x3_choose_block: the launcher's choice for a (batch, hin, win) map -- the shape with the fewest staged pixel slots
+ * over all blocks that needs no more blocks than the run form (`whole`: only shapes that divide the tile grid, as a launch with
+ * gn_quads and splitk 1 requires) -- with that total (`slots`) and the run form's (`slots_run`).
+ * az_winograd_x3_block_geometry: what block `block` of the rectangular form stages, computed by the functions the kernel's
+ * prologue runs: slot_pix[512][3] = (image, row, column) of the input pixel in every staged slot ((-1, -1, -1): the slot holds
+ * zeros), tile_info[64][4] = (image or -1 for a masked tile, tile row, tile column, slot of the tile's patch (0, 0); patch (r, c)
+ * sits r * (2 rect_w + 2) + c slots further).  Returns the slots of the window or AZ_E_* (64 x 1 is AZ_E_UNSUPPORTED here). */
+int az_winograd_x3_choose_block(int32_t batch, int32_t hin, int32_t win, int32_t whole, int32_t* rect_w, int32_t* rect_h,
+                                int64_t* slots, int64_t* slots_run);
+int az_winograd_x3_block_geometry(int32_t batch, int32_t hin, int32_t win, int32_t pad_mode, int32_t rect_w, int32_t rect_h,
+                                  int32_t block, int32_t* slot_pix, int32_t* tile_info);
 /* fp32 operands on the fp16 matrix pipe ("f16x2"; AZ_FP32_MFMA=f16x2): HALF the matrix instructions of the bf16x3 form.
  * An activation x enters as x' = x * AZ_F16X2_IN_SCALE = h + l / 2^11 with h = fp16(x') and l = fp16((x' - h) * 2^11) (22 - 23
  * significant bits), a weight as w' = w * w_scale = wh + wl (two fp16 pieces, the residual unscaled) plus a third plane

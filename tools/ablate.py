@@ -132,8 +132,8 @@ VARIANTS["ax_nosplitp"] = [
 #      the gate: the filter fragment loads per MFMA double in that form (tools/ablate.py wx3_nou prices them).
 _G_PROD = [
     ("wino_x3.hip", "  const int cb = (rect - rrow * rcols) * p.gc + rin_c;\n", "  const int cb = (rect - rrow * rcols) * p.gc + rin_c;\n  const bool prod = !(cb & 1);\n"),
-    ("wino_x3.hip", "    if (m < 5 || m < ndma) {  // (uniform; a block always has at least 520 slots = 4.06 pieces per thread)", "    if (prod && (m < 5 || m < ndma)) {"),
-    ("wino_x3.hip", "    if (m < 5 || m < ndma) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];", "    if (prod && (m < 5 || m < ndma)) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];"),
+    ("wino_x3.hip", "    if (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma) {  // (uniform; a block always has at least 520 slots = 4.06 pieces per thread; RECT: 324 .. 512 slots)", "    if (prod && (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma)) {"),
+    ("wino_x3.hip", "    if (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];", "    if (prod && (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma)) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];"),
     ("wino_x3.hip", "  auto patch_rows = [&](int kt, int r0, int r1) __attribute__((always_inline)) {  // rows [r0, r1) of the staged patch -> rv\n", "  auto patch_rows = [&](int kt, int r0, int r1) __attribute__((always_inline)) {\n    if (!prod) return;\n"),
     ("wino_x3.hip", "    const f32x2 d0 = rv[c], d1 = rv[4 + c], d2 = rv[8 + c], d3 = rv[12 + c];\n", "    if (!prod) return;\n    const f32x2 d0 = rv[c], d1 = rv[4 + c], d2 = rv[8 + c], d3 = rv[12 + c];\n"),
     ("wino_x3.hip", "    const f32x2 u0 = rv[4 * xi], u1 = rv[4 * xi + 1], u2 = rv[4 * xi + 2], u3 = rv[4 * xi + 3];\n", "    if (!prod) return;\n    const f32x2 u0 = rv[4 * xi], u1 = rv[4 * xi + 1], u2 = rv[4 * xi + 2], u3 = rv[4 * xi + 3];\n"),
@@ -320,6 +320,9 @@ VARIANTS["h2big_valu4"] = [("conv.hip", _H2G_OLD, "        if (k < NM - 10) __bu
 
 # ---- x3 Winograd kernel: staged pixel slots at a stride of 80 B instead of 64 B (measured: no gain, more bank conflicts -- profiles/r06_wx3_slot_ab.txt)
 VARIANTS["wx3_slot80"] = [("wino_x3.hip", "constexpr int X_SLOT = 64;", "constexpr int X_SLOT = 80;")]
+# ---- x3 Winograd kernel: the run form of the tile blocks everywhere (no rectangular blocks: profiles/r07_wx3_rect_blocks_ab.txt; the
+#      same switch without a rebuild: AZ_DEBUG_AB=1 AZ_X3_BLOCK=64,1)
+VARIANTS["wx3_norect"] = [("conv.hip", "constexpr bool X3_RECT_BLOCKS = true;", "constexpr bool X3_RECT_BLOCKS = false;")]
 
 # ---- f16x2 attention, 256-query workgroups at head_dim <= 64: four waves per SIMD (<= 128 registers: two resident workgroups per CU, so
 #      that one's load / stage / barrier skeleton hides under the other's products) -- the compiler spills 31 registers to get there
