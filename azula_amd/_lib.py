@@ -418,12 +418,14 @@ PROTOTYPES: dict[str, list] = {
     "az_silu_f32": [vp, vp, i64, c_stream],
     "az_axpby_f32": [vp, vp, vp, vp, vp, i64, i64, i32, c_stream],
     "az_cfg_combine_f32": [vp, vp, vp, vp, i64, c_stream],
+    "az_cfg_split_f32": [vp, vp, vp, i64, c_stream],
     "az_nchw_to_nhwc_f32": [vp, vp, vp, i64, i64, i64, i64, c_stream],
     "az_nhwc_to_nchw_f32": [vp, vp, i64, i64, i64, i64, c_stream],
     "az_upsample_nearest_f32": [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, c_stream],
     "az_groupnorm_bwd_stats_f32": [vp, vp, vp, vp, i64, vp, i32, i64, i64, i64, i64, i32, i32, f32, c_stream],
     "az_groupnorm_bwd_apply_f32": [vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, i64, i64, i64, i64, i32, f32, c_stream],
     "az_rownorm_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, f32, c_stream],
+    "az_rownorm_bwd_w_f32": [vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i32, f32, c_stream],
     "az_silu_bwd_f32": [vp, vp, vp, i64, c_stream],
     "az_channel_scale_f32": [vp, vp, vp, i64, i64, i64, i64, i64, c_stream],
     "az_act_f32": [vp, vp, i64, i32, c_stream],
@@ -487,8 +489,11 @@ PROTOTYPES: dict[str, list] = {
     "az_attention_bf16_f32": [C.POINTER(AzAttnArgs), c_stream],
     "az_attention_f16_f32": [C.POINTER(AzAttnArgs), c_stream],
     "az_qk_prep_f32": [vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, f32, vp, vp, c_stream],
+    "az_qk_prep_w_f32": [vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, f32, vp, vp, vp, vp, c_stream],
     "az_qk_prep_bwd_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, f32, vp, vp,
                            c_stream],
+    "az_qk_prep_bwd_w_f32": [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, f32, vp,
+                             vp, vp, vp, c_stream],
     "az_attention_bwd_f32": [C.POINTER(AzAttnBwdArgs), c_stream],
     "az_swiglu_f32": [vp, vp, i64, i64, i64, i64, c_stream],
     "az_patchify_f32": [vp, vp, vp, i64, i64, i64, i64, i64, i64, c_stream],

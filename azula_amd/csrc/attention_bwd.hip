@@ -297,6 +297,7 @@ struct QkPrepArgs {
   float inv_n, eps;
   const float* cs;
   const float* sn;
+  const float* w[2];  // learned gains of q, k (D floats each) between the RMS norm and the rotation, or null
 };
 
 template <int G>
@@ -306,7 +307,9 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-template <int D, bool BWD>
+// GAIN: q^ = rope(w rms_norm(q)); backward u = R^T g, qg = w u, dx = r (qg - xh mean(qg xh)).  Without it the instantiation is
+// the kernel as it was, bit for bit.
+template <int D, bool BWD, bool GAIN>
 __global__ __launch_bounds__(256) void qk_prep_kernel(QkPrepArgs p) {
   constexpr int G = D / 4, RPB = 256 / G;
   const int gl = threadIdx.x % G;
@@ -331,13 +334,20 @@ __global__ __launch_bounds__(256) void qk_prep_kernel(QkPrepArgs p) {
     }
     float r = 1.f;
     if (p.rms) r = rsqrtf(group_sum<G>(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w) * p.inv_n + p.eps);
+    float4 w = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (GAIN) {
+      const float* wp = p.w[which];  // (rows alternate q / k: the pointer, not the branch, differs between lane groups)
+      if (wp != nullptr) w = *reinterpret_cast<const float4*>(wp + 4 * gl);
+    }
     float4 y;
     if (!BWD) {
       x.x *= r, x.y *= r, x.z *= r, x.w *= r;
+      if (GAIN) x.x *= w.x, x.y *= w.y, x.z *= w.z, x.w *= w.w;
       y = make_float4(x.x * c0 - x.y * s0, x.x * s0 + x.y * c0, x.z * c1 - x.w * s1, x.z * s1 + x.w * c1);
     } else {
       // the rotation's transpose (pairs turned by -theta), then the RMS-norm pullback dx = r (g - xh mean(g xh))
-      const float4 u = make_float4(g.x * c0 + g.y * s0, g.y * c0 - g.x * s0, g.z * c1 + g.w * s1, g.w * c1 - g.z * s1);
+      float4 u = make_float4(g.x * c0 + g.y * s0, g.y * c0 - g.x * s0, g.z * c1 + g.w * s1, g.w * c1 - g.z * s1);
+      if (GAIN) u.x *= w.x, u.y *= w.y, u.z *= w.z, u.w *= w.w;
       y = u;
       if (p.rms) {
         const float4 xh = make_float4(x.x * r, x.y * r, x.z * r, x.w * r);
@@ -349,15 +359,15 @@ __global__ __launch_bounds__(256) void qk_prep_kernel(QkPrepArgs p) {
   }
 }
 
-template <bool BWD>
+template <bool BWD, bool GAIN>
 int qk_prep_launch(const QkPrepArgs& p, int head_dim, hipStream_t s) {
   const int rpb = 256 / (head_dim / 4);
   const dim3 grid((unsigned)az_stream_grid(p.rows, rpb));
   switch (head_dim) {
-    case 16: hipLaunchKernelGGL((qk_prep_kernel<16, BWD>), grid, dim3(256), 0, s, p); break;
-    case 32: hipLaunchKernelGGL((qk_prep_kernel<32, BWD>), grid, dim3(256), 0, s, p); break;
-    case 64: hipLaunchKernelGGL((qk_prep_kernel<64, BWD>), grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL((qk_prep_kernel<128, BWD>), grid, dim3(256), 0, s, p); break;
+    case 16: hipLaunchKernelGGL((qk_prep_kernel<16, BWD, GAIN>), grid, dim3(256), 0, s, p); break;
+    case 32: hipLaunchKernelGGL((qk_prep_kernel<32, BWD, GAIN>), grid, dim3(256), 0, s, p); break;
+    case 64: hipLaunchKernelGGL((qk_prep_kernel<64, BWD, GAIN>), grid, dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL((qk_prep_kernel<128, BWD, GAIN>), grid, dim3(256), 0, s, p); break;
   }
   return az_launch_status();
 }
@@ -392,6 +402,26 @@ int az_qk_prep_f32(float* q_hat, float* k_hat, const float* q, const float* k, i
                    int32_t head_dim, int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride,
                    int64_t out_tstride, int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
                    const float* rope_sin, az_stream_t stream) {
+  return az_qk_prep_w_f32(q_hat, k_hat, q, k, batch, tokens, heads, head_dim, in_bstride, in_tstride, in_hstride, out_bstride,
+                          out_tstride, out_hstride, qk_rmsnorm, norm_dim, eps, rope_cos, rope_sin, nullptr, nullptr, stream);
+}
+
+int az_qk_prep_bwd_f32(float* dq, float* dk, const float* dq_hat, const float* dk_hat, const float* q, const float* k, int64_t batch,
+                       int64_t tokens, int32_t heads, int32_t head_dim, int64_t g_bstride, int64_t g_tstride, int64_t g_hstride,
+                       int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride, int64_t out_tstride,
+                       int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
+                       const float* rope_sin, az_stream_t stream) {
+  return az_qk_prep_bwd_w_f32(dq, dk, dq_hat, dk_hat, q, k, batch, tokens, heads, head_dim, g_bstride, g_tstride, g_hstride, in_bstride,
+                              in_tstride, in_hstride, out_bstride, out_tstride, out_hstride, qk_rmsnorm, norm_dim, eps, rope_cos,
+                              rope_sin, nullptr, nullptr, stream);
+}
+
+// The gains are head_dim floats each and may be null one by one (a null one is a gain of 1); with both null the launch is the
+// gain-free instantiation, so the entries above keep their bits.
+int az_qk_prep_w_f32(float* q_hat, float* k_hat, const float* q, const float* k, int64_t batch, int64_t tokens, int32_t heads,
+                     int32_t head_dim, int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride,
+                   int64_t out_tstride, int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
+                   const float* rope_sin, const float* q_weight, const float* k_weight, az_stream_t stream) {
   AZ_REQUIRE(q_hat && k_hat && q && k && (rope_cos == nullptr) == (rope_sin == nullptr), AZ_E_NULL);
   AZ_REQUIRE(batch > 0 && tokens > 0 && tokens < (1ll << 31) && heads > 0 && norm_dim >= 0 && norm_dim <= head_dim, AZ_E_SHAPE);
   AZ_REQUIRE(head_dim_ok(head_dim), AZ_E_UNSUPPORTED);
@@ -405,14 +435,17 @@ int az_qk_prep_f32(float* q_hat, float* k_hat, const float* q, const float* k, i
   p.T = (int)tokens, p.H = heads, p.rms = qk_rmsnorm != 0;
   p.inv_n = 1.0f / (float)(norm_dim ? norm_dim : head_dim), p.eps = eps;
   p.cs = rope_cos, p.sn = rope_sin;
-  return qk_prep_launch<false>(p, head_dim, az_s(stream));
+  if (q_weight == nullptr && k_weight == nullptr) return qk_prep_launch<false, false>(p, head_dim, az_s(stream));
+  AZ_REQUIRE(AZ_ALIGNED16(q_weight) && AZ_ALIGNED16(k_weight), AZ_E_ALIGN);
+  p.w[0] = q_weight, p.w[1] = k_weight;
+  return qk_prep_launch<false, true>(p, head_dim, az_s(stream));
 }
 
-int az_qk_prep_bwd_f32(float* dq, float* dk, const float* dq_hat, const float* dk_hat, const float* q, const float* k, int64_t batch,
+int az_qk_prep_bwd_w_f32(float* dq, float* dk, const float* dq_hat, const float* dk_hat, const float* q, const float* k, int64_t batch,
                        int64_t tokens, int32_t heads, int32_t head_dim, int64_t g_bstride, int64_t g_tstride, int64_t g_hstride,
                        int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride, int64_t out_tstride,
                        int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
-                       const float* rope_sin, az_stream_t stream) {
+                       const float* rope_sin, const float* q_weight, const float* k_weight, az_stream_t stream) {
   AZ_REQUIRE(dq && dk && dq_hat && dk_hat && q && k && (rope_cos == nullptr) == (rope_sin == nullptr), AZ_E_NULL);
   AZ_REQUIRE(batch > 0 && tokens > 0 && tokens < (1ll << 31) && heads > 0 && norm_dim >= 0 && norm_dim <= head_dim, AZ_E_SHAPE);
   AZ_REQUIRE(head_dim_ok(head_dim), AZ_E_UNSUPPORTED);
@@ -428,7 +461,10 @@ int az_qk_prep_bwd_f32(float* dq, float* dk, const float* dq_hat, const float* d
   p.T = (int)tokens, p.H = heads, p.rms = qk_rmsnorm != 0;
   p.inv_n = 1.0f / (float)(norm_dim ? norm_dim : head_dim), p.eps = eps;
   p.cs = rope_cos, p.sn = rope_sin;
-  return qk_prep_launch<true>(p, head_dim, az_s(stream));
+  if (q_weight == nullptr && k_weight == nullptr) return qk_prep_launch<true, false>(p, head_dim, az_s(stream));
+  AZ_REQUIRE(AZ_ALIGNED16(q_weight) && AZ_ALIGNED16(k_weight), AZ_E_ALIGN);
+  p.w[0] = q_weight, p.w[1] = k_weight;
+  return qk_prep_launch<true, true>(p, head_dim, az_s(stream));
 }
 
 }  // extern "C"

@@ -182,10 +182,14 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(float* __restrict__ d
 
 // One wave per row (pixel).  kind 0: LayerNorm with the UNBIASED variance (xh = (x - mean) rstd, rstd = (var_unb + eps)^-1/2:
 // dx = rstd (q - mean(q) - xh mean(q xh) n / (n - 1))); kind 1: RMSNorm (xh = x rstd: dx = rstd (q - xh mean(q xh))).
+// HAS_W: a learned per-channel gain under the modulation (y = (1 + scale) weight norm(x) + shift: q = g weight (1 + scale));
+// without it the instantiation is the kernel as it was, bit for bit.
+template <bool HAS_W>
 __global__ __launch_bounds__(256) void rownorm_bwd_kernel(float* __restrict__ dx, const float* __restrict__ x,
                                                           const float* __restrict__ g, const float* __restrict__ res,
-                                                          const float* __restrict__ scale, int64_t scale_bstride, int64_t rows,
-                                                          int64_t rows_per_batch, int C, int cs, int kind, float eps) {
+                                                          const float* __restrict__ scale, const float* __restrict__ weight,
+                                                          int64_t scale_bstride, int64_t rows, int64_t rows_per_batch, int C, int cs,
+                                                          int kind, float eps) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -214,7 +218,7 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(float* __restrict__ dx
     }
     float m1 = 0.f, m2 = 0.f;
     for (int c = lane; c < C; c += 64) {
-      const float q = (sc ? 1.f + sc[c] : 1.f) * gr[c];
+      const float q = (sc ? 1.f + sc[c] : 1.f) * (HAS_W ? gr[c] * weight[c] : gr[c]);
       m1 += q;
       m2 += q * ((xr[c] - mean) * rstd);
     }
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(float* __restrict__ dx
     for (int c = lane; c < cs; c += 64) {
       float o = 0.f;
       if (c < C) {
-        const float q = (sc ? 1.f + sc[c] : 1.f) * gr[c];
+        const float q = (sc ? 1.f + sc[c] : 1.f) * (HAS_W ? gr[c] * weight[c] : gr[c]);
         const float xh = (xr[c] - mean) * rstd;
         o = (rr ? rr[c] : 0.f) + rstd * (q - m1 - xh * m2);
       }
@@ -375,6 +379,32 @@ __global__ __launch_bounds__(256) void upsample_nearest_bwd_kernel(float* __rest
   }
 }
 
+// The cotangent of the guided mean m = (1 + g) m+ - g m- on the stacked 2B batch: v2 = [(1 + g) v ; -g v].  The second half
+// starts at v2 + n, which is 16-byte aligned only when n % 4 == 0: float4 stores where it is, scalar stores otherwise; the
+// n % 4 tail is scalar.  12 B / element.
+__global__ __launch_bounds__(256) void cfg_split_kernel(float* __restrict__ v2, const float* __restrict__ v,
+                                                        const float* __restrict__ g, int64_t n) {
+  const float gv = g[0], a = 1.0f + gv, b = -gv;
+  const int64_t n4 = n / 4;
+  const bool hi4 = n % 4 == 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const float4 x = reinterpret_cast<const float4*>(v)[i];
+    reinterpret_cast<float4*>(v2)[i] = make_float4(a * x.x, a * x.y, a * x.z, a * x.w);
+    float* hi = v2 + n + 4 * i;
+    if (hi4) {
+      *reinterpret_cast<float4*>(hi) = make_float4(b * x.x, b * x.y, b * x.z, b * x.w);
+    } else {
+      hi[0] = b * x.x, hi[1] = b * x.y, hi[2] = b * x.z, hi[3] = b * x.w;
+    }
+  }
+  for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float x = v[i];
+    v2[i] = a * x;
+    v2[n + i] = b * x;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -418,6 +448,12 @@ int az_groupnorm_bwd_apply_f32(float* dx, const float* x, const float* g, const 
 
 int az_rownorm_bwd_f32(float* dx, const float* x, const float* g, const float* res, const float* scale, int64_t scale_bstride,
                        int64_t rows, int64_t rows_per_batch, int64_t C, int64_t cs, int32_t kind, float eps, az_stream_t stream) {
+  return az_rownorm_bwd_w_f32(dx, x, g, res, scale, scale_bstride, nullptr, rows, rows_per_batch, C, cs, kind, eps, stream);
+}
+
+int az_rownorm_bwd_w_f32(float* dx, const float* x, const float* g, const float* res, const float* scale, int64_t scale_bstride,
+                         const float* weight, int64_t rows, int64_t rows_per_batch, int64_t C, int64_t cs, int32_t kind, float eps,
+                         az_stream_t stream) {
   AZ_REQUIRE(dx && x && g, AZ_E_NULL);
   AZ_REQUIRE(rows > 0 && rows_per_batch > 0 && C > 0 && cs >= C && cs % 4 == 0 && (kind == 0 || kind == 1) && scale_bstride >= 0 &&
                  (kind == 1 || C > 1),
@@ -425,8 +461,20 @@ int az_rownorm_bwd_f32(float* dx, const float* x, const float* g, const float* r
   AZ_REQUIRE(AZ_ALIGNED16(dx) && AZ_ALIGNED16(x) && AZ_ALIGNED16(g) && AZ_ALIGNED16(res), AZ_E_ALIGN);
   int64_t blocks = (rows + 3) / 4;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, az_s(stream), dx, x, g, res, scale, scale_bstride,
-                     rows, rows_per_batch, (int)C, (int)cs, (int)kind, eps);
+  if (weight != nullptr)
+    hipLaunchKernelGGL(rownorm_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, az_s(stream), dx, x, g, res, scale, weight,
+                       scale_bstride, rows, rows_per_batch, (int)C, (int)cs, (int)kind, eps);
+  else
+    hipLaunchKernelGGL(rownorm_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, az_s(stream), dx, x, g, res, scale, weight,
+                       scale_bstride, rows, rows_per_batch, (int)C, (int)cs, (int)kind, eps);
+  return az_launch_status();
+}
+
+int az_cfg_split_f32(float* v2, const float* v, const float* g, int64_t n, az_stream_t stream) {
+  AZ_REQUIRE(v2 && v && g, AZ_E_NULL);
+  AZ_REQUIRE(n > 0, AZ_E_SHAPE);
+  AZ_REQUIRE(AZ_ALIGNED16(v2) && AZ_ALIGNED16(v), AZ_E_ALIGN);
+  hipLaunchKernelGGL(cfg_split_kernel, dim3(az_stream_grid((n + 3) / 4, 256)), dim3(256), 0, az_s(stream), v2, v, g, n);
   return az_launch_status();
 }
 

@@ -168,7 +168,8 @@ def _vjp_preconditioned(den: "Denoiser", x_t: Tensor, c_in: Tensor, c_out: Tenso
     if vjp is None:
         raise NotImplementedError(
             f"{type(den).__name__}: the backbone {type(backbone).__name__} has no input-gradient (vjp) path on the HIP kernels "
-            "(available: azula_amd.nn.UNet, UNetBlock, DiT, DiTBlock, MultiheadSelfAttention and TimeModulated around them); "
+            "(available: azula_amd.nn.UNet, UNetBlock, DiT, DiTBlock, MultiheadSelfAttention and TimeModulated around them, the ADM "
+            "plugin's UNetModel and the JiT plugin's JiT, also under CFGDenoiser); "
             "there is no torch fallback on device tensors")
     if get_module_dtype(backbone) not in (None, torch.float32):
         raise NotImplementedError(f"{type(den).__name__}: the input-gradient path takes fp32 backbones only")

@@ -801,12 +801,20 @@ class Builder:
                       fp.data_ptr(), fchunks, bpart.data_ptr(), nchunks, B, HW, x.C, x.cs, saved["groups"], saved["eps"])
         return self.wrote(y, bounded=False)
 
-    def row_norm_bwd(self, x: Act, g: Act, kind: int, *, scale=None, scale_off=0, bstride=0, res: Act | None = None, eps=1e-5) -> Act:
-        r"""Pullback of ``(1 + scale) * norm(x) + shift`` over the channel axis (kind 0: layer, unbiased variance; 1: rms), plus ``res``."""
+    def row_norm_bwd(self, x: Act, g: Act, kind: int, *, scale=None, scale_off=0, bstride=0, res: Act | None = None, eps=1e-5,
+                     weight: torch.Tensor | None = None) -> Act:
+        r"""Pullback of ``(1 + scale) * weight * norm(x) + shift`` over the channel axis (kind 0: layer, unbiased variance; 1: rms),
+        plus ``res``.  ``weight``: a learned per-channel gain (C floats on the device) -> ``az_rownorm_bwd_w_f32``."""
         y = self.new_act(x.B, x.H, x.W, x.C)
-        self.tape.add("az_rownorm_bwd_f32", y.ptr, x.ptr, g.ptr, res.ptr if res is not None else None,
-                      scale.data_ptr() + 4 * scale_off if scale is not None else None, bstride, x.B * x.H * x.W, x.H * x.W, x.C, x.cs,
-                      kind, eps, keep=[scale, x.buf])
+        sp = scale.data_ptr() + 4 * scale_off if scale is not None else None
+        rp = res.ptr if res is not None else None
+        if weight is None:
+            self.tape.add("az_rownorm_bwd_f32", y.ptr, x.ptr, g.ptr, rp, sp, bstride, x.B * x.H * x.W, x.H * x.W, x.C, x.cs,
+                          kind, eps, keep=[scale, x.buf])
+        else:
+            assert weight.numel() == x.C and weight.dtype == torch.float32
+            self.tape.add("az_rownorm_bwd_w_f32", y.ptr, x.ptr, g.ptr, rp, sp, bstride, weight.data_ptr(), x.B * x.H * x.W, x.H * x.W,
+                          x.C, x.cs, kind, eps, keep=[scale, x.buf, weight])
         return self.wrote(y, bounded=False)
 
     def zero_stuff(self, g: Act, sh: int, sw: int, H: int, W: int) -> Act:
@@ -857,13 +865,16 @@ class Builder:
         return m8, (m8.stride(0) if m.shape[0] > 1 else 0), (m8.stride(1) if m.shape[1] > 1 else 0)
 
     def attention_keep(self, qkv: Act, heads: int, qk_rmsnorm: bool, scale: float, eps: float = 1e-5, rope: tuple | None = None,
-                       mask: torch.Tensor | None = None, norm_dim: int = 0, order: str = "3HC", skip_prep: bool = False) -> tuple[Act, dict]:
+                       mask: torch.Tensor | None = None, norm_dim: int = 0, order: str = "3HC", skip_prep: bool = False,
+                       qk_weight: tuple | None = None) -> tuple[Act, dict]:
         r"""The forward of :meth:`attention` ('(n H C)' order, fp32) with what :meth:`attention_bwd` reads kept: q^ | k^ =
         rope(rms_norm(q | k)) go out of place into a buffer of their own (``az_qk_prep_f32``), then the forward attention entry
         :func:`choose_attention` picks runs on (q^, k^, v) with no norm and no tables.  Returns (out, record); ``qkv``, q^ | k^
         and ``out`` must stay alive for the pullback (the caller does not free them).  ``order``: the token layout of ``qkv`` as in
         :meth:`attention` ("3HC" / "nHC", or "H3C": guided-diffusion's legacy order).  ``skip_prep``: without RMS norm and RoPE
-        q^ = q and k^ = k, so the copy is skipped and the kernels read q and k where they lie (they take any strides)."""
+        q^ = q and k^ = k, so the copy is skipped and the kernels read q and k where they lie (they take any strides).
+        ``qk_weight = (wq, wk)``: learned gains of head_dim floats between the RMS norm and the rotation, as in :meth:`attention`
+        (``az_qk_prep_w_f32``); the record carries them to :meth:`attention_bwd`."""
         from ._lib import AzAttnArgs
 
         Cq = qkv.C // 3
@@ -878,13 +889,20 @@ class Builder:
         else:
             raise ValueError(order)
         cos, sin = rope if rope is not None else (None, None)
-        prep = not (skip_prep and not qk_rmsnorm and rope is None)
+        prep = not (skip_prep and not qk_rmsnorm and rope is None and qk_weight is None)
         qk = None
+        if qk_weight is not None:
+            assert all(w.numel() == dim and w.dtype == torch.float32 for w in qk_weight)
         if prep:
             qk = self.new_act(B, qkv.H, qkv.W, 2 * Cq, pinned=True)
-            self.tape.add("az_qk_prep_f32", qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0], qkv.ptr + 4 * offs[1], B, L, heads, dim,
-                          L * qkv.cs, qkv.cs, hs, L * qk.cs, qk.cs, dim, int(qk_rmsnorm), norm_dim, eps,
-                          cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None, keep=[qkv.buf, cos, sin])
+            args = (qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0], qkv.ptr + 4 * offs[1], B, L, heads, dim,
+                    L * qkv.cs, qkv.cs, hs, L * qk.cs, qk.cs, dim, int(qk_rmsnorm), norm_dim, eps,
+                    cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None)
+            if qk_weight is None:
+                self.tape.add("az_qk_prep_f32", *args, keep=[qkv.buf, cos, sin])
+            else:
+                self.tape.add("az_qk_prep_w_f32", *args, qk_weight[0].data_ptr(), qk_weight[1].data_ptr(),
+                              keep=[qkv.buf, cos, sin, *qk_weight])
             self.wrote(qk, bounded=False)
         out = self.new_act(B, qkv.H, qkv.W, Cq)
         a = AzAttnArgs()
@@ -902,11 +920,11 @@ class Builder:
         a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
         a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, 0, eps, 0
         rec = dict(qkv=qkv, qk=qk, out=out, heads=heads, dim=dim, scale=scale, eps=eps, rms=bool(qk_rmsnorm), norm_dim=norm_dim,
-                   rope=rope, mask=None, offs=offs, hs=hs)
+                   rope=rope, mask=None, offs=offs, hs=hs, qk_weight=qk_weight)
         if mask is not None:
             m8, mb, mh = rec["mask"] = self._attn_mask(mask, B, heads, L)
             a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
-        kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, None) if qk_rmsnorm else (math.inf, math.inf)
+        kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, qk_weight) if qk_rmsnorm else (math.inf, math.inf)
         a._flops = 4 * B * heads * L * L * dim
         self.tape.add(choose_attention(dim, kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX, None), C.byref(a),
                       keep=[a, qk.buf if prep else qkv.buf])
@@ -943,11 +961,15 @@ class Builder:
         self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qk.buf, qkv.buf, out.buf, rec["mask"]])
         self.wrote(dqk, bounded=False)
         cos, sin = rec["rope"] if rec["rope"] is not None else (None, None)
-        self.tape.add("az_qk_prep_bwd_f32", dqkv.ptr + 4 * offs[0], dqkv.ptr + 4 * offs[1], dqk.ptr, dqk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0],
-                      qkv.ptr + 4 * offs[1], B, L, heads,
-                      dim, L * dqk.cs, dqk.cs, dim, L * qkv.cs, qkv.cs, hs, L * dqkv.cs, dqkv.cs, hs, int(rec["rms"]), rec["norm_dim"],
-                      rec["eps"], cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None,
-                      keep=[cos, sin])
+        args = (dqkv.ptr + 4 * offs[0], dqkv.ptr + 4 * offs[1], dqk.ptr, dqk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0],
+                qkv.ptr + 4 * offs[1], B, L, heads,
+                dim, L * dqk.cs, dqk.cs, dim, L * qkv.cs, qkv.cs, hs, L * dqkv.cs, dqkv.cs, hs, int(rec["rms"]), rec["norm_dim"],
+                rec["eps"], cos.data_ptr() if cos is not None else None, sin.data_ptr() if sin is not None else None)
+        gains = rec.get("qk_weight")
+        if gains is None:
+            self.tape.add("az_qk_prep_bwd_f32", *args, keep=[cos, sin])
+        else:
+            self.tape.add("az_qk_prep_bwd_w_f32", *args, gains[0].data_ptr(), gains[1].data_ptr(), keep=[cos, sin, *gains])
         self.free(dqk)
         return self.wrote(dqkv, bounded=False)
 

@@ -15,5 +15,6 @@ def mean_and_pullback(denoiser: Denoiser, x_t: Tensor, t: Tensor, kwargs: dict):
     if vjp is None:
         raise NotImplementedError(
             f"{type(denoiser).__name__} has no input-gradient path (_az_vjp): KarrasDenoiser / SimpleDenoiser around an "
-            "azula_amd.nn.UNet or DiT, and the ADM plugin's AblatedDenoiser, provide it")
+            "azula_amd.nn.UNet or DiT, the ADM plugin's AblatedDenoiser, the JiT plugin's JITDenoiser, and CFGDenoiser around the "
+            "last two, provide it")
     return vjp(x_t, t, **kwargs)

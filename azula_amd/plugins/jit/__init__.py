@@ -65,6 +65,25 @@ class JITDenoiser(Denoiser):
         output = self.backbone(x_in.to(dtype), c_time.to(dtype), y=label.expand(B), **kwargs).to(x_t)
         return DiracPosterior(mean=output)
 
+    # -- input gradient (azula_amd internal: the guidance classes that need d mean / d x_t) ------------------------
+    @torch.no_grad()
+    @_lib.on_device
+    def _az_vjp(self, x_t: Tensor, t: Tensor, label: Tensor | None = None):
+        r"""``(mean, pullback)`` with ``pullback(v) = (d mean / d x_t)^T v = c_in J_F^T v``: the backbone's HIP pullback
+        (``JiT.vjp``) behind the preconditioning kernel.  A missing label is the null class, as in ``forward``; the label is a
+        scalar or one per sample, ``t`` a scalar or one time per sample."""
+        from ...denoise import _vjp_preconditioned
+
+        if not x_t.is_cuda:
+            raise NotImplementedError("JITDenoiser: the input-gradient path runs on device tensors only (CPU tensors have none)")
+        alpha_t, sigma_t = self.schedule(t)
+        alpha_t, sigma_t = _expand_like(alpha_t, x_t.ndim), _expand_like(sigma_t, x_t.ndim)
+        c_in, c_time = jit_coefficients(alpha_t, sigma_t)
+        if label is None:
+            label = torch.as_tensor(self.num_classes, device=x_t.device)
+        label = torch.as_tensor(label).reshape(-1).expand(x_t.shape[0])
+        return _vjp_preconditioned(self, x_t, c_in.to(x_t.device), None, None, c_time.flatten(), {"y": label})
+
     # -- fused sampling -------------------------------------------------------------------------
     def host_coefficients(self, alpha_t: Tensor, sigma_t: Tensor) -> dict:
         c_in, c_time = jit_coefficients(alpha_t, sigma_t)

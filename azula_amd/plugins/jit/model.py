@@ -17,20 +17,24 @@ same kernels as ``azula_amd.nn.vit``:
 * the in-context class tokens are prepended by two token-window kernels at ``in_context_start`` and dropped
   before the final layer; the final linear's rows are permuted at build time from the model's (p, q, c)
   feature order to the unpatchify kernel's (c, p, q).
+
+``JiT.vjp`` is the input gradient on a plan of its own (:class:`JiTGradPlan`); ``JiTPlan`` does not change.
 """
 
 from __future__ import annotations
 
 import math
+import weakref
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder
+from ...engine import Act, Builder, LinearView
+from ...nn.unet import _GradTapes
 
-__all__ = ["JiT", "JiT_models"]
+__all__ = ["JiT", "JiTGradPlan", "JiT_models"]
 
 
 class _Gain(nn.Module):
@@ -267,6 +271,217 @@ class JiTPlan:
         self.tape = tape
 
 
+class JiTGradPlan(_GradTapes):
+    r"""Gradient plan of a :class:`JiT` for one (batch, shared/per-sample time) signature, alongside ``DiTGradPlan``: the
+    forward-keep tape (the order of :class:`JiTPlan`, nothing the pullback reads released) and the backward tape, on planar
+    (B, C, S, S) buffers.  ``t`` and ``y`` are constants of the pullback, so the modulation table is one.
+
+    Kept per block: the block input (``norm1``'s pullback), the attention record -- raw qkv, q^ | k^ from ``az_qk_prep_w_f32``
+    (the qkv projection runs without its q / k epilogue), the attention output --, ``x2`` (``norm2``) and the w12
+    pre-activation (SwiGLU is a pass of its own behind it, the w12 rows interleaved as in the forward plan).  The backward tape
+    reads a block right to left: gate, w3 and w12 data gradients around ``az_swiglu_bwd_f32``, ``az_rownorm_bwd_w_f32`` with
+    ``res = g``; gate, proj data gradient, ``az_attention_bwd_f32`` + ``az_qk_prep_bwd_w_f32``, qkv data gradient,
+    ``az_rownorm_bwd_w_f32`` with the residual path's cotangent as ``res``.  The class tokens do not depend on x: where they
+    join, the cotangent drops their rows; where they leave, it is copied behind zeroed rows.  Unpatchify and patchify are each
+    other's adjoints.  Plain ``Tape.run``, no graph capture; ``saved_bytes`` reports the pool."""
+
+    def __init__(self, net: "JiT", B: int, t_shared: bool, device) -> None:
+        Hd, heads, p, Z = net.hidden_size, net.num_heads, net.patch_size, net.in_channels
+        S = net.input_size
+        super().__init__(device, B, Z, Z, S, S, 0, 0, net._param_versions())
+        self._net = weakref.ref(net)
+        bld = self.bld
+        grid = S // p
+        L, Lc = grid * grid, net.in_context_len
+        hd = Hd // heads
+        depth = len(net.blocks)
+        start = net.in_context_start
+        joins = bool(Lc) and start < depth  # (the class tokens enter the sequence at block `start`)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.t = torch.zeros(1 if t_shared else B, **f32)
+        self.labels = torch.zeros(B, dtype=torch.int64, device=device)
+        tape = bld.tape
+
+        # ---- conditioning, as JiTPlan: constants of the pullback
+        F_ = net.t_embedder.frequency_embedding_size
+        m0, m2 = net.t_embedder.mlp[0], net.t_embedder.mlp[2]
+        table = net.y_embedder.embedding_table.weight
+        freq, hid, t_emb, y_emb, c = (bld.empty(B, n) for n in (F_, Hd, Hd, Hd, Hd))
+        ones = bld.const(torch.ones(1))
+        tape.add("az_timestep_embedding_f32", freq.data_ptr(), F_, self.t.data_ptr(), 0 if t_shared else 1, B, F_ // 2, 10000.0)
+        bld.linear_small(hid, Hd, freq, F_, bld.const(m0.weight), bld.const(m0.bias), B, Hd, F_, 0, 1)
+        bld.linear_small(t_emb, Hd, hid, Hd, bld.const(m2.weight), bld.const(m2.bias), B, Hd, Hd, 0, 0)
+        tape.add("az_gather_rows_f32", y_emb.data_ptr(), bld.const(table).data_ptr(), self.labels.data_ptr(), B, Hd, table.shape[0])
+        tape.add("az_axpby_f32", c.data_ptr(), ones.data_ptr(), t_emb.data_ptr(), ones.data_ptr(), y_emb.data_ptr(), 1, B * Hd, 0)
+        heads_ = [blk.adaLN_modulation[1] for blk in net.blocks] + [net.final_layer.adaLN_modulation[1]]
+        w_all = torch.cat([m.weight.detach() for m in heads_]).to(device)
+        b_all = torch.cat([m.bias.detach() for m in heads_]).to(device)
+        c_act = Act(bld.empty(B * Hd), 1, B, 1, Hd, Hd, True)
+        tape.add("az_silu_f32", c_act.ptr, c.data_ptr(), B * Hd)
+        bld.wrote(c_act, bounded=False)
+        mods = bld.conv(c_act, bld.pack_conv(w_all, b_all), w_all.shape[0], out_f32=True)
+        mods.pinned = True
+        mod, MS = mods.buf, mods.cs
+
+        # ---- forward-keep
+        e = net.x_embedder
+        tokens = bld.new_act(B, L, 1, Z * p * p, pinned=True)
+        tape.add("az_patchify_f32", tokens.ptr, self.x_in.data_ptr(), None, B, Z, S, S, p, tokens.cs)
+        bld.wrote(tokens, bounded=False)
+        w1 = LinearView(e.proj1.weight)
+        w2 = LinearView(e.proj2.weight)
+        low = bld.conv(tokens, bld.pack_conv(e.proj1.weight.detach().reshape(e.proj1.out_channels, -1), None), e.proj1.out_channels)
+        pos = Act(bld.const(net.pos_embed.detach().reshape(-1)), 1, L, 1, Hd, Hd, True)
+        x = bld.conv(low, bld.pack_conv(e.proj2.weight.detach().reshape(Hd, -1), e.proj2.bias), Hd, res=_Shared(pos))
+        bld.free(low)
+
+        hdp = engine.attn_grad_padded_dim(hd)
+
+        def rope_tables(ctx: int) -> tuple:
+            cos, sin = rotary_tables(hd, heads, grid, ctx)
+            if hdp != hd:  # padded pairs do not turn
+                cos = torch.cat([cos, cos.new_ones(*cos.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
+                sin = torch.cat([sin, sin.new_zeros(*sin.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
+            return bld.const(cos), bld.const(sin)
+
+        rope_img = rope_tables(0)
+        rope_ctx = rope_tables(Lc) if Lc else rope_img
+        recs = []
+        for i, blk in enumerate(net.blocks):
+            if joins and i == start:
+                wide = bld.new_act(B, L + Lc, 1, Hd)
+                ctx_pos = bld.const(net.in_context_posemb.detach().reshape(-1))
+                tape.add("az_token_fill_f32", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd)
+                tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd)
+                bld.wrote(wide, bounded=False)
+                bld.free(x)  # (no pullback reads the narrow copy)
+                x = wide
+            m0_ = 6 * Hd * i  # shift_a | scale_a | gate_a | shift_m | scale_m | gate_m
+            at = blk.attn
+            norm1, norm2 = bld.const(blk.norm1.weight), bld.const(blk.norm2.weight)
+            n1 = bld.row_norm(x, 1, weight=norm1, scale=mod, shift=mod, scale_off=m0_ + Hd, shift_off=m0_, bstride=MS, eps=1e-6)
+            if hdp != hd:  # zero-padded heads: gain 1 on the pad lanes, the padded projections of the forward plan
+                pad1 = torch.ones(hdp - hd)
+                gains = tuple(bld.const(torch.cat([w_.detach().float().cpu(), pad1])) for w_ in (at.q_norm.weight, at.k_norm.weight))
+                wq, bq = engine.pad_qkv_heads(at.qkv.weight, at.qkv.bias, heads, hd, hdp, "3HC")
+                wp = engine.pad_proj_heads(at.proj.weight, heads, hd, hdp)
+            else:
+                gains = (bld.const(at.q_norm.weight), bld.const(at.k_norm.weight))
+                wq, bq, wp = at.qkv.weight.detach(), at.qkv.bias, at.proj.weight.detach()
+            qkv = bld.conv(n1, bld.pack_conv(wq, bq), 3 * heads * hdp)
+            bld.free(n1)
+            att, arec = bld.attention_keep(qkv, heads, True, 1.0 / math.sqrt(hd), eps=1e-6, rope=rope_img if i < start else rope_ctx,
+                                           norm_dim=hd if hdp != hd else 0, order="3HC", qk_weight=gains)
+            x2 = bld.conv(att, bld.pack_conv(wp, at.proj.bias), Hd, gate=mod, gate_off=m0_ + 2 * Hd, gate_bstride=MS, res=x)
+            n2 = bld.row_norm(x2, 1, weight=norm2, scale=mod, shift=mod, scale_off=m0_ + 4 * Hd, shift_off=m0_ + 3 * Hd, bstride=MS,
+                              eps=1e-6)
+            w12, b12 = blk.mlp.w12.weight.detach(), blk.mlp.w12.bias.detach()
+            half = w12.shape[0] // 2  # pair (x2_c, x1_c): silu(x1) * x2 (_src/model.py:159-162)
+            w12i = torch.stack((w12[half:], w12[:half]), dim=1).reshape(2 * half, -1).contiguous()
+            b12i = torch.stack((b12[half:], b12[:half]), dim=1).reshape(-1).contiguous()
+            h = bld.conv(n2, bld.pack_conv(w12i, b12i), 2 * half)
+            bld.free(n2)
+            glu = bld.swiglu(h)
+            out = bld.conv(glu, bld.pack_conv(blk.mlp.w3.weight, blk.mlp.w3.bias), Hd, gate=mod, gate_off=m0_ + 5 * Hd,
+                           gate_bstride=MS, res=x2)
+            bld.free(glu)
+            recs.append(dict(x=x, attn=arec, x2=x2, h=h, m0=m0_, norm1=norm1, norm2=norm2, wqkv=LinearView(wq), wproj=LinearView(wp),
+                             w12=LinearView(w12i), w3=LinearView(blk.mlp.w3.weight)))
+            x = out
+        if joins:  # x[:, in_context_len:]
+            body = bld.new_act(B, L, 1, Hd)
+            tape.add("az_token_copy_f32", body.ptr, L, 0, x.ptr, L + Lc, Lc, L, B, Hd)
+            bld.wrote(body, bounded=False)
+            bld.free(x)
+            x = body
+        fl = net.final_layer
+        mf = 6 * Hd * depth  # shift | scale
+        norm_f = bld.const(fl.norm_final.weight)
+        n = bld.row_norm(x, 1, weight=norm_f, scale=mod, shift=mod, scale_off=mf + Hd, shift_off=mf, bstride=MS, eps=1e-6)
+        x_last = x  # (kept: norm_final's pullback reads it)
+        wl = fl.linear.weight.detach().reshape(p * p, Z, Hd).transpose(0, 1).reshape(Z * p * p, Hd).contiguous()
+        bl = fl.linear.bias.detach().reshape(p * p, Z).t().reshape(-1).contiguous()
+        o = bld.conv(n, bld.pack_conv(wl, bl), Z * p * p, out_f32=True)
+        bld.free(n)
+        tape.add("az_unpatchify_f32", self.out.data_ptr(), o.ptr, B, Z, S, S, p, o.cs)
+        bld.free(o)
+        self.end_forward([])
+
+        # ---- backward
+        tape = bld.tape
+        cache: dict = {}
+        wlv = LinearView(wl)
+        tape.keep.extend([wlv, w1, w2, mods] + [r[k] for r in recs for k in ("wqkv", "wproj", "w12", "w3")])
+        g = bld.new_act(B, L, 1, Z * p * p)
+        tape.add("az_patchify_f32", g.ptr, self.v_in.data_ptr(), None, B, Z, S, S, p, g.cs)  # (the unpatchify's adjoint)
+        bld.wrote(g, bounded=False)
+        gn = bld.conv_dgrad(g, wlv, cache=cache)
+        bld.free(g)
+        g = bld.row_norm_bwd(x_last, gn, 1, scale=mod, scale_off=mf + Hd, bstride=MS, eps=1e-6, weight=norm_f)
+        bld.free(gn)
+        if joins:  # the slice's adjoint: zero rows for the class tokens (a launch of its own: the pool reuses the buffer)
+            gw = bld.new_act(B, L + Lc, 1, Hd)
+            zrow, zpos = bld.const(torch.zeros(Hd)), bld.const(torch.zeros(Lc * Hd))
+            tape.add("az_token_fill_f32", gw.ptr, L + Lc, 0, Lc, zrow.data_ptr(), 0, zpos.data_ptr(), B, Hd, keep=[zrow, zpos])
+            tape.add("az_token_copy_f32", gw.ptr, L + Lc, Lc, g.ptr, L, 0, L, B, Hd)
+            bld.wrote(gw, bounded=False)
+            bld.free(g)
+            g = gw
+        for i in range(depth - 1, -1, -1):
+            r = recs[i]
+            m0_ = r["m0"]
+            g2 = bld.channel_scale(g, mod, m0_ + 5 * Hd, MS)
+            g3 = bld.conv_dgrad(g2, r["w3"], cache=cache)
+            bld.free(g2)
+            g4 = bld.swiglu_bwd(g3, r["h"])
+            bld.free(g3)
+            g5 = bld.conv_dgrad(g4, r["w12"], cache=cache)
+            bld.free(g4)
+            gx2 = bld.row_norm_bwd(r["x2"], g5, 1, scale=mod, scale_off=m0_ + 4 * Hd, bstride=MS, res=g, eps=1e-6, weight=r["norm2"])
+            bld.free(g5)
+            bld.free(g)
+            g6 = bld.channel_scale(gx2, mod, m0_ + 2 * Hd, MS)
+            g7 = bld.conv_dgrad(g6, r["wproj"], cache=cache)
+            bld.free(g6)
+            g8 = bld.attention_bwd(g7, r["attn"])
+            bld.free(g7)
+            g9 = bld.conv_dgrad(g8, r["wqkv"], cache=cache)
+            bld.free(g8)
+            g = bld.row_norm_bwd(r["x"], g9, 1, scale=mod, scale_off=m0_ + Hd, bstride=MS, res=gx2, eps=1e-6, weight=r["norm1"])
+            bld.free(g9)
+            bld.free(gx2)
+            if joins and i == start:  # the class tokens do not depend on x: their rows of the cotangent are dropped
+                gb = bld.new_act(B, L, 1, Hd)
+                tape.add("az_token_copy_f32", gb.ptr, L, 0, g.ptr, L + Lc, Lc, L, B, Hd)
+                bld.wrote(gb, bounded=False)
+                bld.free(g)
+                g = gb
+        glow = bld.conv_dgrad(g, w2, cache=cache)
+        bld.free(g)
+        gt = bld.conv_dgrad(glow, w1, cache=cache)
+        bld.free(glow)
+        tape.add("az_unpatchify_f32", self.dx.data_ptr(), gt.ptr, B, Z, S, S, p, gt.cs)  # (the patchify's adjoint)
+        bld.free(gt)
+        self.end_backward()
+
+    def run_jit(self, x: Tensor, t: Tensor, y: Tensor):
+        self.t.copy_(t.to(device=x.device, dtype=torch.float32))
+        self.labels.copy_(y.to(device=x.device, dtype=torch.int64).expand(self.labels.shape[0]))
+        out, pull = self.run(x, None)
+        net = self._net
+
+        def pullback(v: Tensor) -> Tensor:
+            # the tapes read the norm gains, biases and tables where the module keeps them, the GEMM weights from packed copies:
+            # after an in-place parameter change the saved tensors no longer belong to what the backward tape would read
+            m = net()
+            if m is None or m._param_versions() != self.versions:
+                raise RuntimeError("this pullback belongs to an earlier vjp call: the module's parameters have changed since, "
+                                   "and its saved tensors belong to the old ones")
+            return pull(v)
+
+        return out, pullback
+
+
 class _Shared:
     r"""Marks a residual as batch-shared (``Builder.conv`` epilogue ``res_bcast``)."""
 
@@ -358,6 +573,29 @@ class JiT(nn.Module):
         if p is None or p.versions != self._param_versions():
             p = self._plans[key] = JiTPlan(self, B, t_shared, device)
         return p
+
+    # -- input gradient --------------------------------------------------------------------------------------------
+    def grad_plan(self, B: int, t_shared: bool, device) -> JiTGradPlan:
+        key = ("vjp", B, t_shared, str(device))
+        p = self._plans.get(key)
+        if p is None or p.versions != self._param_versions():
+            p = self._plans[key] = JiTGradPlan(self, B, t_shared, device)
+        return p
+
+    @torch.no_grad()
+    @_lib.on_device
+    def vjp(self, x: Tensor, t: Tensor, y: Tensor):
+        r"""``(out, pullback)``: ``out = self(x, t, y)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``): the input gradient
+        that ``azula.guidance`` takes from ``torch.autograd``, on HIP tapes (:class:`JiTGradPlan`).  ``t`` and ``y`` are constants
+        of the pullback; it may be called any number of times until the next ``vjp`` with the same signature.  Scope: fp32
+        parameters and fp32 device tensors; anything else raises ``NotImplementedError`` (the forward is not affected)."""
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            raise NotImplementedError("JiT.vjp: fp32 parameters and tensors only (half-precision modules have no input-gradient plan)")
+        if not x.is_cuda:
+            raise NotImplementedError("JiT.vjp: device tensors only (CPU tensors have no input-gradient path)")
+        self._check(x)
+        t = t.reshape(-1)
+        return self.grad_plan(x.shape[0], t.numel() == 1, x.device).run_jit(x.contiguous(), t, y)
 
     def _check(self, x: Tensor) -> torch.dtype:
         from ...nn.utils import backbone_io_dtype

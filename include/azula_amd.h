@@ -323,6 +323,14 @@ int az_axpby_f32(float* y, const float* a_dev, const float* x, const float* b_de
  * sampler (azula/guidance/cfg.py:63-65), same association and rounding as the reference.   */
 int az_cfg_combine_f32(float* y, const float* pos, const float* neg, const float* g_dev, int64_t n,
                        az_stream_t stream);
+/* The adjoint of that combine for a guided mean evaluated as ONE pass over the stacked batch [x_t ; x_t] (positive labels |
+ * negative labels): m = (1 + g) m+ - g m-, so the cotangent of the stacked means is
+ *   v2[0:n] = (1.0f + g[0]) * v,   v2[n:2n] = -g[0] * v      (in this op order; g in device memory),
+ * what torch.autograd records behind azula/guidance/cfg.py:63-65 under the gradient methods of azula/guidance/dps.py:55-68 and
+ * mmps.py:69-90.  Any n > 0: float4 body, scalar tail (and scalar stores to the second half when n % 4 != 0); v2 and v 16-byte
+ * aligned.  The sum of the two halves of the pulled-back cotangent is az_axpby_f32.  12 B / element, HBM-bound; no time has been
+ * measured for it.                                                                                                         */
+int az_cfg_split_f32(float* v2, const float* v, const float* g_dev, int64_t n, az_stream_t stream);
 
 /* ------------------------------------------------------------------ layout
  * NCHW (B,C,H,W) -> NHWC with channel stride cs (>= C, multiple of 4), scaled by *scale_dev
@@ -356,6 +364,14 @@ int az_groupnorm_bwd_apply_f32(float* dx, const float* x, const float* g, const 
  * dx = res + rstd (q - mean(q) - xh mean(q xh) C / (C - 1)); RMSNorm, kind 1: dx = res + rstd (q - xh mean(q xh)), xh = x rstd). */
 int az_rownorm_bwd_f32(float* dx, const float* x, const float* g, const float* res, const float* scale, int64_t scale_bstride,
                        int64_t rows, int64_t rows_per_batch, int64_t C, int64_t cs, int32_t kind, float eps, az_stream_t stream);
+/* The same pass with a learned per-channel gain under the modulation: the pullback of y = (1 + scale[b, c]) weight[c] norm(x) + shift
+ * (the RMSNorm modules of plugins/jit/_src/util.py:149-157 inside modulate(), plugins/jit/_src/model.py:175-177,199-201), i.e. the
+ * formulas above with q = g weight (1 + scale).  `weight`: C floats, NULL = none -- then the launch is az_rownorm_bwd_f32's own,
+ * bit for bit.  Kinds 0 and 1, same `res`, strides, zero pad lanes and determinism.  16 B / element (+ 4 B / element with `res`):
+ * HBM-bound; no time has been measured for it.                                                                              */
+int az_rownorm_bwd_w_f32(float* dx, const float* x, const float* g, const float* res, const float* scale, int64_t scale_bstride,
+                         const float* weight, int64_t rows, int64_t rows_per_batch, int64_t C, int64_t cs, int32_t kind, float eps,
+                         az_stream_t stream);
 /* y = g * silu'(p), silu'(p) = s (1 + p (1 - s)), s = 1 / (1 + exp(-p)), on the PRE-activation p (the nn.SiLU between the two
  * convolutions of azula/nn/unet.py:76-83); n % 4 == 0; y may alias g.                                                        */
 int az_silu_bwd_f32(float* y, const float* g, const float* p, int64_t n, az_stream_t stream);
@@ -816,6 +832,21 @@ int az_qk_prep_bwd_f32(float* dq, float* dk, const float* dq_hat, const float* d
                        int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride, int64_t out_tstride,
                        int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
                        const float* rope_sin, az_stream_t stream);
+/* The same pair with learned gains between the RMS norm and the rotation (q_norm.weight / k_norm.weight of
+ * plugins/jit/_src/model.py:112-134 with plugins/jit/_src/util.py:100-157): forward q^ = rope(w_q rms_norm(q)); backward
+ * u = R^T g, qg = w u, dx = r (qg - xh mean(qg xh)), xh = x r, means over norm_dim, r recomputed from the kept raw q / k.
+ * q_weight / k_weight: head_dim floats each, 16-byte aligned, NULL = gain 1; zero-padded heads carry gain 1 (and cos 1, sin 0) on
+ * the pad lanes.  With both NULL the launches are those of the entries above, bit for bit.  8 B / element forward, 12 B /
+ * element backward (+ tables and gains): HBM-bound; no time has been measured for them.                                  */
+int az_qk_prep_w_f32(float* q_hat, float* k_hat, const float* q, const float* k, int64_t batch, int64_t tokens, int32_t heads,
+                     int32_t head_dim, int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride,
+                     int64_t out_tstride, int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
+                     const float* rope_sin, const float* q_weight, const float* k_weight, az_stream_t stream);
+int az_qk_prep_bwd_w_f32(float* dq, float* dk, const float* dq_hat, const float* dk_hat, const float* q, const float* k, int64_t batch,
+                         int64_t tokens, int32_t heads, int32_t head_dim, int64_t g_bstride, int64_t g_tstride, int64_t g_hstride,
+                         int64_t in_bstride, int64_t in_tstride, int64_t in_hstride, int64_t out_bstride, int64_t out_tstride,
+                         int64_t out_hstride, int32_t qk_rmsnorm, int32_t norm_dim, float eps, const float* rope_cos,
+                         const float* rope_sin, const float* q_weight, const float* k_weight, az_stream_t stream);
 /* az_attention_bwd_f32: with P = softmax(scale q^ k^T + mask), out = P v and dout the cotangent of out,
  *   Delta_t = sum_c dout_tc out_tc,  dv = P^T dout,  dP = dout v^T,  dS = P o (dP - Delta),  dq^ = scale dS k^,  dk^ = scale dS^T q^.
  * Three launches: row statistics (the log-sum-exp is recomputed by online softmax -- the forward entries do not export it -- and
