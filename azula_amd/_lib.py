@@ -422,6 +422,8 @@ PROTOTYPES: dict[str, list] = {
     "az_nchw_to_nhwc_f32": [vp, vp, vp, i64, i64, i64, i64, c_stream],
     "az_nhwc_to_nchw_f32": [vp, vp, i64, i64, i64, i64, c_stream],
     "az_upsample_nearest_f32": [vp, vp, i64, i64, i64, i64, i32, i32, i64, i64, c_stream],
+    "az_fourier_planes_f32": [vp, i64, i64, i64, i64, vp, i32, vp, i64, i32, c_stream],
+    "az_upsample_bilinear2x_f32": [vp, vp, i64, i64, i64, i64, c_stream],
     "az_groupnorm_bwd_stats_f32": [vp, vp, vp, vp, i64, vp, i32, i64, i64, i64, i64, i32, i32, f32, c_stream],
     "az_groupnorm_bwd_apply_f32": [vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, i64, i64, i64, i64, i32, f32, c_stream],
     "az_rownorm_bwd_f32": [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, f32, c_stream],

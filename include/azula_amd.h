@@ -343,6 +343,24 @@ int az_nchw_to_nhwc_f32(float* dst, const float* src, const float* scale_dev, in
 int az_upsample_nearest_f32(float* dst, const float* src, int64_t B, int64_t Hin, int64_t Win, int64_t cs, int32_t sh,
                             int32_t sw, int64_t Hout, int64_t Wout, az_stream_t stream);
 
+/* ------------------------------------------------------------------ v-diffusion backbones (csrc/vdm.hip)
+ * az_fourier_planes_f32 replaces azula/plugins/vdm/_src/imagenet_128.py:63-75,186-189 (FourierFeatures.forward,
+ * expand_to_planes and the torch.cat in front of the stem; yfcc_1.py:43-52,73-75,213-215 alike): for every pixel of the NHWC tensor
+ * dst (B, HW, cs) it writes channels [c_lo, c_lo + 2 nfeat_half): cos(2 pi u w_j) for j < nfeat_half, then sin(2 pi u w_j), with
+ * u = t (mode 0: the yfcc models) or u = log(cos^2(t pi / 2) / sin^2(t pi / 2)) (mode 1: _src/utils.py:51-61) and
+ * t = t_dev[b * t_stride] on the DEVICE -- t_stride 0: one scalar for the batch (AzStepCoef.c_time of the current step inside a
+ * captured graph), 1: one time per sample.  Every other channel is left as it is.  `weight`: nfeat_half floats.  Evaluated in
+ * fp64 from the fp32 time and weights and rounded once (log(cos^2 / sin^2) is ill conditioned near t = 1; a thread evaluates its
+ * features once for all its pixels): within 16 * 2^-24 * (1 + |2 pi u w|) of the exact value.  1 <= nfeat_half <= 32, cs % 4 == 0, c_lo + 2 nfeat_half <= cs, B <= 65535 (else AZ_E_SHAPE); dst 16-byte aligned.
+ *
+ * az_upsample_bilinear2x_f32 replaces nn.Upsample(scale_factor=2, mode="bilinear", align_corners=False) of yfcc_1.py:157-159:
+ * NHWC src (B, H, W, cs) -> dst (B, 2H, 2W, cs) with ATen's taps (weights 0.25 / 0.75 per axis, 1 / 0 on the first row and
+ * column, indices clamped at the far border); within 2^-22 * max |src| of the exact value.  cs % 4 == 0, dst != src, both 16-byte
+ * aligned.                                                                                                                    */
+int az_fourier_planes_f32(float* dst, int64_t B, int64_t HW, int64_t cs, int64_t c_lo, const float* weight, int32_t nfeat_half,
+                          const float* t_dev, int64_t t_stride, int32_t mode, az_stream_t stream);
+int az_upsample_bilinear2x_f32(float* dst, const float* src, int64_t B, int64_t H, int64_t W, int64_t cs, az_stream_t stream);
+
 /* ------------------------------------------------------------------ input gradient (csrc/backward.hip)
  * The passes of a vector-Jacobian product v -> (d out / d x)^T v through the UNet that are not convolutions -- what
  * torch.autograd records behind azula/guidance/dps.py:55-68, pgdm.py:57-67, tmpd.py:55-71 and mmps.py:69-90 for the layers of
