@@ -474,6 +474,7 @@ PROTOTYPES: dict[str, list] = {
     "az_winograd_pack_filter_x3_f32": [vp, vp, i32, i32, i32, i32, i32, i32, c_stream],
     "az_winograd_x3_choose_block": [i32, i32, i32, i32, vp, vp, vp, vp],
     "az_winograd_x3_block_geometry": [i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "az_winograd_x3_structured_mask": [C.POINTER(AzConvArgs), vp, vp],
     "az_conv2d_f16x2_f32": [C.POINTER(AzConvArgs), c_stream],
     "az_conv2d_winograd_f16x2_f32": [C.POINTER(AzConvArgs), c_stream],
     "az_pack_conv_weight_f16x2_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, c_stream],

@@ -3037,6 +3037,24 @@ int az_winograd_x3_block_geometry(int32_t batch, int32_t hin, int32_t win, int32
   return g.nslots;
 }
 
+// The mask a launch passes to the kernel: the rule (conv_shared.h: x3_structured_mask), unless AZ_X3_UPS=0 empties it (A/B runs
+// and the bit-equality tests, read per call, honoured under AZ_DEBUG_AB like AZ_X3_BLOCK: the kernels without UPS then run).
+static int x3_launch_mask(const AzConvArgs& a) {
+  if (const char* e = az_ab_env("AZ_X3_UPS"))
+    if (e[0] == '0') return 0;
+  return x3_structured_mask(a);
+}
+
+/* Host only (no device is touched): which sources of a Winograd x3 / f16x2 launch described by `args` are structured -- read
+ * through nearest upsampling in a way that makes 7 of the 16 frequencies exact zeros (bit 0: src0, bit 1: src1) -- by the rule
+ * alone (`mask`) and as a launch made now would pass it to the kernel (`launch_mask`: the A/B switch applied). */
+int az_winograd_x3_structured_mask(const AzConvArgs* a, int32_t* mask, int32_t* launch_mask) {
+  AZ_REQUIRE(a && mask && launch_mask, AZ_E_NULL);
+  *mask = x3_structured_mask(*a);
+  *launch_mask = x3_launch_mask(*a);
+  return AZ_OK;
+}
+
 static int winograd_x3_entry(const AzConvArgs* a, az_stream_t stream, bool h2) {
   WinoP p;
   int splitk = 1;
@@ -3062,6 +3080,7 @@ static int winograd_x3_entry(const AzConvArgs* a, az_stream_t stream, bool h2) {
       wino_order(p, 16);
     }
   }
+  p.ups = x3_launch_mask(p.a);
   if (h2) AZ_REQUIRE(conv_pow2(a->w_scale), AZ_E_SHAPE);
   p.out_scale = h2 ? 1.f / a->w_scale : 1.f;
   if (h2) AZ_REQUIRE(AZ_ALIGNED16(a->in_absmax0) && AZ_ALIGNED16(a->in_absmax1) && (a->in_absmax0 || !a->in_absmax1), AZ_E_ALIGN);
@@ -3167,6 +3186,7 @@ static int wino_prepare(const AzConvArgs* a, int wk, int64_t ustage_bytes, WinoP
   p.cblocks = (a->cout_s + WC - 1) / WC;
   p.tblocks = (p.ntiles + WT - 1) / WT;
   p.rect_w = WT, p.rect_h = 1;
+  p.ups = 0;
   wino_order(p, wk);
   AZ_REQUIRE((int64_t)p.nk * p.cblocks * ustage_bytes <= (1ll << 31), AZ_E_SHAPE);
   return AZ_OK;

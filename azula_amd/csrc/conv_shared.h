@@ -440,6 +440,27 @@ __host__ __device__ __forceinline__ bool x3_rect_tile(const X3RectGeom& g, int j
   return th < tiles_h && tw < tiles_w;
 }
 
+// ---- Structured sources of the x3 / f16x2 Winograd kernel (wino_x3.hip, template parameter UPS; WinoP.ups).  A source read
+// through nearest upsampling (shift >= 1 on both axes) hands patch rows 1 and 2 of every tile the SAME low-resolution row
+// (input rows 2 th and 2 th + 1), and likewise columns 1 and 2.  B^T d = [d0 - d2, d1 + d2, d2 - d1, d1 - d3] with d1 == d2 bit
+// for bit is [a - b, 2 b, +0, b - c]: frequency index 2 is exactly +0 in both directions, 7 of the 16 frequencies (xi = 2 for
+// any nu, nu = 2 for any xi).  They add +0 to accumulators that start at +0, so leaving them out changes no output bit for
+// finite filters.  The rule, per source:
+//   * not anisotropic, shift >= 1 (any shift: rows 2 th and 2 th + 1 differ in bit 0 only);
+//   * hin and win even, so rows / columns 1 and 2 of a patch are always both inside the map (an odd, narrowed map leaves its
+//     last tile row with row 1 inside and row 2 outside: d2 = 0 != d1); circular padding never wraps them either;
+//   * no in-gather affine: it would keep the property (the same operation on equal bits under the same validity bit), but the
+//     UPS kernels are instantiated for AFF = 0 only -- a lazy normalisation in front of an upsampled source stays unstructured.
+// A depth tap does not matter (one plane serves the whole patch).  The kernel walks the plain steps first and the structured
+// ones behind them, so a structured first source in front of a plain second one is reported as plain.
+// Bit s of the result = source s is structured.
+__host__ __device__ __forceinline__ int x3_structured_mask(const AzConvArgs& a) {
+  if (a.aniso || a.in_affine || ((a.hin | a.win) & 1) || (a.pad_mode != 0 && a.pad_mode != 1)) return 0;
+  const int m0 = a.up0 >= 1 ? 1 : 0;
+  const int m1 = a.src1 && a.up1 >= 1 ? 2 : 0;
+  if (a.src1 && !m1) return 0;
+  return m0 | m1;
+}
 
 }  // namespace
 
@@ -456,4 +477,5 @@ struct WinoP {
   int gt, gc;          // workgroup order: rectangles of gt tile blocks x gc cout blocks, tile block fastest inside (1, cblocks: cout fastest)
   int rect_w, rect_h;  // x3 kernel: a block's tiles as a rectangle of rect_w x rect_h = 64 tiles of one image; 64 x 1: runs of adjacent tiles across rows and images
   float out_scale;     // f16x2 form of the x3 kernel: 1 / w_scale; the accumulators are multiplied by out_scale / (the activation scale) behind the K loop
+  int ups;             // x3 kernel: bit s = source s is structured (x3_structured_mask): its K steps skip the 7 zero frequencies; 0: the kernels without UPS
 };

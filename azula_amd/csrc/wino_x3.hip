@@ -83,7 +83,13 @@ static_assert(X_LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 //   table of the epilogue differ: the K loop, the V layout and every output's accumulation order are the run form's, so the
 //   outputs are bit-identical; a GroupNorm record covers the rectangle.  The launcher picks the shape per launch (conv.hip:
 //   x3_choose_block); RECT = false is the run form, token for token what it was.
-template <int AFF, bool TAIL, bool H2 = false, bool RECT = false>
+// UPS: the launch has a structured source (p.ups != 0; conv_shared.h: x3_structured_mask): on its K steps frequency index 2 is
+//   exactly zero in both directions, and the kernel leaves out everything that only moves or multiplies those zeros -- the
+//   two xi = 2 waves have no products on such a step and the k = 0 waves none in phase 1 (nu = 2): no MFMAs, no operand split,
+//   no filter fragments, no V fragment reads, and the producer side does not store the 7 zero rows.  Barriers, LDS buffers,
+//   accumulators (the zero frequencies keep what the other source's steps put there) and the epilogue are unchanged, so the
+//   outputs are bit-identical.  UPS = false is the kernel as it was, token for token; UPS is instantiated for AFF = 0 only.
+template <int AFF, bool TAIL, bool H2 = false, bool RECT = false, bool UPS = false>
 __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   extern __shared__ __attribute__((aligned(16))) float wsm[];
   char* const smem = reinterpret_cast<char*>(wsm);
@@ -305,9 +311,15 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   // columns side of B^T d B of frequency row xi for one half of the frequencies (hs = 0: nu in {0, 1}; 1: nu in {2, 3}), stored
   // as fp32 pairs: row (2 xi + j) of buffer hs, tile vj, channels 2 vq, 2 vq + 1
   const int vrow = vj * X_ROW + (((vq >> 1) ^ ((vj >> 2) & 3)) * 16) + (vq & 1) * 8;
-  auto nu_store = [&](int hs, int xi) __attribute__((always_inline)) {
+  // (pst: the step is structured -- rows xi = 2 and, in the second half, nu = 2 are zeros nobody reads: not stored)
+  auto nu_store = [&](int hs, int xi, bool pst = false) __attribute__((always_inline)) {
+    if (pst && xi == 2) return;
     const f32x2 u0 = rv[4 * xi], u1 = rv[4 * xi + 1], u2 = rv[4 * xi + 2], u3 = rv[4 * xi + 3];
     char* dst = smem + hs * X_HALF + vrow + (2 * xi) * X_FREQ;
+    if (pst && hs == 1) {  // (nu = 2 is a zero row too)
+      *reinterpret_cast<f32x2*>(dst + X_FREQ) = u1 - u3;
+      return;
+    }
     *reinterpret_cast<f32x2*>(dst) = hs == 0 ? u0 - u2 : u2 - u1;
     *reinterpret_cast<f32x2*>(dst + X_FREQ) = hs == 0 ? u1 + u2 : u1 - u3;
   };
@@ -403,8 +415,32 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   // MFMAs first and everything else behind them; a sched_group_barrier pattern was not honoured).  The consumer side of a
   // slot splits the phase's own V fragments just ahead of the products that need them; the producer side follows.
 #define XS_FENCE __builtin_amdgcn_sched_barrier(0)
-  auto phase = [&](auto HS, int kt, int ktn) __attribute__((always_inline)) {
+    auto body = [&](auto HS, auto CONS_, auto NEXT_, auto PST_, int kt, int ktn) __attribute__((always_inline)) {
     constexpr int hs = decltype(HS)::value;
+    // UPS: the versions of a phase on a structured step.  CONS: the wave has products in this phase (false:
+    // produce-only, the consumer side of every slot drops out); NEXT: it has products in the NEXT phase, whose filter fragments
+    // and V fragments are fetched here; PST: the step whose V this phase produces is structured -- its zero rows are not stored.
+    constexpr bool CONS = decltype(CONS_)::value, NEXT = decltype(NEXT_)::value, PST = decltype(PST_)::value;
+    // (the slot sequences below are written once, in the names of the kernel's own steps: these stand-ins drop the consumer side,
+    //  the fetches for the next phase or the zero rows out of a version)
+    const auto& mf_ = mf;
+    const auto& h_piece_ = h_piece;
+    const auto& l_piece_ = l_piece;
+    const auto& derive_u2_ = derive_u2;
+    const auto& piece_ = piece;
+    const auto& remainder_ = remainder;
+    const auto& load_u_ = load_u;
+    const auto& frag_read_ = frag_read;
+    const auto& nu_store_ = nu_store;
+    auto mf = [&](int f, int k) __attribute__((always_inline)) { if constexpr (CONS) mf_(f, k); };
+    auto h_piece = [&](int th) __attribute__((always_inline)) { if constexpr (CONS) h_piece_(th); };
+    auto l_piece = [&](int th) __attribute__((always_inline)) { if constexpr (CONS) l_piece_(th); };
+    auto derive_u2 = [&]() __attribute__((always_inline)) { if constexpr (CONS) derive_u2_(); };
+    auto piece = [&](int th, int pl) __attribute__((always_inline)) { if constexpr (CONS) piece_(th, pl); };
+    auto remainder = [&](int th, int j0, int j1) __attribute__((always_inline)) { if constexpr (CONS) remainder_(th, j0, j1); };
+    auto load_u = [&](int ku, int f, int pl) __attribute__((always_inline)) { if constexpr (NEXT) load_u_(ku, f, pl); };
+    auto frag_read = [&](int half, int th) __attribute__((always_inline)) { if constexpr (NEXT) frag_read_(half, th); };
+    auto nu_store = [&](int half, int xi) __attribute__((always_inline)) { nu_store_(half, xi, PST); };
     constexpr int ob = 1 - hs;  // the buffer (and half of the frequencies) this phase produces
     const int ktu = hs == 0 ? kt : ktn;  // the step whose filter fragments are loaded next (frequency f = ob of it)
     // (entry: xf[0], xf[1] hold the phase's raw fragments, read behind the barrier)
@@ -509,7 +545,16 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     frag_read(ob, 0); frag_read(ob, 1);
     XS_FENCE;
   };
-
+  // The K walk over steps [k0, k1) with one version of each phase (C0, N0: CONS and NEXT of phase 0; C1, N1: of phase 1).
+  auto steps = [&](auto C0, auto N0, auto C1, auto N1, auto PST_, int k0, int k1) __attribute__((always_inline)) {
+#pragma unroll 1
+    for (int kt = k0; kt < k1; ++kt) {
+      const int ktn = min(kt + 1, kt_end - 1);  // (the last step restages itself into a buffer nobody reads: no branch in the body)
+      if (ktn >= p.nkc0 && cur_src == 0) switch_source();  // (uniform, once per K walk: this iteration gathers from the second source)
+      body(std::integral_constant<int, 0>{}, C0, N0, PST_, kt, ktn);
+      body(std::integral_constant<int, 1>{}, C1, N1, PST_, kt, ktn);
+    }
+  };
   if (kt_begin < kt_end) {
 #pragma unroll
     for (int m = 0; m < 6; ++m) gl(kt_begin, m);
@@ -536,12 +581,25 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
     frag_read(0, 0); frag_read(0, 1);
     // waves 4 .. 7 are the younger half of every SIMD pair and lose the vector-issue arbitration by age: static priority
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#pragma unroll 1
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-      const int ktn = min(kt + 1, kt_end - 1);  // (the last step restages itself into a buffer nobody reads: no branch in the body)
-      if (ktn >= p.nkc0 && cur_src == 0) switch_source();  // (uniform, once per K walk: this iteration gathers from the second source)
-      phase(std::integral_constant<int, 0>{}, kt, ktn);
-      phase(std::integral_constant<int, 1>{}, kt, ktn);
+    constexpr std::true_type T{};
+    constexpr std::false_type F{};
+    if constexpr (!UPS) {
+      steps(T, T, T, T, F, kt_begin, kt_end);
+    } else {
+      // The plain steps first (p.ups == 2: the first source's; their last phase 1 produces the first structured step's V in
+      // full and fetches its fragments for every wave, which costs a little and needs no version of its own), then the
+      // structured steps in ONE of three loops, by what the wave owns: the xi = 2 waves have no products at all, the k = 0
+      // waves none in phase 1 (nu = 2).  A structured source is never followed by a plain one (the launcher checks), and a
+      // split-K slice may begin inside either part.  Every wave passes the same number of barriers, two per step.
+      // (The loops follow each other, each with an empty range for the waves it is not for: behind a three-way branch the
+      //  register allocator spilled an accumulator inside every loop, the plain one included.)
+      const int ks = (p.ups & 1) ? kt_begin : max(kt_begin, min(kt_end, p.nkc0));
+      const int swave = __builtin_amdgcn_readfirstlane(wave);
+      const bool xi2 = (swave & 3) == 2, k0 = !xi2 && swave < 4;
+      steps(T, T, T, T, F, kt_begin, ks);
+      steps(T, T, T, T, T, ks, xi2 || k0 ? ks : kt_end);
+      steps(T, F, F, T, T, ks, k0 ? kt_end : ks);
+      steps(F, F, F, F, T, ks, xi2 ? kt_end : ks);
     }
     __builtin_amdgcn_s_setprio(0);
   }
@@ -706,12 +764,12 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
 }  // namespace
 
 // Launch (host side of az_conv2d_winograd_x3_f32, conv.hip validates the descriptor and fills `p` in 16-channel steps).
-template <int AFF, bool TAIL, bool H2, bool RECT>
+template <int AFF, bool TAIL, bool H2, bool RECT, bool UPS = false>
 static int launch_x3(const WinoP& p, unsigned splitk, hipStream_t st) {
   static std::atomic<uint64_t> lds_set{0};  // (one per instantiation, one bit per device: common.h)
-  hipError_t e = az_max_dynamic_lds((const void*)conv_winograd_x3_kernel<AFF, TAIL, H2, RECT>, X_LDS_BYTES, lds_set);
+  hipError_t e = az_max_dynamic_lds((const void*)conv_winograd_x3_kernel<AFF, TAIL, H2, RECT, UPS>, X_LDS_BYTES, lds_set);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((conv_winograd_x3_kernel<AFF, TAIL, H2, RECT>), dim3((unsigned)((int64_t)p.cblocks * p.tblocks), splitk), dim3(512), X_LDS_BYTES,
+  hipLaunchKernelGGL((conv_winograd_x3_kernel<AFF, TAIL, H2, RECT, UPS>), dim3((unsigned)((int64_t)p.cblocks * p.tblocks), splitk), dim3(512), X_LDS_BYTES,
                      st, p);
   return az_launch_status();
 }
@@ -720,6 +778,10 @@ template <bool H2, bool RECT>
 static int launch_x3_mode(const WinoP& p, unsigned splitk, hipStream_t st) {
   const bool tail = (p.a.c0s % XK) != 0 || (p.a.c1s % XK) != 0;
   const int aff = !p.a.in_affine ? 0 : (p.a.in_act == 0 ? 1 : 2);
+  if (p.ups) {  // a structured source (the rule excludes in_affine; a structured first source in front of a plain second one has no version)
+    if (aff != 0 || p.ups != x3_structured_mask(p.a)) return AZ_E_SHAPE;
+    return tail ? launch_x3<0, true, H2, RECT, true>(p, splitk, st) : launch_x3<0, false, H2, RECT, true>(p, splitk, st);
+  }
   switch (aff * 2 + (tail ? 1 : 0)) {
     case 0: return launch_x3<0, false, H2, RECT>(p, splitk, st);
     case 1: return launch_x3<0, true, H2, RECT>(p, splitk, st);

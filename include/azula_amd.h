@@ -709,6 +709,14 @@ int az_winograd_x3_choose_block(int32_t batch, int32_t hin, int32_t win, int32_t
                                 int64_t* slots, int64_t* slots_run);
 int az_winograd_x3_block_geometry(int32_t batch, int32_t hin, int32_t win, int32_t pad_mode, int32_t rect_w, int32_t rect_h,
                                   int32_t block, int32_t* slot_pix, int32_t* tile_info);
+/* Structured sources of az_conv2d_winograd_x3_f32 / az_conv2d_winograd_f16x2_f32 (host arithmetic only: no device is touched, no
+ * pointer of `args` is dereferenced).  A source read through nearest upsampling (up >= 1 on both axes) of an even-sized map with
+ * zero or circular padding and no in_affine hands rows 1 and 2 and columns 1 and 2 of every 4 x 4 patch equal values, so 7 of its
+ * 16 Winograd frequencies (xi = 2 or nu = 2) are exact zeros; on that source's K steps the kernel skips their filter loads, V
+ * traffic and matrix instructions, with bit-identical outputs.  A structured src0 in front of a plain src1 counts as plain.
+ * mask: bit 0 = src0, bit 1 = src1 structured by that rule; launch_mask: what a launch made now would hand the kernel (the same,
+ * or 0 under AZ_DEBUG_AB=1 AZ_X3_UPS=0).                                                                                      */
+int az_winograd_x3_structured_mask(const AzConvArgs* args, int32_t* mask, int32_t* launch_mask);
 /* fp32 operands on the fp16 matrix pipe ("f16x2"; AZ_FP32_MFMA=f16x2): HALF the matrix instructions of the bf16x3 form.
  * An activation x enters as x' = x * AZ_F16X2_IN_SCALE = h + l / 2^11 with h = fp16(x') and l = fp16((x' - h) * 2^11) (22 - 23
  * significant bits), a weight as w' = w * w_scale = wh + wl (two fp16 pieces, the residual unscaled) plus a third plane

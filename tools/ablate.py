@@ -323,6 +323,10 @@ VARIANTS["wx3_slot80"] = [("wino_x3.hip", "constexpr int X_SLOT = 64;", "constex
 # ---- x3 Winograd kernel: the run form of the tile blocks everywhere (no rectangular blocks: profiles/r07_wx3_rect_blocks_ab.txt; the
 #      same switch without a rebuild: AZ_DEBUG_AB=1 AZ_X3_BLOCK=64,1)
 VARIANTS["wx3_norect"] = [("conv.hip", "constexpr bool X3_RECT_BLOCKS = true;", "constexpr bool X3_RECT_BLOCKS = false;")]
+# ---- structured (nearest-upsampled) sources of the x3 / f16x2 Winograd kernel (wino_x3.hip: UPS; profiles/r08_wx3_upsampled_ab.txt):
+#      the launcher hands every launch an empty mask, so the kernels without UPS run everywhere -- RESULTS STAY CORRECT, bit for bit
+#      (the same switch without a rebuild: AZ_DEBUG_AB=1 AZ_X3_UPS=0)
+VARIANTS["wx3_noups"] = [("conv.hip", "  return x3_structured_mask(a);\n}", "  return 0;\n}")]
 
 # ---- f16x2 attention, 256-query workgroups at head_dim <= 64: four waves per SIMD (<= 128 registers: two resident workgroups per CU, so
 #      that one's load / stage / barrier skeleton hides under the other's products) -- the compiler spills 31 registers to get there
