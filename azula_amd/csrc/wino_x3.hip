@@ -31,6 +31,8 @@
 //     on the UNet's maps): patches overlap by two rows as well, one window of 18 x 18 = 324 pixels is staged instead of the
 //     520 - 576 of the runs (3 instead of 5 - 6 lane slots per thread and step), the patch read is the same code at another
 //     row stride, and a wave's eight tiles stay neighbours along a row, so its bank pattern is the run form's.
+//     A pending normalisation of the input (in_affine, template parameter AFF) is applied to the rectangle's pixels WHILE they are
+//     staged, each once, instead of to every thread's patch (the run form, whose slots span images).
 //   * Epilogue: every wave applies the nu side of A^T M A to its two frequencies in registers, the k = 1 waves hand their partial
 //     to the k = 0 waves through LDS, which park Z[xi][px] as [xi][tile][px][cout]; all 8 waves read rows back applying the xi
 //     side; bias / SiLU / gate / residual / split-K slabs / GroupNorm moments of the output as in the fp32 kernel.
@@ -69,6 +71,9 @@ static_assert(4 * X_SLOTS <= 6 * 512, "six staging pieces per thread");
 static_assert(X_LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 
 // AFF: 0 = plain input, 1 = the input is x * scale + shift (in_affine: a GroupNorm apply pass folded into the gather), 2 = SiLU of that.
+//   Runs (RECT = false): evaluated on the thread's raw 4x4 patch under its validity mask (affine_load / affine / vmask).  Rectangles:
+//   evaluated on the staged lane slots in front of their LDS store (gs), 5,184 instead of 16,384 values per block and step, off
+//   phase 1's patch chain; the patch arrives transformed and those three are empty.
 // TAIL: a source's channel count is not a multiple of 16 -- the last step of that source masks the channel pairs past its end.
 // H2: the "f16x2" form (az_conv2d_winograd_f16x2_f32, include/azula_amd.h): the filter arrives as the IEEE half pieces
 //   [uh | ul | uh / 2^11] of U * w_scale in the SAME fragment layout, V is split into two half pieces of V * AZ_F16X2_IN_SCALE,
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   const int prow = RECT ? rg.ws * X_SLOT : (2 * pj_len + 2) * X_SLOT;
   const char* const patch = smem + X_STAGE + (RECT ? v_pslot : 8 * (pj_s + fdiv(vj + tw0, p.tiles_w)) + 2 * (vj - pj_s)) * X_SLOT + vq * 8;
   unsigned vmask = 0;
-  if constexpr (AFF != 0) {
+  if constexpr (AFF != 0 && !RECT) {  // (RECT: the affine is applied to the staged pixels, see gs)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -254,6 +259,27 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
   // the staging area at byte 16 L (gs) half a phase later.  (LDS-DMA moved the same bytes without registers, but one
   // buffer_load ... lds costs the issuing wave 100 - 180 cycles beside MFMAs: profiles/r05_wx3_timeline_v3.txt.)
   float4 gq[6];
+  // in_affine ([scale | shift], (batch, c0s) each; a single source): the input is act(x * scale + shift), padding stays zero.
+  // RECT applies it HERE, to the staged lane slots on their way into LDS: all slots of a block belong to image rg.b and a
+  // thread's lane slots L = m * 512 + tid all carry channels 4 (tid & 3) .. + 3 of the step, so ONE scale quad and ONE shift
+  // quad per thread and step, loaded beside piece 0, serve its 3 - 4 pieces -- 324 slots x 16 channels = 5,184 values per block
+  // and step where the 64 overlapping 4 x 4 patches hold 16,384 (the run form below still transforms the patch: its slots
+  // span images).  The same fused multiply-add on the same bits as the patch form's, so the outputs of in-image tiles are
+  // bit-identical.  A slot outside the map (doff == OOB) was loaded as zeros by the bounds-checked load: only its SHIFT has to be
+  // suppressed (sq_ok, known since the prologue, takes the place of the patch mask: 0 * scale + 0 = +0, silu(0) = 0); a channel
+  // quad past the source's end (TAIL) loads scale = shift = 0.
+  // What changes: tiles of a ragged rectangle that lie outside the image used to be zeroed as whole patches; now only their
+  // out-of-image pixels are zero.  Their outputs are never stored, and GroupNorm records are enabled for whole rectangles only.
+  const __amdgpu_buffer_rsrc_t raf = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(AFF != 0 ? a.in_affine : nullptr), 0, AFF != 0 ? (unsigned)(2 * a.batch * a.c0s * 4) : 0u, 0x00020000);
+  const unsigned af_shift = (unsigned)(a.batch * a.c0s * 4);  // the shift table sits behind the scale table
+  const unsigned sq_off = (unsigned)((rg.b * a.c0s + (tid & 3) * 4) * 4);
+  float4 sq_sc = {0.f, 0.f, 0.f, 0.f}, sq_sh = {0.f, 0.f, 0.f, 0.f};
+  bool sq_ok[6] = {false, false, false, false, false, false};
+  if constexpr (RECT && AFF != 0) {
+#pragma unroll
+    for (int m = 0; m < 6; ++m) sq_ok[m] = doff[m] != OOB;
+  }
   auto gl = [&](int kt, int m) __attribute__((always_inline)) {
     if (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma) {  // (uniform; a block always has at least 520 slots = 4.06 pieces per thread; RECT: 324 .. 512 slots)
       const bool src1 = kt >= p.nkc0;
@@ -262,9 +288,26 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
       unsigned off = doff[m];
       if constexpr (TAIL) off = kc * XK + (tid & 3) * 4 < (src1 ? a.c1s : a.c0s) ? off : OOB;  // (channel quads past the source's end)
       gq[m] = buf_ld4(r, off, (unsigned)(kc * XK * 4));
+      if constexpr (RECT && AFF != 0) {
+        if (m == 0) {  // the step's scale / shift quad of the thread's channels
+          const unsigned qo = !TAIL || kt * XK + (tid & 3) * 4 < a.c0s ? sq_off : OOB;
+          sq_sc = buf_ld4(raf, qo, (unsigned)(kt * XK * 4));
+          sq_sh = buf_ld4(raf, qo, (unsigned)(kt * XK * 4) + af_shift);
+        }
+      }
     }
   };
   auto gs = [&](int m) __attribute__((always_inline)) {
+    if constexpr (RECT && AFF != 0) {
+      if (m < 3 || (m < 4 && m < ndma)) {
+        // (the select sits on the shift, not on the result: as a select of the result the compiler branches around the multiply-adds)
+        const f32x2 tl = {sq_ok[m] ? sq_sh.x : 0.f, sq_ok[m] ? sq_sh.y : 0.f}, th = {sq_ok[m] ? sq_sh.z : 0.f, sq_ok[m] ? sq_sh.w : 0.f};
+        f32x2 lo = f32x2{gq[m].x, gq[m].y} * f32x2{sq_sc.x, sq_sc.y} + tl;
+        f32x2 hi = f32x2{gq[m].z, gq[m].w} * f32x2{sq_sc.z, sq_sc.w} + th;
+        if constexpr (AFF == 2) lo = f32x2{az_silu(lo.x), az_silu(lo.y)}, hi = f32x2{az_silu(hi.x), az_silu(hi.y)};
+        gq[m] = make_float4(lo.x, lo.y, hi.x, hi.y);
+      }
+    }
     if (RECT ? m < 3 || (m < 4 && m < ndma) : m < 5 || m < ndma) *reinterpret_cast<float4*>(smem + X_STAGE + ((m * 512 + tid) >> 2) * X_SLOT + (tid & 3) * 16) = gq[m];
   };
   auto patch_rows = [&](int kt, int r0, int r1) __attribute__((always_inline)) {  // rows [r0, r1) of the staged patch -> rv
@@ -273,25 +316,23 @@ __global__ __launch_bounds__(512, 2) void conv_winograd_x3_kernel(WinoP p) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) rv[4 * r + c] = *reinterpret_cast<const f32x2*>(patch + r * prow + c * X_SLOT);
   };
-  // with in_affine the input is act(x * scale + shift) (padding positions stay zero): applied to the raw patch in place
+  // The run form (RECT = false) of in_affine: applied to the raw patch in place, under the patch's validity mask (both lambdas
+  // are empty in the rectangle form, whose pixels arrive transformed).
   // the scale / shift pair of the thread's channel pair for step kt: two bounds-checked 8-byte loads issued well ahead of their
   // use (as a pointer dereference in front of the multiply they put a global round trip on every step: - 2 % on the affine layers).
   // (Measured and not kept: the plain affine in the transformed domain, B^T (s d + t m) B = s B^T d B + t (B^T r)(B^T c)^T for the
   //  validity pattern m = r c^T -- 36 instead of 80 vector instructions per step, the same time.)
-  const __amdgpu_buffer_rsrc_t raf = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(AFF != 0 ? a.in_affine : nullptr), 0, AFF != 0 ? (unsigned)(2 * a.batch * a.c0s * 4) : 0u, 0x00020000);
   const unsigned af_voff = (unsigned)(((b_first + (v_b < 0 ? 0 : v_b)) * a.c0s + vq * 2) * 4);
-  const unsigned af_shift = (unsigned)(a.batch * a.c0s * 4);  // the shift table sits behind the scale table
   f32x2 af_sc = {0.f, 0.f}, af_sh = {0.f, 0.f};
   auto affine_load = [&](int kt) __attribute__((always_inline)) {
-    if constexpr (AFF != 0) {
+    if constexpr (AFF != 0 && !RECT) {
       const bool kv = !TAIL || kt * XK + vq * 2 < a.c0s;  // (masked pairs hold zeros and stay zero)
       af_sc = buf_ld2(raf, kv ? af_voff : OOB, (unsigned)(kt * XK * 4));
       af_sh = buf_ld2(raf, kv ? af_voff : OOB, (unsigned)(kt * XK * 4) + af_shift);
     }
   };
   auto affine = [&]() __attribute__((always_inline)) {
-    if constexpr (AFF != 0) {
+    if constexpr (AFF != 0 && !RECT) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         f32x2 v = rv[i] * af_sc + af_sh;

@@ -137,7 +137,7 @@ _G_PROD = [
     ("wino_x3.hip", "  auto patch_rows = [&](int kt, int r0, int r1) __attribute__((always_inline)) {  // rows [r0, r1) of the staged patch -> rv\n", "  auto patch_rows = [&](int kt, int r0, int r1) __attribute__((always_inline)) {\n    if (!prod) return;\n"),
     ("wino_x3.hip", "    const f32x2 d0 = rv[c], d1 = rv[4 + c], d2 = rv[8 + c], d3 = rv[12 + c];\n", "    if (!prod) return;\n    const f32x2 d0 = rv[c], d1 = rv[4 + c], d2 = rv[8 + c], d3 = rv[12 + c];\n"),
     ("wino_x3.hip", "    const f32x2 u0 = rv[4 * xi], u1 = rv[4 * xi + 1], u2 = rv[4 * xi + 2], u3 = rv[4 * xi + 3];\n", "    if (!prod) return;\n    const f32x2 u0 = rv[4 * xi], u1 = rv[4 * xi + 1], u2 = rv[4 * xi + 2], u3 = rv[4 * xi + 3];\n"),
-    ("wino_x3.hip", "    if constexpr (AFF != 0) {\n#pragma unroll\n      for (int i = 0; i < 16; ++i) {\n        f32x2 v = rv[i] * af_sc + af_sh;", "    if constexpr (AFF != 0) {\n      if (!prod) return;\n#pragma unroll\n      for (int i = 0; i < 16; ++i) {\n        f32x2 v = rv[i] * af_sc + af_sh;"),
+    ("wino_x3.hip", "    if constexpr (AFF != 0 && !RECT) {\n#pragma unroll\n      for (int i = 0; i < 16; ++i) {\n        f32x2 v = rv[i] * af_sc + af_sh;", "    if constexpr (AFF != 0 && !RECT) {\n      if (!prod) return;\n#pragma unroll\n      for (int i = 0; i < 16; ++i) {\n        f32x2 v = rv[i] * af_sc + af_sh;"),
 ]
 _G_CONS = [
     ("wino_x3.hip", "    const char* vb = smem + hs * X_HALF + fragB + th * (32 * X_ROW);\n", "    if (th == 1) return;\n    const char* vb = smem + hs * X_HALF + fragB + th * (32 * X_ROW);\n"),

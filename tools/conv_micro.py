@@ -1,10 +1,12 @@
 r"""Micro-benchmark of az_conv2d_f32 on one shape (for rocprofv3 PMC passes and A/B tuning).
 
-    python tools/conv_micro.py B H W Cin Cout [ks] [stride] [reps] [C1] [up]
+    python tools/conv_micro.py B H W Cin Cout [ks] [stride] [reps] [C1] [up] [affine]
 
 C1 > 0: a second source of C1 channels behind the Cin of the first, read through nearest upsampling by 2^up (the UNet's merge
 layers: C1 = the lower level's channels, up = 1).  C1 = 0 with up > 0: the one source is read through 2^up upsampling (ADM's
 up-ResBlocks and Upsample layers).  (H, W) is always the map the convolution runs on.
+affine: the input carries a pending normalisation (AzConvArgs.in_affine, the first convolution of a UNetBlock): 1 = plain
+(in_act 0), 2 = with SiLU (in_act 1); 0 or absent: none.  AZ_AFFINE=1 / 2 in the environment does the same.
 """
 import sys
 import os
@@ -20,6 +22,7 @@ stride = int(sys.argv[7]) if len(sys.argv) > 7 else 1
 reps = int(sys.argv[8]) if len(sys.argv) > 8 else 20
 C1 = int(sys.argv[9]) if len(sys.argv) > 9 else 0
 up = int(sys.argv[10]) if len(sys.argv) > 10 else 0
+affine = int(sys.argv[11]) if len(sys.argv) > 11 else int(os.environ.get("AZ_AFFINE") or 0)
 up0, up1 = (0, up) if C1 else (up, 0)
 low = lambda n, u: (n + (1 << u) - 1) >> u  # noqa: E731
 dev = torch.device("cuda")
@@ -30,8 +33,8 @@ x = Act(torch.randn(B * low(H, up0) * low(W, up0) * Cin, device=dev) * scale, B,
 x1 = Act(torch.randn(B * low(H, up1) * low(W, up1) * C1, device=dev) * scale, B, low(H, up1), low(W, up1), C1, C1, True) if C1 else None
 w = torch.randn(Cout, Cin + C1, ks, ks, device=dev) / ((Cin + C1) * ks * ks) ** 0.5 * scale
 b = torch.randn(Cout, device=dev)
-if os.environ.get("AZ_AFFINE"):  # the input carries a pending normalisation (AzConvArgs.in_affine): AZ_AFFINE=1 plain, 2 with SiLU
-    x.affine = (torch.randn(2 * B * Cin, device=dev) * scale, int(os.environ["AZ_AFFINE"]) - 1)
+if affine:  # the input carries a pending normalisation (AzConvArgs.in_affine): 1 plain, 2 with SiLU
+    x.affine = (torch.randn(2 * B * Cin, device=dev) * scale, affine - 1)
 wino = {"1": True, "0": False, "4": 4, "x3": "x3", "wx3": "wx3", "h2": "h2", "wh2": "wh2"}.get(os.environ.get("AZ_WINO", ""), None)
 src = dict(src1=x1, up1=up1) if C1 else dict(up0=up0)
 y = bld.conv(x, bld.pack_conv(w, b, cin0=Cin) if C1 else bld.pack_conv(w, b), Cout, hin=H, win=W, stride=stride, act=int(os.environ.get("AZ_ACT", "1")),
@@ -67,4 +70,5 @@ if len(bld.tape.ops) > 1:  # per-op times (e.g. the split pass of AZ_X3_PLANES=1
         per.append(f"{name} {e0.elapsed_time(e1) / reps * 1e3:.1f} us")
     print("   ", "; ".join(per))
 cin = f"{Cin}+{C1}(up{up})" if C1 else (f"{Cin}(up{up})" if up else f"{Cin}")
-print(f"conv[{desc._algo[10:-4]}] {B}x{H}x{W} {cin}->{Cout} k{ks} s{stride} splitk={desc.splitk}: {ms * 1e3:.1f} us  {desc._flops / ms / 1e9:.1f} TF/s")
+aff = ("", " affine", " affine+silu")[affine] if desc.in_affine else ""
+print(f"conv[{desc._algo[10:-4]}{aff}] {B}x{H}x{W} {cin}->{Cout} k{ks} s{stride} splitk={desc.splitk}: {ms * 1e3:.1f} us  {desc._flops / ms / 1e9:.1f} TF/s")
