@@ -2,7 +2,9 @@ r"""``azula_amd.linalg.covariance``, ``GaussianDenoiser`` and ``JFPSDenoiser`` w
 reference's recorded signatures; host applies, ``inv``, ``color``, ``logdet``, the algebra and both denoisers against the
 restatement of ``tests/covariance_oracle.py`` (independent of ``azula_amd``) bit for bit and against fixture G27 within the
 round-off of another CPU; the covariance identities in fp64 for every ``from_data`` variant; the algebra's dispatch rules;
-JFPS's public surface; and the C ABI of the covariance entries."""
+JFPS's public surface; the C ABI of the covariance entries; and the cases of the kernel tests (tests/covariance_cases.py): they reach
+every tile constant, the exact family is exact in fp32, five planted faults change its reference, and torch's own evaluation meets
+the hard family's derived bound."""
 
 import ctypes
 import inspect
@@ -11,9 +13,11 @@ import os
 import subprocess
 import tempfile
 
+import numpy as np
 import pytest
 import torch
 
+import covariance_cases as cc
 import covariance_oracle as co
 from conftest import ROOT, max_err
 from oracle import nets, sampling, synth
@@ -355,3 +359,114 @@ def test_host_ddim_loop_with_jfps(golden):
                                      iterations=lp["iterations"]), g["jf_loop_x1"], steps=lp["steps"], eta=lp["eta"])
     assert torch.equal(x0, ref)
     assert close(x0, g["jf_loop_x0"], 1e-4)
+
+
+# ------------------------------------------------------------------------------------ the kernel tests' cases (covariance_cases.py)
+ALL_CASES = [c for cases in cc.CASES.values() for c in cases]
+DOT_CASES = cc.PROJECT_CASES + cc.EXPAND_CASES + cc.MODE_CASES
+
+
+def test_case_lists_reach_every_tile_constant():
+    r"""Just below, on and just above: 64 features, 64 rank columns, 32 rows, 512 per segment, inner = 64, the grid caps."""
+    def values(cases, field):
+        return {getattr(c, field) for c in cases}
+
+    assert values(cc.PROJECT_CASES, "n") >= {1, 63, 64, 65, 511, 512, 513, 1100}
+    assert values(cc.PROJECT_CASES, "r") >= {1, 63, 64, 65, 130} and values(cc.PROJECT_CASES, "rows") >= {1, 31, 32, 33, 70}
+    assert values(cc.PROJECT_CASES, "c") == {0, 1}
+    assert any(c.n % cc.SEG % cc.TILE and c.n > cc.SEG for c in cc.PROJECT_CASES)  # a ragged tile inside a later segment
+    assert values(cc.EXPAND_CASES, "n") >= {1, 63, 64, 65, 130} and values(cc.EXPAND_CASES, "r") >= {1, 64, 65, 200}
+    assert values(cc.EXPAND_CASES, "rows") >= {1, 32, 33, 70} and values(cc.EXPAND_CASES, "x") == {"none", "d", "d0"}
+    assert values(cc.EXPAND_CASES, "a") == {0, 1} == values(cc.EXPAND_CASES, "g") and values(cc.EXPAND_CASES, "s") == {1, -1}
+    assert values(cc.MODE_CASES, "n") >= {1, 5, 63, 64, 65, 100, 130} and values(cc.MODE_CASES, "inner") >= {1, 7, 63, 64, 70}
+    assert values(cc.MODE_CASES, "outer") >= {1, 3, 10} and values(cc.MODE_CASES, "transpose") == {0, 1}
+    ragged = [c for c in cc.MODE_CASES if (c.outer * c.inner) % cc.TILE]
+    assert any(c.inner >= 64 for c in ragged) and any(c.inner < 64 and c.outer * c.inner > cc.TILE for c in ragged)
+    assert any(64 < c.n < 128 for c in cc.MODE_CASES)
+    pairs = {("f32", "f32"), ("f64", "f64"), ("f32", "f64"), ("f64", "f32")}
+    for cases in (cc.PROJECT_CASES, cc.EXPAND_CASES, cc.MODE_CASES):
+        assert {(c.xd, c.fd) for c in cases} == pairs
+    s = cc.SCALE_CASES
+    assert values(s, "h") == {0, 1, 2, 3} and values(s, "e") == {"n", "1", "none"} and values(s, "n") >= {1, 255, 256, 257}
+    assert values(s, "u") == {0, 1} == values(s, "v") == values(s, "alias") and values(s, "k") == {"one", "host", "dev"}
+    assert values(s, "rho") == {"host", "dev"} and any(c.sd == "f64" and c.xd == "f32" and c.k == "dev" for c in s)
+    assert any(c.rows == 65535 + 2 and c.n == 3 for c in s) and cc.STRIDE_X_N == 256 * 65536 + 5
+    assert all(not c.alias or cc.DT[c.xd] == cc.out_dtype(c) for c in s)
+    assert len({cc.case_id(c) for c in ALL_CASES}) == len(ALL_CASES)
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=cc.case_id)
+def test_exact_family_is_exact_in_fp32(case):
+    r"""Every intermediate any evaluation order could form is bounded by the sum of absolute values: below 2^24, so fp32 is
+    exact, and torch's fp32 evaluation equals the integer reference."""
+    inp = cc.inputs(case, "exact")
+    if isinstance(case, cc.Scale):
+        ref, B = cc.scale_ref(inp, case, np.float64, want_bound=True)
+        assert B.max() < 2.0 ** 24 and np.isfinite(ref).all()
+        assert (ref * 4 == np.round(ref * 4)).all()  # quarters at the finest (e / (e + rho) = 3 / 4)
+    else:
+        ref = cc.reference(case, inp, dt=np.float64)
+        assert cc.magnitude(case, inp).max() < 2.0 ** 24
+        assert (ref == np.round(ref)).all() and np.abs(ref).max() > 0
+        assert np.array_equal(cc.reference(case, inp).astype(np.float64), ref)
+    got = cc.torch_eval(case, inp, torch.float32)
+    assert got.dtype == torch.float32 and torch.equal(got.double(), torch.from_numpy(ref))
+    for name in ("W", "Q"):
+        if name in inp:
+            F = inp[name]
+            assert (F[-1] != 0).all() and (F[:, -1] != 0).all() and F[0, 0] != 0 and F.abs().max() <= 3
+            assert F.shape[0] != F.shape[1] or F.shape[0] < 3 or not torch.equal(F, F.T)
+            if min(F.shape) >= 8:  # no two rows and no two columns alike
+                assert len({tuple(r.tolist()) for r in F}) == F.shape[0] and len({tuple(r.tolist()) for r in F.T}) == F.shape[1]
+
+
+@pytest.mark.parametrize("case", DOT_CASES, ids=cc.case_id)
+def test_planted_faults_change_the_exact_reference(case):
+    inp = cc.inputs(case, "exact")
+    ref = cc.reference(case, inp, dt=np.float64)
+    for fault in cc.FAULTS:
+        if cc.fault_applies(case, fault):
+            bad = cc.reference(case, inp, fault=fault, dt=np.float64)
+            assert bad.shape == ref.shape and not np.array_equal(bad, ref), fault
+
+
+def test_every_fault_occurs_in_every_entry_it_exists_for():
+    for cases in (cc.PROJECT_CASES, cc.EXPAND_CASES, cc.MODE_CASES):
+        for fault in cc.FAULTS:
+            n = sum(cc.fault_applies(c, fault) for c in cases)
+            assert n >= 2 or (fault == "segment_twice" and cases is not cc.PROJECT_CASES), (fault, n)
+
+
+def test_project_partials_sum_to_the_projection():
+    for case in cc.PROJECT_CASES:
+        inp = cc.inputs(case, "exact")
+        parts = cc.project_partials(inp)
+        assert parts.shape == (cc.segments(case.n), case.rows, case.r)
+        assert np.array_equal(parts.sum(0), cc.reference(case, inp, dt=np.float64))
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=cc.case_id)
+def test_hard_family_bound_holds_for_torch(case):
+    r"""torch's own evaluation in the output dtype (fp32 wherever the operands are stored in fp32) is inside the derived bound: a
+    bound that the plain evaluation cannot meet would show here."""
+    inp = cc.inputs(case, "hard")
+    ref, allowed, dtype = cc.reference(case, inp), cc.bound(case, inp), cc.out_dtype(case)
+    assert np.isfinite(ref.astype(np.float64)).all() and (allowed >= 0).all()
+    ratio, err = cc.worst_ratio(cc.torch_eval(case, inp, dtype), ref, allowed)
+    print(f"COV host {cc.case_id(case)}: err {err:.3e} ratio {ratio:.4f}")
+    assert ratio <= 1.0, (err, ratio)
+
+
+def test_hard_family_spans_three_decades_and_the_bound_can_fail():
+    case = cc.Project(1100, 130, 70, 1, "f32", "f32")
+    inp = cc.inputs(case, "hard")
+    W = inp["W"].abs()
+    assert W.max() / W.min() > 500 and (inp["W"] < 0).any() and (inp["W"] > 0).any()
+    assert inp["x"].double().mean(1).abs().max() > 3  # the rows' offsets
+    ref, allowed = cc.reference(case, inp), cc.bound(case, inp)
+    half = cc.torch_eval(case, {k: (v.bfloat16().float() if torch.is_tensor(v) else v) for k, v in inp.items()}, torch.float32)
+    assert cc.worst_ratio(half, ref, allowed)[0] > 1.0  # operands rounded to 8 bits are outside it
+    bad = torch.from_numpy(cc.reference(case, inp, fault="last_feature").astype(np.float64)).float()
+    assert cc.worst_ratio(bad, ref, allowed)[0] > 1.0
+    assert cc.roundings(case) == (512 + 3, 1) and cc.roundings(cc.Expand(65, 200, 70, "d", 1, 1, -1, "f32", "f32")) == (200, 4)
+    assert cc.roundings(cc.Mode(130, 7, 3, 1, "f64", "f32")) == (130, 0)
