@@ -163,6 +163,29 @@ class Act:
         return v
 
 
+class SharedResidual:
+    r"""Marks the residual Act of :meth:`Builder.conv` as batch-shared (the epilogue's ``res_bcast``)."""
+
+    def __init__(self, act: Act) -> None:
+        self.act = act
+
+
+def param_versions(module: torch.nn.Module) -> tuple:
+    r"""What a compiled plan of ``module`` is valid for: (address, in-place version, dtype) of every parameter."""
+    return tuple((p.data_ptr(), p._version, p.dtype) for p in module.parameters())
+
+
+def mod_rows(mod: torch.Tensor | None, B: int, D: int, what: str = "module", tokens: bool = False) -> int:
+    r"""Rows of a modulation vector ``mod`` -- (D) or (B, D) [``tokens``: (*, D) with the leading shape of x] -- for a batch of B:
+    0 without modulation (``D == 0``), 1 when the samples share it, else B."""
+    if D == 0:
+        return 0
+    assert mod is not None, f"this {what} is modulated: pass mod"
+    rows = 1 if mod.ndim == 1 else (mod.numel() // mod.shape[-1] if tokens else mod.shape[0])
+    assert rows in (1, B), "mod must be (D) or (*, D) with the leading shape of x"
+    return rows
+
+
 # Winograd for stride-1 3x3 convs (see conv.hip): "1" = exact F(2x2,3x3) where it pays (default), "0" = never,
 # "2" = F(2x2) wherever it is legal (used by the parity tests to push whole networks through it),
 # "4" = the faster but inexact F(4x4,3x3) on layers with >= WINOGRAD4_MIN_TILES tiles, "1" elsewhere
@@ -324,6 +347,32 @@ def attention_qk_bound(dim: int, norm_dim: int, scale: float, qk_weight: tuple |
     n = norm_dim or dim
     gq, gk = (1.0, 1.0) if qk_weight is None else (float(qk_weight[0].detach().abs().max()), float(qk_weight[1].detach().abs().max()))
     return math.sqrt(n) * gk, math.sqrt(n) * gq * abs(scale) * 1.4426950408889634
+
+
+def qk_in_h2_domain(qk_rmsnorm: bool, dim: int, norm_dim: int, scale: float, qk_weight: tuple | None) -> bool:
+    r"""q / k are RMS-normalised with a plan-time bound inside the f16x2 attention kernel's domain (``choose_attention(qk_normed=)``)."""
+    if not qk_rmsnorm:
+        return False
+    kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, qk_weight)
+    return kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX
+
+
+def _token_strides(a, L: int, **tensors) -> None:
+    r"""Batch / token / head strides (in elements) of an attention descriptor's operands: ``name=(token Act of L tokens, head stride)``."""
+    for name, (t, hstride) in tensors.items():
+        setattr(a, name + "_bstride", L * t.cs)
+        setattr(a, name + "_tstride", t.cs)
+        setattr(a, name + "_hstride", hstride)
+
+
+def qkv_layout(order: str, Cq: int, dim: int) -> tuple[tuple, int]:
+    r"""(channel offsets of q, k, v in a fused token row of 3 Cq channels, head stride) for ``order``: "nHC" = azula '(n H C)'
+    (attention.py:90) and "3HC" = ADM's new order (unet.py:371), "H3C" = ADM legacy (unet.py:338)."""
+    if order in ("nHC", "3HC"):
+        return (0, Cq, 2 * Cq), dim
+    if order == "H3C":
+        return (0, dim, 2 * dim), 3 * dim
+    raise ValueError(order)
 
 
 def choose_attention(dim: int, qk_normed: bool, half: torch.dtype | None) -> str:
@@ -576,7 +625,7 @@ class Builder:
             a.gate = gate.data_ptr() + 4 * gate_off
             a.gate_bstride = gate_bstride
         if res is not None:
-            if hasattr(res, "act"):  # batch-shared residual (positional embedding table)
+            if isinstance(res, SharedResidual):  # (a positional embedding table)
                 res = res.act
                 a.res_bcast = 1
             a.res, a.res_up, a.hres, a.wres = res.ptr, res_up, res.H, res.W
@@ -856,7 +905,8 @@ class Builder:
         return self.wrote(y, bounded=False)
 
     def _attn_mask(self, mask: torch.Tensor, B: int, heads: int, L: int) -> tuple:
-        r"""(byte mask on the device, batch stride, head stride) of a boolean mask as :meth:`attention` reads it."""
+        r"""(byte mask on the device, batch stride, head stride) of a boolean mask -- (L, L) or (B | 1, 1 | H, L, L), True = attend
+        (reference attention.py:97-104) -- as the attention kernels read it."""
         m = mask[None, None] if mask.ndim == 2 else mask
         if m.ndim != 4 or m.shape[-2:] != (L, L) or m.shape[0] not in (1, B) or m.shape[1] not in (1, heads):
             raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast to ({B}, {heads}, {L}, {L})")
@@ -882,12 +932,7 @@ class Builder:
         assert qkv.cs == qkv.C and dim * heads == Cq and not qkv.half and self.half is None
         assert dim in ATTN_GRAD_HEAD_DIMS, dim
         B, L = qkv.B, qkv.H * qkv.W
-        if order in ("nHC", "3HC"):
-            offs, hs = (0, Cq, 2 * Cq), dim
-        elif order == "H3C":
-            offs, hs = (0, dim, 2 * dim), 3 * dim
-        else:
-            raise ValueError(order)
+        offs, hs = qkv_layout(order, Cq, dim)
         cos, sin = rope if rope is not None else (None, None)
         prep = not (skip_prep and not qk_rmsnorm and rope is None and qk_weight is None)
         qk = None
@@ -906,33 +951,25 @@ class Builder:
             self.wrote(qk, bounded=False)
         out = self.new_act(B, qkv.H, qkv.W, Cq)
         a = AzAttnArgs()
-        a.v, a.out = qkv.ptr + 4 * offs[2], out.ptr
+        qt, qo, ko, qh = (qk, 0, Cq, dim) if prep else (qkv, offs[0], offs[1], hs)  # (q^ | k^, or q and k where they lie)
+        a.q, a.k, a.v, a.out = qt.ptr + 4 * qo, qt.ptr + 4 * ko, qkv.ptr + 4 * offs[2], out.ptr
         a.batch, a.heads, a.tokens, a.head_dim = B, heads, L, dim
-        if prep:
-            a.q, a.k = qk.ptr, qk.ptr + 4 * Cq
-            a.q_bstride, a.q_tstride, a.q_hstride = L * qk.cs, qk.cs, dim
-            a.k_bstride, a.k_tstride, a.k_hstride = L * qk.cs, qk.cs, dim
-        else:
-            a.q, a.k = qkv.ptr + 4 * offs[0], qkv.ptr + 4 * offs[1]
-            a.q_bstride, a.q_tstride, a.q_hstride = L * qkv.cs, qkv.cs, hs
-            a.k_bstride, a.k_tstride, a.k_hstride = L * qkv.cs, qkv.cs, hs
-        a.v_bstride, a.v_tstride, a.v_hstride = L * qkv.cs, qkv.cs, hs
-        a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
+        _token_strides(a, L, q=(qt, qh), k=(qt, qh), v=(qkv, hs), o=(out, dim))
         a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, 0, eps, 0
         rec = dict(qkv=qkv, qk=qk, out=out, heads=heads, dim=dim, scale=scale, eps=eps, rms=bool(qk_rmsnorm), norm_dim=norm_dim,
                    rope=rope, mask=None, offs=offs, hs=hs, qk_weight=qk_weight)
         if mask is not None:
             m8, mb, mh = rec["mask"] = self._attn_mask(mask, B, heads, L)
             a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
-        kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, qk_weight) if qk_rmsnorm else (math.inf, math.inf)
         a._flops = 4 * B * heads * L * L * dim
-        self.tape.add(choose_attention(dim, kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX, None), C.byref(a),
+        self.tape.add(choose_attention(dim, qk_in_h2_domain(qk_rmsnorm, dim, norm_dim, scale, qk_weight), None), C.byref(a),
                       keep=[a, qk.buf if prep else qkv.buf])
         return self.wrote(out, bounded=False), rec
 
     def attention_bwd(self, g: Act, rec: dict) -> Act:
         r"""Cotangent ``g`` of the attention output -> cotangent of the fused q | k | v token tensor: ``az_attention_bwd_f32``
-        (dq^ | dk^ into a temporary, dv straight into its third) and ``az_qk_prep_bwd_f32`` (the q and k thirds)."""
+        (dq^ | dk^ into a temporary, dv straight into its third) and ``az_qk_prep_bwd_f32`` (the q and k thirds); one launch where
+        q^ = q and k^ = k."""
         from ._lib import AzAttnBwdArgs
 
         qkv, qk, out, heads, dim = rec["qkv"], rec["qk"], rec["out"], rec["heads"], rec["dim"]
@@ -941,25 +978,24 @@ class Builder:
         B, L = qkv.B, qkv.H * qkv.W
         assert (g.B, g.H, g.W, g.C) == (out.B, out.H, out.W, out.C)
         dqkv = self.new_act(B, qkv.H, qkv.W, 3 * Cq)
-        if qk is None:  # (attention_keep(skip_prep=True): q^ = q, k^ = k -- all three cotangents go straight into their places)
-            return self._attention_bwd_in_place(g, rec, dqkv)
-        dqk = self.new_act(B, qkv.H, qkv.W, 2 * Cq)
+        if qk is None:  # in place (attention_keep(skip_prep=True)): q^ | k^ and their cotangents live in qkv / dqkv themselves
+            qt, dqt, qh, qo, ko = qkv, dqkv, hs, offs[0], offs[1]
+        else:  # q^ | k^ in a buffer of their own: dq^ | dk^ into a temporary, az_qk_prep_bwd_f32 takes them to the q and k thirds
+            qt, dqt, qh, qo, ko = qk, self.new_act(B, qkv.H, qkv.W, 2 * Cq), dim, 0, Cq
         a = AzAttnBwdArgs()
-        a.q, a.k, a.v, a.out, a.dout = qk.ptr, qk.ptr + 4 * Cq, qkv.ptr + 4 * offs[2], out.ptr, g.ptr
-        a.dq, a.dk, a.dv = dqk.ptr, dqk.ptr + 4 * Cq, dqkv.ptr + 4 * offs[2]
+        a.q, a.k, a.v, a.out, a.dout = qt.ptr + 4 * qo, qt.ptr + 4 * ko, qkv.ptr + 4 * offs[2], out.ptr, g.ptr
+        a.dq, a.dk, a.dv = dqt.ptr + 4 * qo, dqt.ptr + 4 * ko, dqkv.ptr + 4 * offs[2]
         a.workspace = self.empty(2 * B * heads * L).data_ptr()
         a.batch, a.heads, a.tokens, a.head_dim, a.scale = B, heads, L, dim, rec["scale"]
-        for n, t, h in (("q", qk, dim), ("k", qk, dim), ("v", qkv, hs), ("o", out, dim), ("do", g, dim), ("dq", dqk, dim), ("dk", dqk, dim),
-                        ("dv", dqkv, hs)):
-            setattr(a, n + "_bstride", L * t.cs)
-            setattr(a, n + "_tstride", t.cs)
-            setattr(a, n + "_hstride", h)
+        _token_strides(a, L, q=(qt, qh), k=(qt, qh), v=(qkv, hs), o=(out, dim), do=(g, dim), dq=(dqt, qh), dk=(dqt, qh), dv=(dqkv, hs))
         if rec["mask"] is not None:
             m8, mb, mh = rec["mask"]
             a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
         a._flops = 16 * B * heads * L * L * dim
-        self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qk.buf, qkv.buf, out.buf, rec["mask"]])
-        self.wrote(dqk, bounded=False)
+        self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qt.buf, qkv.buf, out.buf, rec["mask"]])
+        if qk is None:
+            return self.wrote(dqkv, bounded=False)
+        dqk = self.wrote(dqt, bounded=False)
         cos, sin = rec["rope"] if rec["rope"] is not None else (None, None)
         args = (dqkv.ptr + 4 * offs[0], dqkv.ptr + 4 * offs[1], dqk.ptr, dqk.ptr + 4 * Cq, qkv.ptr + 4 * offs[0],
                 qkv.ptr + 4 * offs[1], B, L, heads,
@@ -973,64 +1009,9 @@ class Builder:
         self.free(dqk)
         return self.wrote(dqkv, bounded=False)
 
-    def _attention_bwd_in_place(self, g: Act, rec: dict, dqkv: Act) -> Act:
-        from ._lib import AzAttnBwdArgs
-
-        qkv, out, heads, dim, offs, hs = rec["qkv"], rec["out"], rec["heads"], rec["dim"], rec["offs"], rec["hs"]
-        B, L = qkv.B, qkv.H * qkv.W
-        a = AzAttnBwdArgs()
-        a.q, a.k, a.v = (qkv.ptr + 4 * o for o in offs)
-        a.dq, a.dk, a.dv = (dqkv.ptr + 4 * o for o in offs)
-        a.out, a.dout = out.ptr, g.ptr
-        a.workspace = self.empty(2 * B * heads * L).data_ptr()
-        a.batch, a.heads, a.tokens, a.head_dim, a.scale = B, heads, L, dim, rec["scale"]
-        for n, t, h in (("q", qkv, hs), ("k", qkv, hs), ("v", qkv, hs), ("o", out, dim), ("do", g, dim), ("dq", dqkv, hs), ("dk", dqkv, hs),
-                        ("dv", dqkv, hs)):
-            setattr(a, n + "_bstride", L * t.cs)
-            setattr(a, n + "_tstride", t.cs)
-            setattr(a, n + "_hstride", h)
-        if rec["mask"] is not None:
-            m8, mb, mh = rec["mask"]
-            a.mask, a.mask_bstride, a.mask_hstride = m8.data_ptr(), mb, mh
-        a._flops = 16 * B * heads * L * L * dim
-        self.tape.add("az_attention_bwd_f32", C.byref(a), keep=[a, qkv.buf, out.buf, rec["mask"]])
-        return self.wrote(dqkv, bounded=False)
-
-    # -- input gradient of the ADM norm pass (csrc/backward_adm.hip) ------------------------------------------------------
-    def group_norm_keep(self, x: Act, groups: int, *, weight=None, bias=None, scale=None, shift=None, scale_off=0, shift_off=0,
-                        bstride=0, act=0, pool=0, eps=1e-5, x1: Act | None = None) -> tuple[Act, dict]:
-        r"""The forward of :meth:`group_norm` (``y = pool(act((GN(x | x1) w + b) (1 + scale) + shift))``, the sources read in
-        place) with what :meth:`group_norm_keep_bwd` reads kept: the statistics pass always runs over ``x | x1`` and its records,
-        the ``S | T`` tables, ``x`` and ``x1`` stay alive.  No pre-activation is kept: the pullback recomputes ``act'`` from x."""
-        assert not x.half and self.half is None
-        B, HW = x.B, x.H * x.W
-        x1p, c0s, C_, cs = None, 0, x.C, x.cs
-        if x1 is not None:
-            assert x.C == x.cs and x1.C == x1.cs and (x1.B, x1.H, x1.W) == (x.B, x.H, x.W)
-            x1p, c0s, C_, cs = x1.ptr, x.cs, x.C + x1.C, x.cs + x1.cs
-        ST = self.empty(2 * B * cs)
-        S, T = ST[: B * cs], ST[B * cs :]
-        nchunks = int(min(512, max(1, (HW * cs * 4) // 65536)))
-        partials = self.empty(B * nchunks * groups * 4)
-        self.tape.add("az_groupnorm_stats_f32", partials.data_ptr(), x.ptr, x1p, c0s, B, HW, C_, cs, groups, nchunks)
-        f = AzNormFinalizeArgs()
-        f.partials, f.S, f.T = partials.data_ptr(), S.data_ptr(), T.data_ptr()
-        f.weight = weight.data_ptr() if weight is not None else None
-        f.bias = bias.data_ptr() if bias is not None else None
-        f.scale = scale.data_ptr() + 4 * scale_off if scale is not None else None
-        f.shift = shift.data_ptr() + 4 * shift_off if shift is not None else None
-        f.scale_bstride = bstride
-        f.B, f.C, f.cs, f.groups, f.nchunks, f.eps = B, C_, cs, groups, nchunks, eps
-        self.tape.add("az_groupnorm_finalize_f32", C.byref(f), keep=[f, weight, bias, scale, shift])
-        y = self.new_act(B, x.H // 2 if pool == 1 else x.H, x.W // 2 if pool else x.W, C_)
-        assert y.cs == cs
-        self.tape.add("az_affine_act_f32", y.ptr, x.ptr, x1p, c0s, S.data_ptr(), T.data_ptr(), B, x.H, x.W, cs, act, pool)
-        rec = dict(x=x, x1=x1, c0s=c0s, C=C_, cs=cs, ST=ST, partials=partials, nchunks=nchunks, groups=groups, eps=eps, weight=weight,
-                   scale=scale, scale_off=scale_off, bstride=bstride, act=act, pool=pool)
-        return self.wrote(y, bounded=True), rec
-
+    # -- input gradient of the ADM norm pass (csrc/backward_adm.hip; the forward is group_norm(saved=)) ------------------------------------------------------
     def group_norm_keep_bwd(self, g: Act, rec: dict, *, res0: Act | None = None, res1: Act | None = None) -> tuple[Act, Act | None]:
-        r"""Cotangent ``g`` of :meth:`group_norm_keep`'s output (on the pooled grid) -> the cotangents of ``x`` and ``x1``, plus
+        r"""Cotangent ``g`` of the output of :meth:`group_norm` with ``saved=rec`` (on the pooled grid) -> the cotangents of ``x`` and ``x1``, plus
         ``res0`` / ``res1`` (a tensor consumed twice: its cotangents add): ``az_norm_affine_bwd_{stats,apply}_f32``."""
         x, x1, cs, groups = rec["x"], rec["x1"], rec["cs"], rec["groups"]
         B, HW = x.B, x.H * x.W
@@ -1065,12 +1046,13 @@ class Builder:
         self.tape.add("az_axpby_f32", y.ptr, one.data_ptr(), a.ptr, one.data_ptr(), b.ptr, 1, a.B * a.H * a.W * a.cs, 0, keep=[one])
         return self.wrote(y, bounded=False)
 
-    def avgpool(self, x: Act, pool: int) -> Act:
-        r"""The pooling-only pass of ADMPlan (``az_affine_act_f32`` with S = 1, T = 0)."""
-        B = x.B
-        y = self.new_act(B, x.H // 2 if pool == 1 else x.H, x.W // 2, x.C)
+    def avgpool(self, x: Act, pool: int, depth: int = 1) -> Act:
+        r"""The pooling-only pass of the ADM plans (the elementwise pass with S = 1, T = 0; ``pool`` as in :meth:`group_norm`).
+        ``depth``: ``x`` holds B volumes of ``depth`` planes each, pooled in-plane -- a sample is one (depth H) x W image."""
+        B = x.B // depth
         ones, zeros = self.const(torch.ones(B * x.cs)), self.const(torch.zeros(B * x.cs))
-        return self._affine_act(y, x, None, 0, ones.data_ptr(), zeros.data_ptr(), B, x.H, x.W, x.cs, 0, pool, bounded=False)
+        y = self.new_act(x.B, x.H // 2 if pool == 1 else x.H, x.W // 2, x.C)
+        return self._affine_act(y, x, None, 0, ones.data_ptr(), zeros.data_ptr(), B, depth * x.H, x.W, x.cs, 0, pool, bounded=False)
 
     def avgpool_bwd(self, g: Act, pool: int, H: int, W: int, res: Act | None = None) -> Act:
         r"""Pullback of :meth:`avgpool` onto the (H, W) grid, plus ``res``."""
@@ -1115,9 +1097,11 @@ class Builder:
     ) -> Act:
         r"""y = act((GN(x)*w + b) * (1 + scale) + shift), optionally 2x2 average pooled.  With ``x1`` the
         input is the channel concatenation [x | x1], read in place (never materialised).  ``saved``: a dict that receives what
-        :meth:`group_norm_bwd` needs (the statistics pass always runs then: its records are the saved statistics)."""
+        :meth:`group_norm_bwd` and :meth:`group_norm_keep_bwd` read (fp32 plans): the statistics pass always runs then, and its
+        records, the ``S | T`` tables, ``x`` and ``x1`` must stay alive for the pullback.  No pre-activation is kept: the pullbacks
+        recompute ``act'`` from x."""
         B, HW = x.B, x.H * x.W
-        x1p, c0s = None, 0
+        x1p, c0s, x0 = None, 0, x
         srcs = [x] + ([x1] if x1 is not None else [])
         src_quads = [self.fact(s, s.gn_quads) for s in srcs]
         src_channels = [s.C for s in srcs]
@@ -1146,8 +1130,9 @@ class Builder:
                 self.tape.add("az_groupnorm_stats_f32", partials.data_ptr(), x.ptr, x1p, c0s, B, HW, x.C, x.cs, groups, nchunks)
             f.partials = partials.data_ptr()
             if saved is not None:
-                assert x1 is None and not x.half
-                saved.update(partials=partials, nchunks=nchunks, groups=groups, eps=eps)
+                assert not x.half and self.half is None
+                saved.update(x=x0, x1=x1, c0s=c0s, C=x.C, cs=x.cs, ST=ST, partials=partials, nchunks=nchunks, groups=groups, eps=eps,
+                             weight=weight, scale=scale, scale_off=scale_off, bstride=bstride, act=act, pool=pool)
         f.S, f.T = S.data_ptr(), T.data_ptr()
         f.weight = weight.data_ptr() if weight is not None else None
         f.bias = bias.data_ptr() if bias is not None else None
@@ -1207,23 +1192,13 @@ class Builder:
         a.io_dtype = int(qkv.half)  # (q, k, v, out in the module's 2-byte type: the bf16 / f16 entries only)
         es = 2 if qkv.half else 4
         base = qkv.ptr
-        if order in ("nHC", "3HC"):
-            offs, hs = (0, Cq, 2 * Cq), dim
-        elif order == "H3C":
-            offs, hs = (0, dim, 2 * dim), 3 * dim
-        else:
-            raise ValueError(order)
+        offs, hs = qkv_layout(order, Cq, dim)
         a.q, a.k, a.v, a.out = base + es * offs[0], base + es * offs[1], base + es * offs[2], out.ptr
         a.batch, a.heads, a.tokens, a.head_dim = qkv.B, heads, L, dim
-        for n in ("q", "k", "v"):
-            setattr(a, n + "_bstride", L * qkv.cs)
-            setattr(a, n + "_tstride", qkv.cs)
-            setattr(a, n + "_hstride", hs)
-        a.o_bstride, a.o_tstride, a.o_hstride = L * out.cs, out.cs, dim
+        _token_strides(a, L, q=(qkv, hs), k=(qkv, hs), v=(qkv, hs), o=(out, dim))
         a.scale, a.qk_rmsnorm, a.eps, a.norm_dim = scale, int(qk_rmsnorm), eps, norm_dim
         # q / k RMS-normalised here or by the projection's epilogue (qk_rmsnorm is the layer's flag either way), with gains in range
-        kmax, qsmax = attention_qk_bound(dim, norm_dim, scale, qk_weight) if qk_rmsnorm else (math.inf, math.inf)
-        qk_normed = kmax < ATTN_H2_K_MAX and qsmax < ATTN_H2_QS_MAX
+        qk_normed = qk_in_h2_domain(qk_rmsnorm, dim, norm_dim, scale, qk_weight)
         if qkv.qk_prepared:  # the projection's epilogue has normalised / gained / rotated q and k already (Builder.conv(qk_prep=...))
             assert order in ("nHC", "3HC")
             a.qk_rmsnorm, rope, qk_weight = 0, None, None
@@ -1233,17 +1208,9 @@ class Builder:
         if qk_weight is not None:  # learned (dim,) gains of the q / k RMS norms
             a.q_weight, a.k_weight = qk_weight[0].data_ptr(), qk_weight[1].data_ptr()
             self.tape.keep.extend(qk_weight)
-        if mask is not None:  # (L, L), (B | 1, 1 | H, L, L) boolean: True = attend (reference attention.py:97-104)
-            m = mask
-            if m.ndim == 2:
-                m = m[None, None]
-            if m.ndim != 4 or m.shape[-2:] != (L, L) or m.shape[0] not in (1, qkv.B) or m.shape[1] not in (1, heads):
-                raise ValueError(f"attention mask of shape {tuple(mask.shape)} does not broadcast to ({qkv.B}, {heads}, {L}, {L})")
-            m8 = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        if mask is not None:
+            m8, a.mask_bstride, a.mask_hstride = self._attn_mask(mask, qkv.B, heads, L)
             a.mask = m8.data_ptr()
-            a.mask_bstride = m8.stride(0) if m.shape[0] > 1 else 0
-            a.mask_hstride = m8.stride(1) if m.shape[1] > 1 else 0
-            self.tape.keep.append(m8)
         a._flops = 4 * qkv.B * heads * L * L * dim
         self.tape.add(choose_attention(dim, qk_normed, self.half), C.byref(a), keep=[a])
         return self.wrote(out, bounded=False)  # (a convex combination of the values: as large as the weights make them)

@@ -17,13 +17,15 @@ parameters; the forward is a compiled tape of C-ABI kernels on a channel-padded 
 
 from __future__ import annotations
 
+import math
 from collections.abc import Sequence
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-from ..engine import Act, Builder, Tape, ada_zero_triple, mod_front_tape, pad4
+from ..engine import Act, Builder, Tape, ada_zero_triple, mod_front_tape, mod_rows, pad4, param_versions
+from ..gradplan import _GradTapes
 from .. import _lib, engine
 
 __all__ = ["UNet", "UNetBlock"]
@@ -100,24 +102,34 @@ class UNetBlock(nn.Module):
 
         self._plans: dict = {}
 
-    def _emit(self, bld: Builder, x: Act, D: int, mod_rows: int, mod_jobs: list, keep_input: bool = False) -> Act:
+    def _emit(self, bld: Builder, x: Act, D: int, mod_rows: int, mod_jobs: list, keep_input: bool = False,
+              saved: dict | None = None) -> Act:
         r"""y = (a + 1) norm(x) + b;  y = conv(silu(conv(y)));  out = x + c y   (reference ``unet.py:85-95``): one
-        statistics + one scale/shift pass, two convolutions with SiLU / gate / residual in their epilogues."""
+        statistics + one scale/shift pass, two convolutions with SiLU / gate / residual in their epilogues.
+
+        ``saved``: a dict that receives what :meth:`_emit_bwd` reads, kept alive -- the input ``x``, the GroupNorm statistics and
+        the PRE-activation ``h``.  The forward-keep form takes no lazy norm and no epilogue moments, runs the first convolution
+        without its SiLU epilogue and SiLU as a pass of its own behind it, and hands neither ``x`` nor ``h`` back to the pool."""
+        keep = saved is not None
         Cc, cs = self.channels, pad4(self.channels)
         abc, bstride = ada_zero_triple(bld, self.ada_zero, Cc, D, mod_rows, mod_jobs)
+        gn = {} if keep else None
         if self.norm_kind == "group":
-            n_ = bld.group_norm(x, self.groups, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride, lazy=True)
+            n_ = bld.group_norm(x, self.groups, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride, lazy=not keep, saved=gn)
         else:
             n_ = bld.row_norm(x, 0 if self.norm_kind == "layer" else 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
         c0, c3 = self.ffn[0], self.ffn[3]
         # (its moments bound the maximum of SiLU(conv) for the second convolution's f16x2 scale: no pass over the hidden tensor)
-        h1 = bld.conv(n_, bld.pack_conv(c0.weight, c0.bias), c0.out_channels, act=1, periodic=self.periodic,
-                      gn_stats=engine.moments_for_scale())
+        h = bld.conv(n_, bld.pack_conv(c0.weight, c0.bias), c0.out_channels, act=0 if keep else 1, periodic=self.periodic,
+                     gn_stats=not keep and engine.moments_for_scale())
         bld.free(n_)
-        y = bld.conv(h1, bld.pack_conv(c3.weight, c3.bias), c3.out_channels, gate=abc, gate_off=2 * cs, gate_bstride=bstride,
-                     res=x, periodic=self.periodic, gn_stats=self.norm_kind == "group")  # feeds the next block's norm
-        bld.free(h1)
-        if not keep_input:
+        a1 = bld.silu(h) if keep else h
+        y = bld.conv(a1, bld.pack_conv(c3.weight, c3.bias), c3.out_channels, gate=abc, gate_off=2 * cs, gate_bstride=bstride,
+                     res=x, periodic=self.periodic, gn_stats=not keep and self.norm_kind == "group")  # feeds the next block's norm
+        bld.free(a1)
+        if keep:
+            saved.update(x=x, abc=abc, bstride=bstride, gn=gn, h=h)
+        elif not keep_input:
             bld.free(x)
         return y
 
@@ -127,27 +139,6 @@ class UNetBlock(nn.Module):
             raise NotImplementedError("UNetBlock.vjp: spatial = 1 / 2 with zero padding only")
         if any(p.dtype != torch.float32 for p in self.parameters()):
             raise NotImplementedError("UNetBlock.vjp: fp32 parameters only")
-
-    def _emit_keep(self, bld: Builder, x: Act, D: int, mod_rows: int, mod_jobs: list) -> tuple[Act, dict]:
-        r"""The forward of :meth:`_emit` with what the pullback needs kept alive: the input ``x``, the GroupNorm statistics
-        and the PRE-activation ``h`` (the first convolution runs without its SiLU epilogue; SiLU is a pass of its own in
-        front of the second).  ``x`` and ``h`` are never handed back to the pool."""
-        Cc, cs = self.channels, pad4(self.channels)
-        abc, bstride = ada_zero_triple(bld, self.ada_zero, Cc, D, mod_rows, mod_jobs)
-        saved = {"x": x, "abc": abc, "bstride": bstride}
-        if self.norm_kind == "group":
-            saved["gn"] = {}
-            n_ = bld.group_norm(x, self.groups, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride, saved=saved["gn"])
-        else:
-            n_ = bld.row_norm(x, 0 if self.norm_kind == "layer" else 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
-        c0, c3 = self.ffn[0], self.ffn[3]
-        h = bld.conv(n_, bld.pack_conv(c0.weight, c0.bias), c0.out_channels)
-        bld.free(n_)
-        a1 = bld.silu(h)
-        y = bld.conv(a1, bld.pack_conv(c3.weight, c3.bias), c3.out_channels, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
-        bld.free(a1)
-        saved["h"] = h
-        return y, saved
 
     def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict) -> Act:
         r"""Cotangent of the block's output -> cotangent of its input: g2 = c g; g3 = dgrad(conv2)(g2); g4 = g3 silu'(h);
@@ -187,22 +178,16 @@ class UNetBlock(nn.Module):
         assert x.ndim == 4 and x.shape[1] == self.channels
         B, Cc, H, W = x.shape
         D = self.mod_features
-        rows = 0
-        if D > 0:
-            assert mod is not None, "this block is modulated: pass mod"
-            rows = 1 if mod.ndim == 1 else mod.shape[0]
-            assert rows in (1, B)
-        key = ("vjp", B, H, W, rows, str(x.device))
-        versions = tuple((p.data_ptr(), p._version, p.dtype) for p in self.parameters())
-        plan = self._plans.get(key)
-        if plan is None or plan.versions != versions:
+
+        def make(rows: int, versions: tuple) -> _GradTapes:
             plan = _GradTapes(x.device, B, Cc, Cc, H, W, rows, D, versions)
             bld = plan.bld
             xin = bld.new_act(B, H, W, Cc, pinned=True)
             plan.fwd.add("az_nchw_to_nhwc_f32", xin.ptr, plan.x_in.data_ptr(), None, B, Cc, H * W, xin.cs)
             bld.wrote(xin, bounded=False)
             jobs: list = []
-            out, saved = self._emit_keep(bld, xin, D, rows, jobs)
+            saved: dict = {}
+            out = self._emit(bld, xin, D, rows, jobs, saved=saved)
             bld.tape.add("az_nhwc_to_nchw_f32", plan.out.data_ptr(), out.ptr, B, Cc, H * W, out.cs)
             plan.end_forward(jobs)
             g = bld.new_act(B, H, W, Cc, pinned=True)
@@ -211,97 +196,71 @@ class UNetBlock(nn.Module):
             dx = self._emit_bwd(bld, g, saved, {})
             bld.tape.add("az_nhwc_to_nchw_f32", plan.dx.data_ptr(), dx.ptr, B, Cc, H * W, dx.cs)
             plan.end_backward()
-            self._plans[key] = plan
-        out, pullback = plan.run(x, mod)
+            return plan
+
+        out, pullback = self._cached_plan(x, mod, make, vjp=True)[0].run(x, mod)
         if one_d:
             return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
         return out, pullback
 
-    def _forward_3d(self, x: Tensor, mod: Tensor | None, out_dtype) -> Tensor:
-        r"""(B, C, D, H, W): one-block plan on the volume form (see ``unet3d.py``)."""
-        from .unet3d import Vol, block3d
-
-        assert x.ndim == 5 and x.shape[1] == self.channels
-        B, Cc, Dd, H, W = x.shape
-        D = self.mod_features
-        rows = 0
-        if D > 0:
-            assert mod is not None, "this block is modulated: pass mod"
-            rows = 1 if mod.ndim == 1 else mod.shape[0]
-            assert rows in (1, B)
-        key = (B, Dd, H, W, rows, str(x.device))
-        versions = tuple((p.data_ptr(), p._version, p.dtype) for p in self.parameters())
+    def _cached_plan(self, x: Tensor, mod: Tensor | None, make, vjp: bool = False):
+        r"""(plan, modulation rows) of this block for ``x`` (B, C, *dims) and ``mod``: the cached plan while the parameters are what
+        it was built for, else ``make(rows, versions)``.  A forward plan (a tuple that starts with its versions) replaces every
+        cached plan; a gradient plan lives beside them under a ``"vjp"`` key."""
+        rows = mod_rows(mod, x.shape[0], self.mod_features, "block")
+        key = (*(("vjp",) if vjp else ()), x.shape[0], *x.shape[2:], rows, str(x.device))
+        versions = param_versions(self)
         plan = self._plans.get(key)
-        if plan is None or plan[0] != versions:
-            bld = Builder(x.device, half=next(self.parameters()).dtype)
-            xa = bld.new_act(B * Dd, H, W, Cc, pinned=True)
-            xin = Vol(xa, B, Dd)
-            mod_buf = torch.empty(max(rows, 1), max(D, 1), dtype=torch.float32, device=x.device)
-            jobs: list = []
-            out = block3d(self, bld, xin, D, rows, jobs, keep_input=True)
-            bld.finish()
-            tape = bld.tape
-            if jobs:
-                tape = mod_front_tape(bld, jobs, mod_buf, rows, D)
-                tape.extend(bld.tape)
-            res = torch.empty(B, Cc, Dd, H, W, dtype=torch.float32, device=x.device)
-            tape.add("az_nhwc_to_nchw_f32", res.data_ptr(), out.buf.data_ptr(), B, Cc, Dd * H * W, out.cs)
-            plan = (versions, xin, mod_buf, tape, res)
-            self._plans.clear()
-            self._plans[key] = plan
-        _, xin, mod_buf, tape, res = plan
-        xs = x.to(torch.float32).contiguous()
-        _lib.call("az_nchw_to_nhwc_f32", xin.buf.data_ptr(), xs.data_ptr(), None, B, Cc, Dd * H * W, xin.cs, _lib.stream_ptr())
-        if rows:
-            mod_buf.copy_(mod.to(torch.float32).reshape(rows, -1))
-        tape.run()
-        return res.to(out_dtype, copy=True)
+        if plan is None or (plan.versions if vjp else plan[0]) != versions:
+            if not vjp:
+                self._plans.clear()
+            plan = self._plans[key] = make(rows, versions)
+        return plan, rows
 
     @torch.no_grad()
     @_lib.on_device
     def forward(self, x: Tensor, mod: Tensor | None = None) -> Tensor:
-        r"""x: (B, C, H, W) [(B, C, L) for spatial = 1]; mod: (D) or (B, D) -> like x (reference ``unet.py:97-116``)."""
+        r"""x: (B, C, H, W) [(B, C, L) for spatial = 1, (B, C, D, H, W) for spatial = 3]; mod: (D) or (B, D) -> like x
+        (reference ``unet.py:97-116``)."""
         from .utils import backbone_io_dtype
 
         out_dtype = backbone_io_dtype(self, x, "azula_amd.nn.UNetBlock")
         if self.spatial == 1:  # (B, C, L): the same kernels and the same plan cache on a one-row image (no module state is touched)
             assert x.ndim == 3
-            return self._forward_2d(x[:, :, None], mod, out_dtype)[:, :, 0]
-        if self.spatial == 3:
-            return self._forward_3d(x, mod, out_dtype)
-        return self._forward_2d(x, mod, out_dtype)
+            return self._forward_nd(x[:, :, None], mod, out_dtype)[:, :, 0]
+        return self._forward_nd(x, mod, out_dtype)
 
-    def _forward_2d(self, x: Tensor, mod: Tensor | None, out_dtype) -> Tensor:
-        assert x.ndim == 4 and x.shape[1] == self.channels
-        B, Cc, H, W = x.shape
+    def _forward_nd(self, x: Tensor, mod: Tensor | None, out_dtype) -> Tensor:
+        r"""(B, C, H, W) images, or (B, C, D, H, W) volumes as B D planes on the volume form (see ``unet3d.py``): a one-block plan."""
+        vol = self.spatial == 3
+        assert x.ndim == (5 if vol else 4) and x.shape[1] == self.channels
+        B, Cc, *dims = x.shape
+        planes, (H, W) = (dims[0] if vol else 1), dims[-2:]
         D = self.mod_features
-        rows = 0
-        if D > 0:
-            assert mod is not None, "this block is modulated: pass mod"
-            rows = 1 if mod.ndim == 1 else mod.shape[0]
-            assert rows in (1, B)
-        key = (B, H, W, rows, str(x.device))
-        versions = tuple((p.data_ptr(), p._version, p.dtype) for p in self.parameters())
-        plan = self._plans.get(key)
-        if plan is None or plan[0] != versions:
+
+        def make(rows: int, versions: tuple) -> tuple:
             bld = Builder(x.device, half=next(self.parameters()).dtype)
-            xin = bld.new_act(B, H, W, Cc, pinned=True)
+            xin = bld.new_act(B * planes, H, W, Cc, pinned=True)
             mod_buf = torch.empty(max(rows, 1), max(D, 1), dtype=torch.float32, device=x.device)
             jobs: list = []
-            out = self._emit(bld, xin, D, rows, jobs, keep_input=True)
+            if vol:
+                from .unet3d import Vol, block3d
+
+                out = block3d(self, bld, Vol(xin, B, planes), D, rows, jobs, keep_input=True)
+            else:
+                out = self._emit(bld, xin, D, rows, jobs, keep_input=True)
             bld.finish()
             tape = bld.tape
             if jobs:
                 tape = mod_front_tape(bld, jobs, mod_buf, rows, D)
                 tape.extend(bld.tape)
-            res = torch.empty(B, Cc, H, W, dtype=torch.float32, device=x.device)
-            tape.add("az_nhwc_to_nchw_f32", res.data_ptr(), out.ptr, B, Cc, H * W, out.cs)
-            plan = (versions, xin, mod_buf, tape, res)
-            self._plans.clear()
-            self._plans[key] = plan
-        _, xin, mod_buf, tape, res = plan
+            res = torch.empty(B, Cc, *dims, dtype=torch.float32, device=x.device)
+            tape.add("az_nhwc_to_nchw_f32", res.data_ptr(), out.buf.data_ptr(), B, Cc, math.prod(dims), out.cs)
+            return (versions, xin, mod_buf, tape, res)
+
+        (_, xin, mod_buf, tape, res), rows = self._cached_plan(x, mod, make)
         xs = x.to(torch.float32).contiguous()
-        _lib.call("az_nchw_to_nhwc_f32", xin.ptr, xs.data_ptr(), None, B, Cc, H * W, xin.cs, _lib.stream_ptr())
+        _lib.call("az_nchw_to_nhwc_f32", xin.ptr, xs.data_ptr(), None, B, Cc, math.prod(dims), xin.cs, _lib.stream_ptr())
         if rows:
             mod_buf.copy_(mod.to(torch.float32).reshape(rows, -1))
         tape.run()
@@ -342,65 +301,8 @@ class UNetPlan:
         self.mod_rows = mod_rows
         self.out = torch.empty(B, net.out_channels, H, W, dtype=torch.float32, device=device)
         self.versions = net._param_versions()
-        L = len(net.hid_blocks)
-        stride = net.stride
-        # power-of-two strides (<= 16): the decoder's nearest upsampling is a right shift inside the merge convolution's gather;
-        # any other stride: a nearest-upsampling pass of its own in front of the merge convolution (reference unet.py:186,250-254)
-        sv = (stride, stride) if isinstance(stride, int) else tuple(stride)
-        pow2 = all(v in (1, 2, 4, 8, 16) for v in sv)
-        up = 0
-        if pow2:
-            up = stride.bit_length() - 1 if isinstance(stride, int) else tuple(v.bit_length() - 1 for v in stride)
-
         mod_jobs: list[tuple] = []  # queued modulation MLPs (ada_zero_triple), emitted together at the tape front
-        per = net.periodic
-        gn = any(isinstance(m, UNetBlock) and m.norm_kind == "group" for m in net.modules())
-
-        def block(blk: UNetBlock, x: Act, keep_input: bool) -> Act:
-            return blk._emit(bld, x, D, mod_rows, mod_jobs, keep_input)
-
-        cur = self.x_in
-        skips: list[Act] = []
-        for i in range(L):
-            first = net.descent[i][0]
-            if i > 0:
-                skips.append(cur)  # output of level i-1 = memory entry (unet.py:226-230)
-            if i == 0 and self.planar:
-                nxt = bld.conv_stem(cur.buf, B, cin, H, W, bld.pack_conv(first.weight, first.bias), first.out_channels, periodic=per,
-                                    gn_stats=gn)
-            else:
-                nxt = bld.conv(cur, bld.pack_conv(first.weight, first.bias), first.out_channels, stride=stride if i > 0 else 1,
-                               periodic=per, gn_stats=gn)
-            cur = nxt
-            for j in range(net.hid_blocks[i]):
-                cur = block(net.descent[i][1 + j], cur, keep_input=False)
-        for k in range(L):
-            i = L - 1 - k
-            mods = net.ascent[k]
-            idx = 0
-            if i + 1 < L:
-                y = skips[i]
-                conv = mods[0]
-                if not pow2:
-                    wide = bld.upsample_nearest(cur, sv[0], sv[1], y.H, y.W)
-                    bld.free(cur)
-                    cur = wide
-                merged = bld.conv(
-                    y, bld.pack_conv(conv.weight, conv.bias, cin0=y.C), conv.out_channels, src1=cur, up1=up,
-                    hin=y.H, win=y.W, periodic=per, gn_stats=gn,
-                )
-                bld.free(cur)
-                bld.free(y)
-                cur = merged
-                idx = 1
-            for j in range(net.hid_blocks[i]):
-                cur = block(mods[idx + j], cur, keep_input=False)
-            idx += net.hid_blocks[i]
-            if i == 0:
-                conv = mods[idx]
-                bld.conv(cur, bld.pack_conv(conv.weight, conv.bias), conv.out_channels, dst_nchw=self.out, periodic=per)
-                bld.free(cur)
-            # i > 0: nearest upsampling is folded into the next level's merge conv (up1 = log2 stride)
+        _walk(net, bld, self.x_in, self.out, mod_rows, mod_jobs, planar=self.planar)
         bld.finish()
         self.tape = bld.tape
         if mod_jobs:  # h_i = silu(W0_i mod + b0_i) for all blocks as ONE GEMV; abc_i = W2_i h_i + b2_i as ONE grouped GEMV
@@ -409,131 +311,94 @@ class UNetPlan:
             self.tape = pre
 
 
-class _GradTapes:
-    r"""The two tapes of a gradient plan and their static planar buffers.  *forward-keep* (``fwd``): ``x_in`` (planar) ->
-    ``out`` (planar) with every tensor the pullback reads kept alive; *backward* (``bwd``): ``v_in`` (the cotangent of the
-    output, planar) -> ``dx`` (the cotangent of the input, planar).  The backward tape only writes temporaries of its own, so it
-    runs any number of times after one forward-keep run.  Plain ``Tape.run`` on the current stream: no graph capture."""
+def _walk(net: "UNet", bld: Builder, cur: Act, out: Tensor, mod_rows: int, mod_jobs: list, *, planar: bool = False,
+          keep: bool = False) -> tuple:
+    r"""The network from the input Act ``cur`` to the planar output ``out``: descent with the skip list (reference
+    unet.py:226-230), ascent with the merge convolutions reading ``cat((skip, upsampled))`` in place.  ``planar``: ``cur`` is the
+    planar latent, read by ``Builder.conv_stem``.  ``keep``: the forward-keep tape of a gradient plan -- blocks in their keep form
+    (``UNetBlock._emit(saved=)``), no convolution-epilogue moments, the last block's output not released.  Returns what the
+    backward walk reads: per level the (block, record) pairs of descent and ascent and the map sizes, and the last convolution."""
+    L, D, stride = len(net.hid_blocks), net.mod_features, net.stride
+    # power-of-two strides (<= 16): the decoder's nearest upsampling is a right shift inside the merge convolution's gather;
+    # any other stride: a nearest-upsampling pass of its own in front of the merge convolution (reference unet.py:186,250-254)
+    sv = (stride, stride) if isinstance(stride, int) else tuple(stride)
+    pow2 = all(v in (1, 2, 4, 8, 16) for v in sv)
+    up = 0
+    if pow2:
+        up = stride.bit_length() - 1 if isinstance(stride, int) else tuple(v.bit_length() - 1 for v in stride)
+    per = net.periodic
+    gn = not keep and any(isinstance(m, UNetBlock) and m.norm_kind == "group" for m in net.modules())
 
-    def __init__(self, device, B: int, cin: int, cout: int, H: int, W: int, mod_rows: int, D: int, versions, tokens: bool = False) -> None:
-        self.versions = versions
-        self.bld = Builder(device)
-        if tokens:  # (B, L, C) token plans: the four buffers are views of the plan's own activations (DiTGradPlan / vit.py)
-            self.x_in = self.out = self.v_in = self.dx = None
+    def blocks(mods, x: Act) -> tuple[Act, list]:
+        recs = []
+        for blk in mods:
+            saved = {} if keep else None
+            x = blk._emit(bld, x, D, mod_rows, mod_jobs, saved=saved)
+            recs.append((blk, saved))
+        return x, recs
+
+    skips: list[Act] = []
+    down, upr, sizes = [], {}, []
+    for i in range(L):
+        first = net.descent[i][0]
+        if i > 0:
+            skips.append(cur)  # output of level i-1 = memory entry (unet.py:226-230)
+        if i == 0 and planar:
+            cur = bld.conv_stem(cur.buf, cur.B, cur.C, cur.H, cur.W, bld.pack_conv(first.weight, first.bias), first.out_channels,
+                                periodic=per, gn_stats=gn)
         else:
-            self.x_in = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
-            self.out = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
-            self.v_in = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
-            self.dx = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
-        self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
-        self.mod_rows, self.D = mod_rows, D
-        self.fwd = self.bld.tape  # (the builder records onto it until end_forward)
-        self.bwd: Tape | None = None
-        self.serial = 0  # forward-keep runs so far: a pullback belongs to one of them
-
-    def end_forward(self, mod_jobs: list) -> None:
-        if mod_jobs:
-            pre = mod_front_tape(self.bld, mod_jobs, self.mod, self.mod_rows, self.D)
-            pre.extend(self.fwd)
-            self.fwd = pre
-        self.bld.tape = Tape()
-
-    def end_backward(self) -> None:
-        self.bld.finish()  # (one split-K workspace for both tapes)
-        self.bwd = self.bld.tape
-        self.bwd.keep.append(self.fwd)
-
-    @property
-    def saved_bytes(self) -> int:
-        return self.bld.pool.bytes
-
-    def run(self, x: Tensor, mod: Tensor | None):
-        self.x_in.copy_(x)
-        if self.mod_rows:
-            self.mod.copy_(mod.to(torch.float32).reshape(self.mod_rows, -1))
-        self.fwd.run()
-        self.serial += 1
-        serial = self.serial
-
-        @torch.no_grad()
-        def pullback(v: Tensor) -> Tensor:
-            if serial != self.serial:
-                raise RuntimeError("this pullback belongs to an earlier vjp call on the same module and shapes: its saved "
-                                   "tensors have been overwritten")
-            if not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != tuple(self.out.shape):
-                raise ValueError(f"pullback: expected an fp32 device tensor of shape {tuple(self.out.shape)}")
-            with torch.cuda.device(self.v_in.device):
-                self.v_in.copy_(v)
-                self.bwd.run()
-                return self.dx.clone()
-
-        return self.out.clone(), pullback
+            cur = bld.conv(cur, bld.pack_conv(first.weight, first.bias), first.out_channels, stride=stride if i > 0 else 1,
+                           periodic=per, gn_stats=gn)
+        sizes.append((cur.H, cur.W))
+        cur, recs = blocks(net.descent[i][1 : 1 + net.hid_blocks[i]], cur)
+        down.append(recs)
+    for k in range(L):
+        i = L - 1 - k
+        mods = net.ascent[k]
+        idx = 0
+        if i + 1 < L:
+            y = skips[i]
+            conv = mods[0]
+            if not pow2:
+                wide = bld.upsample_nearest(cur, sv[0], sv[1], y.H, y.W)
+                bld.free(cur)
+                cur = wide
+            merged = bld.conv(
+                y, bld.pack_conv(conv.weight, conv.bias, cin0=y.C), conv.out_channels, src1=cur, up1=up,
+                hin=y.H, win=y.W, periodic=per, gn_stats=gn,
+            )
+            bld.free(cur)  # (outputs of a level's last block: no pullback reads them)
+            bld.free(y)
+            cur = merged
+            idx = 1
+        cur, upr[i] = blocks(mods[idx : idx + net.hid_blocks[i]], cur)
+        # i > 0: nearest upsampling is folded into the next level's merge conv (up1 = log2 stride)
+    last = net.ascent[L - 1][idx + net.hid_blocks[0]]
+    bld.conv(cur, bld.pack_conv(last.weight, last.bias), last.out_channels, dst_nchw=out, periodic=per)
+    if not keep:
+        bld.free(cur)
+    return down, upr, sizes, last
 
 
 class UNetGradPlan(_GradTapes):
     r"""Gradient plan of a :class:`UNet` for one (batch, H, W, modulation-rows) signature: the forward-keep and backward tapes
-    (see :class:`_GradTapes`).  A different plan from :class:`UNetPlan`, whose launches it leaves untouched: no lazy
-    normalisation, no convolution-epilogue moments, SiLU as a pass of its own behind the kept pre-activation."""
+    (see :class:`_GradTapes`).  The forward-keep tape is :class:`UNetPlan`'s walk in its keep form (:func:`_walk`), a different
+    tape from that plan's, whose launches it leaves untouched: no lazy normalisation, no convolution-epilogue moments, SiLU as a
+    pass of its own behind the kept pre-activation."""
 
     def __init__(self, net: "UNet", B: int, H: int, W: int, mod_rows: int, device: torch.device) -> None:
         cin, D = net.in_channels, net.mod_features
         super().__init__(device, B, cin, net.out_channels, H, W, mod_rows, D, net._param_versions())
         bld = self.bld
         L = len(net.hid_blocks)
-        stride = net.stride
-        sv = (stride, stride) if isinstance(stride, int) else tuple(stride)
-        pow2 = all(v in (1, 2, 4, 8, 16) for v in sv)
-        up = 0
-        if pow2:
-            up = stride.bit_length() - 1 if isinstance(stride, int) else tuple(v.bit_length() - 1 for v in stride)
+        sv = (net.stride, net.stride) if isinstance(net.stride, int) else tuple(net.stride)
         mod_jobs: list[tuple] = []
 
-        # ---- forward-keep: the order of UNetPlan, nothing the pullback reads is released
+        # ---- forward-keep: the walk of UNetPlan, nothing the pullback reads is released
         cur = bld.new_act(B, H, W, cin, pinned=True)
         bld.tape.add("az_nchw_to_nhwc_f32", cur.ptr, self.x_in.data_ptr(), None, B, cin, H * W, cur.cs)
         bld.wrote(cur, bounded=False)
-        skips: list[Act] = []
-        down: list[list[dict]] = []  # per level: the saved records of its descent blocks
-        sizes: list[tuple] = []  # per level: (H, W) of its maps
-        for i in range(L):
-            first = net.descent[i][0]
-            if i > 0:
-                skips.append(cur)
-            cur = bld.conv(cur, bld.pack_conv(first.weight, first.bias), first.out_channels, stride=stride if i > 0 else 1)
-            sizes.append((cur.H, cur.W))
-            recs = []
-            for j in range(net.hid_blocks[i]):
-                cur, rec = net.descent[i][1 + j]._emit_keep(bld, cur, D, mod_rows, mod_jobs)
-                recs.append((net.descent[i][1 + j], rec))
-            down.append(recs)
-        upr: dict[int, list] = {}
-        for k in range(L):
-            i = L - 1 - k
-            mods = net.ascent[k]
-            idx = 0
-            if i + 1 < L:
-                y = skips[i]
-                conv = mods[0]
-                if not pow2:
-                    wide = bld.upsample_nearest(cur, sv[0], sv[1], y.H, y.W)
-                    bld.free(cur)
-                    cur = wide
-                merged = bld.conv(y, bld.pack_conv(conv.weight, conv.bias, cin0=y.C), conv.out_channels, src1=cur, up1=up,
-                                  hin=y.H, win=y.W)
-                bld.free(cur)  # (outputs of a level's last block: no pullback reads them)
-                bld.free(y)
-                cur = merged
-                idx = 1
-            recs = []
-            for j in range(net.hid_blocks[i]):
-                cur, rec = mods[idx + j]._emit_keep(bld, cur, D, mod_rows, mod_jobs)
-                recs.append((mods[idx + j], rec))
-            upr[i] = recs
-            idx += net.hid_blocks[i]
-            if i == 0:
-                conv = mods[idx]
-                bld.conv(cur, bld.pack_conv(conv.weight, conv.bias), conv.out_channels, dst_nchw=self.out)
-                last = conv
+        down, upr, sizes, last = _walk(net, bld, cur, self.out, mod_rows, mod_jobs, keep=True)
         self.end_forward(mod_jobs)
 
         # ---- backward: the same graph walked from the output to the input
@@ -635,7 +500,7 @@ class UNet(nn.Module):
 
     # -- plan management -----------------------------------------------------------------------
     def _param_versions(self) -> tuple:
-        return tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
+        return param_versions(self)
 
     def plan3d(self, B: int, D: int, H: int, W: int, mod_rows: int, device: torch.device):
         from .unet3d import UNet3DPlan
@@ -683,11 +548,7 @@ class UNet(nn.Module):
             x = x[:, :, None]
         B, Cin, H, W = x.shape
         assert Cin == self.in_channels
-        rows = 0
-        if self.mod_features > 0:
-            assert mod is not None, "this UNet is modulated: pass mod"
-            rows = 1 if mod.ndim == 1 else mod.shape[0]
-            assert rows in (1, B)
+        rows = mod_rows(mod, B, self.mod_features, "UNet")
         out, pullback = self.grad_plan(B, H, W, rows, x.device).run(x, mod)
         if one_d:
             return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
@@ -747,17 +608,12 @@ class UNet(nn.Module):
         assert x.ndim == 5, "spatial = 3: expected (B, C, D, H, W)"
         B, Cin, D, H, W = x.shape
         assert Cin == self.in_channels + self.cond_channels
-        rows = 0
-        if self.mod_features > 0:
-            assert mod is not None, "this UNet is modulated: pass mod"
-            mod = mod.to(torch.float32)
-            rows = 1 if mod.ndim == 1 else mod.shape[0]
-            assert rows in (1, B)
+        rows = mod_rows(mod, B, self.mod_features, "UNet")
         p = self.plan3d(B, D, H, W, rows, x.device)
         s = _lib.stream_ptr()
         _lib.call("az_nchw_to_nhwc_f32", p.x_in.buf.data_ptr(), x.data_ptr(), None, B, Cin, D * H * W, p.x_in.cs, s)
         if rows:
-            p.mod.copy_(mod.reshape(rows, -1))
+            p.mod.copy_(mod.to(torch.float32).reshape(rows, -1))
         p.tape.run(s)
         return p.out.to(out_dtype, copy=True)
 
@@ -778,13 +634,7 @@ class UNet(nn.Module):
             return self._forward_3d(x, mod, out_dtype)
         B, Cin, H, W = x.shape
         assert Cin == self.in_channels + self.cond_channels
-        if self.mod_features > 0:
-            assert mod is not None, "this UNet is modulated: pass mod"
-            mod = mod.to(torch.float32)
-            rows = 1 if mod.ndim == 1 else mod.shape[0]
-            assert rows in (1, B)
-        else:
-            rows = 0
+        rows = mod_rows(mod, B, self.mod_features, "UNet")
         p = self.plan(B, H, W, rows, x.device)
         s = _lib.stream_ptr()
         if p.planar:
@@ -792,7 +642,7 @@ class UNet(nn.Module):
         else:
             _lib.call("az_nchw_to_nhwc_f32", p.x_in.ptr, x.data_ptr(), None, B, Cin, H * W, p.x_in.cs, s)
         if rows:
-            p.mod.copy_(mod.reshape(rows, -1))
+            p.mod.copy_(mod.to(torch.float32).reshape(rows, -1))
         p.tape.run(s)
         out = p.out.to(out_dtype, copy=True)
         return out[:, :, 0] if self.spatial == 1 else out

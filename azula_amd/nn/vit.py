@@ -29,8 +29,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _lib, engine
-from ..engine import Act, Builder, LinearView, Tape, ada_zero_triple, mod_front_tape, pad4
-from .unet import _GradTapes
+from ..engine import Act, Builder, LinearView, SharedResidual, ada_zero_triple, mod_front_tape, mod_rows, pad4, param_versions
+from ..gradplan import _TokenGradTapes
 
 __all__ = ["DiT", "DiTBlock", "MultiheadSelfAttention", "ViT"]
 
@@ -65,49 +65,20 @@ class MultiheadSelfAttention(nn.Module):
         self.qk_norm = qk_norm
         self._plans: dict = {}
 
-    def _emit(self, bld: Builder, y: Act, pos_h: Tensor | None, mask: Tensor | None, res: Act | None = None) -> Act:
-        r"""qkv projection -> attention (q/k RMS norm, RoPE, mask in the kernel) -> y_proj (+ ``res``)."""
-        C_ = self.qkv_proj.in_features
-        rope = None
-        if self.theta_proj is not None:  # theta = theta_proj(pos) on the host (reference op order), tables on device
-            if pos_h is None:
-                raise ValueError("this attention layer uses RoPE: pass pos")
-            theta = torch.nn.functional.linear(pos_h.to(torch.float32).cpu(), self.theta_proj.weight.detach().float().cpu())
-            rope = (bld.const(torch.cos(theta)), bld.const(torch.sin(theta)))
-        # with RoPE: q / k RMS norm and the rotation in the projection's epilogue, once per layer (C6-like: attention 0.38 -> 0.49 of
-        # the MFMA peak).  The RMS norm alone stays in the attention kernel: measured on DiT-B/2 (C3) the kernel gains 7 % but the
-        # captured step loses 0.4 % (23.77 vs 23.67 ms, two rounds each) -- a norm of the staged K rows is nearly free there.
-        d = C_ // self.heads
-        dp = engine.attn_padded_dim(d, bld.half)
-        if dp != d:  # a head size the kernels are not instantiated for: zero-padded heads (engine.ATTN_HEAD_DIMS; G24)
-            if rope is not None:
-                theta_p = engine.pad_head_table(theta, self.heads, d // 2, dp // 2)
-                rope = (bld.const(torch.cos(theta_p)), bld.const(torch.sin(theta_p)))
-            wq, bq = engine.pad_qkv_heads(self.qkv_proj.weight, self.qkv_proj.bias, self.heads, d, dp, "nHC")
-            qkv = bld.conv(y, bld.pack_conv(wq, bq), 3 * self.heads * dp)
-            att = bld.attention(qkv, self.heads, "nHC", self.qk_norm, 1.0 / math.sqrt(d), rope=rope, mask=mask, norm_dim=d)
-            bld.free(qkv)
-            out = bld.conv(att, bld.pack_conv(engine.pad_proj_heads(self.y_proj.weight, self.heads, d, dp), None), C_, res=res)
-            bld.free(att)
-            return out
-        prep = dict(heads=self.heads, head_dim=d, rmsnorm=self.qk_norm, eps=1e-5, rope=rope) if rope else None
-        qkv = bld.conv(y, bld.pack_conv(self.qkv_proj.weight, self.qkv_proj.bias), 3 * C_, qk_prep=prep)
-        att = bld.attention(qkv, self.heads, "nHC", self.qk_norm, 1.0 / math.sqrt(d), rope=rope, mask=mask)
-        bld.free(qkv)
-        out = bld.conv(att, bld.pack_conv(self.y_proj.weight, None), C_, res=res)
-        bld.free(att)
-        return out
+    def _emit(self, bld: Builder, y: Act, pos_h: Tensor | None, mask: Tensor | None, res: Act | None = None,
+              saved: dict | None = None) -> Act:
+        r"""qkv projection -> attention (q/k RMS norm, RoPE, mask in the kernel) -> y_proj (+ ``res``).  A head size the kernels are
+        not instantiated for runs zero-padded to the next one (engine.ATTN_HEAD_DIMS; G24).
 
-    # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
-    def _emit_keep(self, bld: Builder, y: Act, pos_h: Tensor | None, mask: Tensor | None, res: Act | None = None) -> tuple[Act, dict]:
-        r"""The forward of :meth:`_emit` with what the pullback reads kept: the raw ``qkv``, q^ | k^ and the attention output
-        in front of ``y_proj`` (``Builder.attention_keep``).  The projection runs without the q / k epilogue; head sizes other
-        than 16 / 32 / 64 / 128 run zero-padded to the next of these (``engine.attn_grad_padded_dim``)."""
+        ``saved``: a dict that receives what :meth:`_emit_bwd` reads, kept alive -- the raw ``qkv``, q^ | k^ and the attention
+        output in front of ``y_proj`` (``Builder.attention_keep``).  The forward-keep form runs the projection without the q / k
+        epilogue and pads heads to the sizes of the backward kernels (``engine.attn_grad_padded_dim``)."""
+        keep = saved is not None
         C_ = self.qkv_proj.in_features
         d = C_ // self.heads
-        dp = engine.attn_grad_padded_dim(d)
+        dp = engine.attn_grad_padded_dim(d) if keep else engine.attn_padded_dim(d, bld.half)
         theta = None
-        if self.theta_proj is not None:
+        if self.theta_proj is not None:  # theta = theta_proj(pos) on the host (reference op order), tables on device
             if pos_h is None:
                 raise ValueError("this attention layer uses RoPE: pass pos")
             theta = torch.nn.functional.linear(pos_h.to(torch.float32).cpu(), self.theta_proj.weight.detach().float().cpu())
@@ -118,12 +89,25 @@ class MultiheadSelfAttention(nn.Module):
             wq, bq = engine.pad_qkv_heads(wq, bq, self.heads, d, dp, "nHC")
             wy = engine.pad_proj_heads(wy, self.heads, d, dp)
         rope = None if theta is None else (bld.const(torch.cos(theta)), bld.const(torch.sin(theta)))
-        qkv = bld.conv(y, bld.pack_conv(wq, bq), 3 * self.heads * dp)
-        att, rec = bld.attention_keep(qkv, self.heads, self.qk_norm, 1.0 / math.sqrt(d), rope=rope, mask=mask,
-                                      norm_dim=d if dp != d else 0)
+        scale, norm_dim = 1.0 / math.sqrt(d), (d if dp != d else 0)
+        if keep:
+            qkv = bld.conv(y, bld.pack_conv(wq, bq), 3 * self.heads * dp)
+            att, rec = bld.attention_keep(qkv, self.heads, self.qk_norm, scale, rope=rope, mask=mask, norm_dim=norm_dim)
+            saved.update(attn=rec, wq=LinearView(wq), wy=LinearView(wy))
+        else:
+            # with RoPE: q / k RMS norm and the rotation in the projection's epilogue, once per layer (C6-like: attention 0.38 -> 0.49
+            # of the MFMA peak).  The RMS norm alone stays in the attention kernel: measured on DiT-B/2 (C3) the kernel gains 7 % but
+            # the captured step loses 0.4 % (23.77 vs 23.67 ms, two rounds each) -- a norm of the staged K rows is nearly free there.
+            prep = dict(heads=self.heads, head_dim=d, rmsnorm=self.qk_norm, eps=1e-5, rope=rope) if rope and dp == d else None
+            qkv = bld.conv(y, bld.pack_conv(wq, bq), 3 * self.heads * dp, qk_prep=prep)
+            att = bld.attention(qkv, self.heads, "nHC", self.qk_norm, scale, rope=rope, mask=mask, norm_dim=norm_dim)
+            bld.free(qkv)
         out = bld.conv(att, bld.pack_conv(wy, None), C_, res=res)
-        return out, {"attn": rec, "wq": LinearView(wq), "wy": LinearView(wy)}
+        if not keep:
+            bld.free(att)
+        return out
 
+    # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
     def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict, res: Act | None = None) -> Act:
         r"""Cotangent of the layer's output -> cotangent of its input (+ ``res`` in the epilogue of the qkv data-gradient GEMM)."""
         g_att = bld.conv_dgrad(g, saved["wy"], cache=cache)
@@ -143,7 +127,8 @@ class MultiheadSelfAttention(nn.Module):
 
         def build(plan, xin, pos_h):
             bld = plan.bld
-            out, saved = self._emit_keep(bld, xin, pos_h, mask)
+            saved: dict = {}
+            out = self._emit(bld, xin, pos_h, mask, saved=saved)
             plan.set_output(out)
             plan.end_forward([])
             g = plan.cotangent(out.C)
@@ -185,7 +170,7 @@ class _TokenPlan:
 
     def __init__(self, module: nn.Module, B: int, L: int, Cin: int, pos_h, mod_rows: int, D: int, emit, device) -> None:
         bld = self.bld = Builder(device, half=next(module.parameters()).dtype, half_act=_half_act_ok(module) and Cin % 8 == 0)
-        self.versions = _versions(module)
+        self.versions = param_versions(module)
         self.x_in = bld.new_act(B, L, 1, Cin, pinned=True)
         self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
         self.mod_jobs: list = []
@@ -213,25 +198,21 @@ class _TokenPlan:
         return o.buf.view(B, L, o.cs)[..., : o.C].reshape(*x.shape[:-1], o.C).clone()
 
 
-def _versions(module: nn.Module) -> tuple:
-    return tuple((p.data_ptr(), p._version, p.dtype) for p in module.parameters())
-
-
-def _token_plan(module, x: Tensor, pos, mask, D: int, emit, mod: Tensor | None = None) -> _TokenPlan:
-    r"""Plan cache of a standalone token module, keyed on shapes, positions, mask content and parameter versions."""
+def _cached_token_plan(module, x: Tensor, pos, mask, D: int, mod: Tensor | None, make, vjp: bool = False):
+    r"""Plan cache of a standalone token module, keyed on shapes, positions, mask content and parameter versions (gradient plans
+    under a ``"vjp"`` key beside the forward ones).  ``make(B, L, Cin, rows, pos_h, versions)`` builds a missing or stale plan."""
     assert x.ndim >= 2, "expected (*, L, C) tokens"
     L, Cin = x.shape[-2], x.shape[-1]
     B = x.numel() // (L * Cin)
-    rows = 0
-    if D > 0:
-        assert mod is not None, "this block is modulated: pass mod"
-        rows = 1 if mod.ndim == 1 else mod.numel() // mod.shape[-1]
-        assert rows in (1, B), "mod must be (D) or (*, D) with the leading shape of x"
+    rows = mod_rows(mod, B, D, "block", tokens=True)
     # Positions and mask are BAKED into the plan (RoPE tables, mask bytes).  The key holds their CONTENT (bytes compare by
     # value: no hash-collision reuse); a tensor already seen -- same storage, shape and version counter -- is recognised
-    # without copying it to the host again, so a steady-state forward does not synchronise the device.
+    # without copying it to the host again, so a steady-state call does not synchronise the device.
     def ident(t):
         return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), str(t.dtype), str(t.device))
+
+    def host(t):
+        return None if t is None else t.detach().to("cpu", torch.float32).reshape(L, -1)
 
     seen = module.__dict__.setdefault("_plan_seen", {})
     ik = (ident(pos), ident(mask))
@@ -239,22 +220,25 @@ def _token_plan(module, x: Tensor, pos, mask, D: int, emit, mod: Tensor | None =
     content = hit[0] if hit is not None and hit[1] is pos and hit[2] is mask else None
     pos_h = None
     if content is None:
-        pos_h = None if pos is None else pos.detach().to("cpu", torch.float32).reshape(L, -1)
+        pos_h = host(pos)
         content = (None if pos_h is None else pos_h.numpy().tobytes(),
                    None if mask is None else (tuple(mask.shape), mask.detach().cpu().numpy().tobytes()))
         if len(seen) >= 2:
             seen.clear()
         seen[ik] = (content, pos, mask)
-    key = (B, L, Cin, rows, str(x.device), content)
+    key = (*(("vjp",) if vjp else ()), B, L, Cin, rows, str(x.device), content)
+    versions = param_versions(module)
     plan = module._plans.get(key)
-    if plan is None or plan.versions != _versions(module):
-        if plan is not None or len(module._plans) >= 4:
+    if plan is None or plan.versions != versions:
+        if not vjp and (plan is not None or len(module._plans) >= 4):
             module._plans.clear()  # stale parameters, or more than a few live (positions, mask) variants
-        if pos_h is None and pos is not None:
-            pos_h = pos.detach().to("cpu", torch.float32).reshape(L, -1)
-        plan = _TokenPlan(module, B, L, Cin, pos_h, rows, D, emit, x.device)
-        module._plans[key] = plan
+        plan = module._plans[key] = make(B, L, Cin, rows, host(pos) if pos_h is None else pos_h, versions)
     return plan
+
+
+def _token_plan(module, x: Tensor, pos, mask, D: int, emit, mod: Tensor | None = None) -> _TokenPlan:
+    return _cached_token_plan(module, x, pos, mask, D, mod,
+                              lambda B, L, Cin, rows, pos_h, versions: _TokenPlan(module, B, L, Cin, pos_h, rows, D, emit, x.device))
 
 
 def _vjp_scope(module: nn.Module, x: Tensor, name: str) -> None:
@@ -269,71 +253,14 @@ def _vjp_scope(module: nn.Module, x: Tensor, name: str) -> None:
             engine.attn_grad_padded_dim(m.qkv_proj.in_features // m.heads)  # (raises NotImplementedError above 128)
 
 
-class _TokenGradTapes(_GradTapes):
-    r""":class:`_GradTapes` on (B, L, C) token tensors: ``x_in`` / ``out`` / ``v_in`` / ``dx`` are views of the plan's own
-    (channel-padded) activations, so nothing is rearranged on the way in or out."""
-
-    def __init__(self, device, B: int, L: int, cin: int, mod_rows: int, D: int, versions) -> None:
-        super().__init__(device, B, cin, cin, L, 1, mod_rows, D, versions, tokens=True)
-        self.B, self.L = B, L
-
-    def _pinned(self, channels: int) -> Act:
-        a = self.bld.new_act(self.B, self.L, 1, channels, pinned=True)
-        a.buf.zero_()  # (the pad lanes stay zero: only the real channels are ever copied in)
-        return self.bld.wrote(a, bounded=False)
-
-    def _view(self, a: Act) -> Tensor:
-        return a.buf.view(self.B, self.L, a.cs)[..., : a.C]
-
-    def token_input(self, channels: int) -> Act:
-        a = self._pinned(channels)
-        self.x_in = self._view(a)
-        return a
-
-    def cotangent(self, channels: int) -> Act:
-        a = self._pinned(channels)
-        self.v_in = self._view(a)
-        return a
-
-    def set_output(self, out: Act) -> None:
-        out.pinned = True
-        self.out = self._view(out)
-
-    def set_dx(self, dx: Act) -> None:
-        dx.pinned = True
-        self.dx = self._view(dx)
-        self.end_backward()
-
-    def run(self, x: Tensor, mod: Tensor | None):
-        lead = tuple(x.shape[:-2])  # (standalone modules take (*, L, C))
-        out, pull = super().run(x.reshape(self.B, self.L, -1), mod)
-        if lead == (self.B,):
-            return out, pull
-        return out.reshape(*lead, self.L, -1), lambda v: pull(v.reshape(self.B, self.L, -1)).reshape(*lead, self.L, -1)
-
-
 def _token_grad_plan(module, x: Tensor, pos, mask, D: int, mod: Tensor | None, build) -> _TokenGradTapes:
-    r"""Gradient-plan cache of a standalone token module, keyed on shapes, the content of positions and mask, and parameter
-    versions.  ``build(plan, x_in, pos_h)`` emits both tapes."""
-    assert x.ndim >= 2, "expected (*, L, C) tokens"
-    L, Cin = x.shape[-2], x.shape[-1]
-    B = x.numel() // (L * Cin)
-    rows = 0
-    if D > 0:
-        assert mod is not None, "this block is modulated: pass mod"
-        rows = 1 if mod.ndim == 1 else mod.numel() // mod.shape[-1]
-        assert rows in (1, B), "mod must be (D) or (*, D) with the leading shape of x"
-    pos_h = None if pos is None else pos.detach().to("cpu", torch.float32).reshape(L, -1)
-    content = (None if pos_h is None else pos_h.numpy().tobytes(),
-               None if mask is None else (tuple(mask.shape), mask.detach().cpu().numpy().tobytes()))
-    key = ("vjp", B, L, Cin, rows, str(x.device), content)
-    versions = _versions(module)
-    plan = module._plans.get(key)
-    if plan is None or plan.versions != versions:
+    r"""The gradient plan of a standalone token module from the same cache; ``build(plan, x_in, pos_h)`` emits both tapes."""
+    def make(B, L, Cin, rows, pos_h, versions):
         plan = _TokenGradTapes(x.device, B, L, Cin, rows, D, versions)
         build(plan, plan.token_input(Cin), pos_h)
-        module._plans[key] = plan
-    return plan
+        return plan
+
+    return _cached_token_plan(module, x, pos, mask, D, mod, make, vjp=True)
 
 
 class DiTBlock(nn.Module):
@@ -370,51 +297,45 @@ class DiTBlock(nn.Module):
         )
         self._plans: dict = {}
 
-    def _emit(self, bld: Builder, x: Act, pos_h, mask, D: int, mod_rows: int, mod_jobs: list, keep_input: bool = False) -> Act:
-        r"""y = (a + 1) RMSNorm(x) + b;  y = y + MSA(y);  y = FFN(y);  out = x + c y   (reference ``dit.py:95-112``)."""
+    _ACT_KIND = {"silu": 1, "relu": 2, "relu2": 3}
+
+    def _emit(self, bld: Builder, x: Act, pos_h, mask, D: int, mod_rows: int, mod_jobs: list, keep_input: bool = False,
+              saved: dict | None = None) -> Act:
+        r"""y = (a + 1) RMSNorm(x) + b;  y = y + MSA(y);  y = FFN(y);  out = x + c y   (reference ``dit.py:95-112``).
+
+        ``saved``: a dict that receives what :meth:`_emit_bwd` reads, kept alive -- the block input ``x``, the attention layer's
+        record and the FFN PRE-activation ``h`` (``ffn[0]`` then runs without its activation epilogue; the activation is a pass of
+        its own behind it).  The modulated norm output and ``y2`` are only read by weight gradients, which an input gradient
+        does not need: they go back to the pool either way."""
+        keep = saved is not None
         C_, cs = self.channels, pad4(self.channels)
         abc, bstride = ada_zero_triple(bld, self.ada_zero, C_, D, mod_rows, mod_jobs)
         y = bld.row_norm(x, 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
-        y2 = self.msa._emit(bld, y, pos_h, mask, res=y)
+        msa = {} if keep else None
+        y2 = self.msa._emit(bld, y, pos_h, mask, res=y, saved=msa)
         bld.free(y)
         f0, f3 = self.ffn[0], self.ffn[3]
-        code = {"silu": 1, "relu": 2, "relu2": 3, "swiglu": 0}[self.ffn_activation]
-        fused_glu = self.ffn_activation == "swiglu" and f0.out_features % 8 == 0  # SwiGLU in the GEMM's epilogue (act = 4)
-        f1 = bld.conv(y2, bld.pack_conv(f0.weight, f0.bias), f0.out_features, act=4 if fused_glu else code)
+        glu = self.ffn_activation == "swiglu"  # x1 * silu(x2) over interleaved pairs (layers.py:107-110)
+        if keep or glu:  # the activation behind the GEMM, or SwiGLU in its epilogue (act = 4) where the width allows
+            code = 4 if glu and not keep and f0.out_features % 8 == 0 else 0
+        else:
+            code = self._ACT_KIND[self.ffn_activation]
+        h = bld.conv(y2, bld.pack_conv(f0.weight, f0.bias), f0.out_features, act=code)
         bld.free(y2)
-        if self.ffn_activation == "swiglu" and not fused_glu:  # x1 * silu(x2) over interleaved pairs (layers.py:107-110)
-            glu = bld.new_act(f1.B, f1.H, f1.W, f1.C // 2)
-            bld.tape.add("az_swiglu_f32", glu.ptr, f1.ptr, f1.B * f1.H * f1.W, f1.C // 2, f1.cs, glu.cs)
-            bld.wrote(glu, bounded=False)
-            bld.free(f1)
-            f1 = glu
-        out = bld.conv(f1, bld.pack_conv(f3.weight, f3.bias), C_, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
-        bld.free(f1)
-        if not keep_input:
+        a1 = h
+        if code == 0:
+            a1 = bld.swiglu(h) if glu else bld.act(h, self._ACT_KIND[self.ffn_activation])
+            if not keep:
+                bld.free(h)
+        out = bld.conv(a1, bld.pack_conv(f3.weight, f3.bias), C_, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
+        bld.free(a1)
+        if keep:
+            saved.update(x=x, abc=abc, bstride=bstride, msa=msa, h=h, f0=LinearView(f0.weight), f3=LinearView(f3.weight))
+        elif not keep_input:
             bld.free(x)
         return out
 
     # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
-    _ACT_KIND = {"silu": 1, "relu": 2, "relu2": 3}
-
-    def _emit_keep(self, bld: Builder, x: Act, pos_h, mask, D: int, mod_rows: int, mod_jobs: list) -> tuple[Act, dict]:
-        r"""The forward of :meth:`_emit` with what the pullback reads kept alive: the block input ``x``, the attention layer's
-        record (raw qkv, q^ | k^, attention output) and the FFN PRE-activation ``h`` (``ffn[0]`` runs without its activation
-        epilogue; the activation is a pass of its own behind it).  The modulated norm output and ``y2`` are only read by
-        weight gradients, which an input gradient does not need: they go back to the pool."""
-        C_, cs = self.channels, pad4(self.channels)
-        abc, bstride = ada_zero_triple(bld, self.ada_zero, C_, D, mod_rows, mod_jobs)
-        y = bld.row_norm(x, 1, scale=abc, shift=abc, scale_off=0, shift_off=cs, bstride=bstride)
-        y2, msa = self.msa._emit_keep(bld, y, pos_h, mask, res=y)
-        bld.free(y)
-        f0, f3 = self.ffn[0], self.ffn[3]
-        h = bld.conv(y2, bld.pack_conv(f0.weight, f0.bias), f0.out_features)
-        bld.free(y2)
-        a1 = bld.swiglu(h) if self.ffn_activation == "swiglu" else bld.act(h, self._ACT_KIND[self.ffn_activation])
-        out = bld.conv(a1, bld.pack_conv(f3.weight, f3.bias), C_, gate=abc, gate_off=2 * cs, gate_bstride=bstride, res=x)
-        bld.free(a1)
-        return out, {"x": x, "abc": abc, "bstride": bstride, "msa": msa, "h": h, "f0": LinearView(f0.weight), "f3": LinearView(f3.weight)}
-
     def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict) -> Act:
         r"""Cotangent of the block's output -> cotangent of its input: g_f = c g; g_y2 = ffn^T g_f; g_y = g_y2 + msa^T g_y2 (the
         add in the qkv data-gradient GEMM's epilogue); dx = g + norm^T g_y (``az_rownorm_bwd_f32`` with ``res = g``)."""
@@ -449,7 +370,8 @@ class DiTBlock(nn.Module):
         def build(plan, xin, pos_h):
             bld = plan.bld
             jobs: list = []
-            out, saved = self._emit_keep(bld, xin, pos_h, mask, D, plan.mod_rows, jobs)
+            saved: dict = {}
+            out = self._emit(bld, xin, pos_h, mask, D, plan.mod_rows, jobs, saved=saved)
             plan.set_output(out)
             plan.end_forward(jobs)
             g = plan.cotangent(out.C)
@@ -483,6 +405,21 @@ def host_sine_encoding(x: Tensor, features: int, omega: float) -> Tensor:
     return torch.cat((torch.sin(x * freqs), torch.cos(x * freqs)), dim=-1)
 
 
+def _pos_table(net: "DiT", bld: Builder, pos: Tensor, L: int) -> Act:
+    r"""The batch-shared positional embedding table (L, C) in fp32: host sine encoding -> one GEMM, run here at build time on a
+    builder of its own, which the plan's tape keeps alive with the table."""
+    C_ = net.hid_channels
+    enc = host_sine_encoding(pos.to(torch.float32).cpu(), C_, omega=1e2).flatten(-2)  # (L, P*C)
+    pb = Builder(bld.device)
+    enc_act = Act(enc.to(bld.device).contiguous().reshape(-1), 1, L, 1, enc.shape[1], enc.shape[1], True)
+    ptab = pb.conv(enc_act, pb.pack_conv(net.pos_embedding[2].weight, None), C_)
+    pb.finish()
+    pb.tape.run()
+    ptab.pinned = True
+    bld.tape.keep.extend([pb, enc_act, ptab])
+    return ptab
+
+
 class DiTPlan:
     r"""Compiled forward for (batch, tokens[, patch geometry], modulation rows)."""
 
@@ -491,7 +428,7 @@ class DiTPlan:
         D, C_ = net.mod_features, net.hid_channels
         self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
         self.mod_rows = mod_rows
-        self.versions = net._param_versions()
+        self.versions = param_versions(net)
         cin = net.in_proj.in_features
         cout = net.out_proj.out_features
         if patch is not None:
@@ -506,22 +443,14 @@ class DiTPlan:
             self.x_in_buf, self.x_in_cs = tokens.buf, tokens.cs
         self.tokens = tokens
 
-        # positional embedding table (L, C): host sine encoding -> one GEMM at build time
-        enc = host_sine_encoding(pos.to(torch.float32).cpu(), C_, omega=1e2).flatten(-2)  # (L, P*C)
-        pb = Builder(device)
-        enc_act = Act(enc.to(device).contiguous().reshape(-1), 1, L, 1, enc.shape[1], enc.shape[1], True)
-        ptab = pb.conv(enc_act, pb.pack_conv(net.pos_embedding[2].weight, None), C_)
-        pb.finish()
-        pb.tape.run()
+        ptab = _pos_table(net, bld, pos, L)
         if bld.half_act:  # the residual operand of the first GEMM has the destination's element type
             pt = torch.zeros(L, bld.pad(C_), dtype=bld.half, device=device)
             pt[:, :C_] = ptab.buf.view(L, ptab.cs)[:, :C_]
             ptab = Act(pt.reshape(-1), 1, L, 1, C_, bld.pad(C_), True)
         self.pos_table = ptab
-        bld.tape.keep.extend([pb, enc_act])
-        ptab.pinned = True
 
-        x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=_bcast(ptab))
+        x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=SharedResidual(ptab))
         mod_jobs: list[tuple] = []  # queued modulation MLPs of the blocks, emitted together at the tape front
         for blk in net.blocks:
             x = blk._emit(bld, x, pos, None, D, mod_rows, mod_jobs)
@@ -552,23 +481,15 @@ class DiTGradPlan(_TokenGradTapes):
     def __init__(self, net: "DiT", B: int, L: int, pos: Tensor, mod_rows: int, device) -> None:
         D, C_ = net.mod_features, net.hid_channels
         cin, cout = net.in_proj.in_features, net.out_proj.out_features
-        super().__init__(device, B, L, cin, mod_rows, D, net._param_versions())
+        super().__init__(device, B, L, cin, mod_rows, D, param_versions(net))
         bld = self.bld
         tokens = self.token_input(cin)
-        enc = host_sine_encoding(pos.to(torch.float32).cpu(), C_, omega=1e2).flatten(-2)  # (L, P*C), as DiTPlan
-        pb = Builder(device)
-        enc_act = Act(enc.to(device).contiguous().reshape(-1), 1, L, 1, enc.shape[1], enc.shape[1], True)
-        ptab = pb.conv(enc_act, pb.pack_conv(net.pos_embedding[2].weight, None), C_)
-        pb.finish()
-        pb.tape.run()
-        ptab.pinned = True
-        bld.tape.keep.extend([pb, enc_act, ptab])
-
-        x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=_bcast(ptab))
+        x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=SharedResidual(_pos_table(net, bld, pos, L)))
         mod_jobs: list[tuple] = []
         recs = []
         for blk in net.blocks:
-            x, rec = blk._emit_keep(bld, x, pos, None, D, mod_rows, mod_jobs)
+            rec: dict = {}
+            x = blk._emit(bld, x, pos, None, D, mod_rows, mod_jobs, saved=rec)
             recs.append((blk, rec))
         self.set_output(bld.conv(x, bld.pack_conv(net.out_proj.weight, net.out_proj.bias), cout))
         bld.free(x)  # (the last block's output: no pullback reads it)
@@ -583,17 +504,6 @@ class DiTGradPlan(_TokenGradTapes):
         dx = bld.conv_dgrad(g, wi, cache=cache)
         bld.free(g)
         self.set_dx(dx)
-
-
-class _Bcast:
-    r"""Marks a residual Act as batch-shared (conv epilogue ``res_bcast``)."""
-
-    def __init__(self, act: Act) -> None:
-        self.act = act
-
-
-def _bcast(a: Act) -> "_Bcast":
-    return _Bcast(a)
 
 
 class DiT(nn.Module):
@@ -625,25 +535,17 @@ class DiT(nn.Module):
         ])
         self._plans: dict = {}
 
-    def _param_versions(self) -> tuple:
-        return tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-
     def _check_device(self, x: Tensor) -> torch.dtype:
         from .utils import backbone_io_dtype
 
         return backbone_io_dtype(self, x, f"azula_amd.nn.{type(self).__name__}")
 
     def _mod_rows(self, mod, B: int) -> int:
-        if self.mod_features == 0:
-            return 0
-        assert mod is not None, "this network is modulated: pass mod"
-        rows = 1 if mod.ndim == 1 else mod.shape[0]
-        assert rows in (1, B)
-        return rows
+        return mod_rows(mod, B, self.mod_features, "network")
 
     def _get_plan(self, key, make):
         p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
+        if p is None or p.versions != param_versions(self):
             p = make()
             self._plans[key] = p
         return p

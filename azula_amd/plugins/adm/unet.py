@@ -30,8 +30,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder, pad8
-from ...nn.unet import _GradTapes
+from ...engine import Act, Builder, pad8, param_versions
+from ...gradplan import _GradTapes
 
 __all__ = ["UNetModel"]
 
@@ -119,6 +119,291 @@ def timestep_embedding_table(steps: int, dim: int, max_period: int = 10000) -> T
     return emb
 
 
+def _packed(bld: Builder, conv, **kw):
+    r"""Filter of a ConvNd layer; a 3-tap Conv1d becomes the middle row of a 3x3 filter."""
+    w = conv.weight
+    if w.ndim == 3 and w.shape[-1] == 3:
+        w2 = torch.zeros(*w.shape[:2], 3, 3, dtype=w.dtype, device=w.device)
+        w2[:, :, 1, :] = w.detach()
+        w = w2
+    return bld.pack_conv(w, conv.bias, **kw)
+
+
+def _emit_forward(plan, net: "UNetModel", x_in: Act | None, B: int, H: int, W: int, emb_rows: int, *, coef_ptr: int | None = None,
+                  frac: bool = False, D: int = 1, keep: bool = False) -> tuple:
+    r"""The network on ``plan.bld``'s tape, from the input Act ``x_in`` (None: the planar ``plan.x_in`` tensor) to ``plan.out``: the embedding front (time, label), one
+    grouped launch for every ResBlock's FiLM table, encoder / middle / decoder, the output head.  Sets the plan's embedding inputs
+    (``table``, ``t_idx``, ``t_frac``, ``labels``).
+
+    ``keep``: the forward-keep tape of :class:`ADMGradPlan` (``dims`` 1 and 2, fp32).  It keeps, per norm pass, its input and
+    its statistics (``Builder.group_norm(saved=)``: no pre-activation, no SiLU pass of its own -- the pullback recomputes
+    ``silu'`` from the input), per attention block q | k | v and the attention output (``Builder.attention_keep``, heads padded
+    to the backward kernels' sizes, the projections as ``LinearView``s in ``plan._views``); it takes no planar stem and no
+    convolution-epilogue moments, and hands nothing a pullback reads back to the pool.  Returns the per-layer records of the
+    input, middle and output blocks, the head norm's record and the number of skip tensors (empty / None without ``keep``)."""
+    bld, device = plan.bld, plan.bld.device
+    mc, E = net.model_channels, 4 * net.model_channels
+    cin = net.in_channels
+    one_d = net.dims == 1  # (B, C, L) signals: H = 1, every resampling acts along the width alone
+    assert not one_d or H == 1
+    # dims = 3: a (B, C, D, H, W) volume is B * D channel-padded NHWC planes -- every `Act` below has batch PB = B * D.  The
+    # depth axis is never resampled (_src/unet.py:103-104,128: Upsample / Downsample act on the inner two axes), so a
+    # Conv3d is the sum over its depth taps of 2-D convolutions of depth-shifted planes (AzConvArgs.depth, one launch per
+    # tap accumulating through the residual operand, as nn/unet3d.py), the norms and elementwise passes see a sample as
+    # one (D H) x W image (`vol`), the attention blocks as D H W tokens.
+    three_d = net.dims == 3
+    assert (three_d or D == 1) and not (keep and three_d)
+    PB = B * D
+    up2 = (0, 1) if one_d else 1  # log2 of the nearest upsampling per axis
+    down2 = (1, 2) if one_d else 2  # stride per axis
+    pool2 = 2 if one_d else 1  # az_affine_act_f32's pooling mode: 1x2 or 2x2
+    wino = False if one_d else None  # (a one-row map: the direct kernel; F(2x2, 3x3) would compute a second, discarded row)
+    stats = not keep  # GroupNorm moments from the producing convolution's epilogue (a kept norm runs its own statistics pass)
+
+    def vol(a: Act | None) -> Act | None:
+        r"""The B samples of a plane stack as (D H) x W images (same memory); the producing convolution's GroupNorm
+        partials, one set per plane, are D sets per sample."""
+        if a is None or not three_d:
+            return a
+        q = a.gn_quads
+        return a.view(B, D * a.H, gn_quads=(q[0], D * q[1], q[2]) if q is not None else None)
+
+    def planes(a: Act) -> Act:
+        r"""Inverse of `vol` for a pass's result (pooled or not): B (D H') x W' images -> B D planes of H' x W'."""
+        if not three_d:
+            return a
+        return a.view(PB, a.H // D, pinned=a.pinned)
+
+    def group_norm(x: Act, norm: nn.GroupNorm, x1: Act | None = None, **kw) -> tuple[Act, dict | None]:
+        r"""(GroupNorm(32) of x | x1 with the layer's affine, its record in keep mode)."""
+        rec = {} if keep else None
+        y = bld.group_norm(vol(x), 32, weight=bld.const(norm.weight), bias=bld.const(norm.bias), x1=vol(x1), saved=rec, **kw)
+        return planes(y), rec
+
+    def conv(src: Act, layer, cout: int, *, cin0=None, **kw) -> Act | None:
+        r"""conv_nd layer on `src` (| kw["src1"] concatenated).  Conv3d with three depth taps: the centre tap first (it exists for
+        every plane; bias, residual), the others accumulate in place; the moments for a following GroupNorm come from the last."""
+        w = layer.weight
+        if not (three_d and w.ndim == 5 and w.shape[2] > 1):
+            if w.ndim == 5:  # 1 x 1 x 1
+                return bld.conv(src, bld.pack_conv(w[:, :, 0], layer.bias, cin0=cin0), cout, **kw)
+            return bld.conv(src, _packed(bld, layer, cin0=cin0), cout, **kw)
+        assert w.shape[2] == 3
+        gn_stats, dst = kw.pop("gn_stats", False), kw.pop("dst_nchw", None)
+        assert dst is None
+        res, res_up = kw.pop("res", None), kw.pop("res_up", 0)
+        # a depth tap that reads only padding (|j - 1| >= D: a single-plane volume) contributes zero and is not launched; the
+        # moments ride on the LAST tap that is
+        taps = [j for j in (0, 2) if abs(j - 1) < D]
+        out = bld.conv(src, bld.pack_conv(w[:, :, 1], layer.bias, cin0=cin0), cout, res=res, res_up=res_up, depth=(D, 0),
+                       gn_stats=gn_stats and not taps, **kw)
+        for j in taps:
+            bld.conv(src, bld.pack_conv(w[:, :, j], None, cin0=cin0), cout, res=out, out=out, depth=(D, j - 1),
+                     gn_stats=gn_stats and j == taps[-1], **kw)
+        return out
+
+    # ---- embedding: emb = time_embed(t) [+ label_emb(y)]; a constant of the pullback
+    plan.table = bld.const(timestep_embedding_table(net.table_steps, mc))
+    plan.t_idx = torch.zeros(emb_rows, dtype=torch.int64, device=device)
+    plan.t_frac = torch.zeros(emb_rows, dtype=torch.float32, device=device) if frac else None
+    plan.labels = torch.zeros(B, dtype=torch.int64, device=device) if net.num_classes is not None else None
+    temb = bld.empty(emb_rows, mc)
+    row0 = torch.zeros(B, dtype=torch.int64, device=device)  # index vector that replicates a single row per sample
+    bld.tape.keep.append(row0)  # (int64: Builder.const would cast it to fp32 and halve its size)
+    trow = emb_rows
+    if coef_ptr is not None:  # fused sampling: row index = the step's time_index, read on the device
+        assert emb_rows == 1 or net.num_classes is not None
+        bld.tape.add("az_gather_step_row_f32", temb.data_ptr(), plan.table.data_ptr(), coef_ptr, 0, mc, net.table_steps)
+        trow = 1
+    elif frac:  # fractional timesteps (_src/nn.py:90-108 "these may be fractional"): the sinusoid on the device, no table
+        assert mc % 2 == 0, "odd model_channels with fractional timesteps"
+        bld.tape.add("az_timestep_embedding_f32", temb.data_ptr(), mc, plan.t_frac.data_ptr(), 1, emb_rows, mc // 2, 10000.0)
+    else:
+        bld.tape.add("az_gather_rows_f32", temb.data_ptr(), plan.table.data_ptr(), plan.t_idx.data_ptr(), emb_rows, mc, net.table_steps)
+    te0, te2 = net.time_embed[0], net.time_embed[2]
+    hid = bld.empty(trow, E)
+    emb = bld.empty(emb_rows, E)
+    bld.linear_small(hid, E, temb, mc, bld.const(te0.weight), bld.const(te0.bias), trow, E, mc, 0, 1)
+    if net.num_classes is None:
+        bld.linear_small(emb, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), trow, E, E, 0, 0)
+    else:  # emb = time_embed(t) + label_emb(y), per sample (_src/unet.py:621-623)
+        assert emb_rows == B
+        tbase = bld.empty(trow, E)
+        bld.linear_small(tbase, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), trow, E, E, 0, 0)
+        lab = bld.empty(B, E)
+        lw = bld.const(net.label_emb.weight)
+        bld.tape.add("az_gather_rows_f32", lab.data_ptr(), lw.data_ptr(), plan.labels.data_ptr(), B, E, net.num_classes)
+        ones = bld.const(torch.ones(1))
+        if trow == 1 and not keep:  # one time row for all samples (the gradient plan's rows are per sample: at B = 1, tbase itself)
+            tb = bld.empty(B, E)
+            bld.tape.add("az_gather_rows_f32", tb.data_ptr(), tbase.data_ptr(), row0.data_ptr(), B, E, 1)
+            tbase = tb
+        bld.tape.add("az_axpby_f32", emb.data_ptr(), ones.data_ptr(), tbase.data_ptr(), ones.data_ptr(), lab.data_ptr(), 1, B * E, 0)
+    film_at = len(bld.tape.ops)  # every ResBlock's FiLM projection reads only `emb`: one grouped launch here
+    film_jobs: list[tuple] = []
+    if x_in is None:  # the gradient plan's input arrives planar: one layout pass
+        x_in = bld.new_act(B, H, W, cin, pinned=True)
+        bld.tape.add("az_nchw_to_nhwc_f32", x_in.ptr, plan.x_in.data_ptr(), None, B, cin, H * W, x_in.cs)
+        bld.wrote(x_in, bounded=False)
+
+    # ---- layers: (output, record).  None of them frees its inputs
+    def resblock(rb: ResBlock, x: Act, x1: Act | None = None) -> tuple[Act, dict]:
+        r"""x (| x1 concatenated) -> block output."""
+        oc, ocs = rb.out_channels, bld.pad(rb.out_channels)
+        ci, co = rb.in_layers[2], rb.out_layers[3]
+        # FiLM table: emb_layers = SiLU -> Linear(E, 2*oc); (scale | shift) padded to ocs each
+        lin = rb.emb_layers[1]
+        nf = 2 if rb.use_scale_shift_norm else 1  # (scale | shift), or the additive embedding alone
+        w = torch.zeros(nf * ocs, E, dtype=torch.float32, device=device)
+        b_ = torch.zeros(nf * ocs, dtype=torch.float32, device=device)
+        for n in range(nf):
+            w[n * ocs : n * ocs + oc] = lin.weight.detach()[n * oc : (n + 1) * oc]
+            b_[n * ocs : n * ocs + oc] = lin.bias.detach()[n * oc : (n + 1) * oc]
+        film = bld.empty(emb_rows, nf * ocs)
+        film_jobs.append((film, bld.const(w), bld.const(b_), nf * ocs))
+        fbs = nf * ocs if emb_rows > 1 else 0
+        # h = conv(updown(SiLU(GN(x))))
+        n1, r1 = group_norm(x, rb.in_layers[0], x1, act=1, pool=pool2 if rb.down else 0)
+        h = conv(n1, ci, oc, up0=up2 if rb.up else 0, winograd=wino,
+                 gn_stats=stats and rb.use_scale_shift_norm)  # -> out_layers' GroupNorm
+        bld.free(n1)
+        if rb.use_scale_shift_norm:  # h = SiLU(GN(h) * (1 + scale) + shift)
+            n2, r2 = group_norm(h, rb.out_layers[0], scale=film, shift=film, scale_off=0, shift_off=ocs, bstride=fbs, act=1)
+        else:  # h = SiLU(GN(h + emb_out)), _src/unet.py:244-246: the statistics are those of the SUM -> one more pass
+            eb = film
+            if emb_rows == 1 and B > 1:  # the pass wants one row per sample
+                eb = bld.empty(B, ocs)
+                bld.tape.add("az_gather_rows_f32", eb.data_ptr(), film.data_ptr(), row0.data_ptr(), B, ocs, 1)
+            he = bld.new_act(PB, h.H, h.W, oc)
+            bld._affine_act(he, h, None, 0, bld.const(torch.ones(B * ocs)).data_ptr(), eb.data_ptr(), B, D * h.H, h.W, ocs, 0, 0,
+                            bounded=False)
+            if keep:  # (the kept tensor is the sum)
+                bld.free(h)
+            n2, r2 = group_norm(he, rb.out_layers[0], act=1)
+            if not keep:
+                bld.free(he)
+        if not keep:
+            bld.free(h)
+        # skip path
+        assert x1 is None or not (rb.down or rb.up or isinstance(rb.skip_connection, nn.Identity))
+        if rb.down:
+            xs = bld.avgpool(x, pool2, D)
+            out = conv(n2, co, oc, res=xs, gn_stats=stats, winograd=wino)
+            bld.free(xs)
+        elif rb.up:
+            out = conv(n2, co, oc, res=x, res_up=1, gn_stats=stats, winograd=wino)  # (one row: oh >> 1 = 0)
+        elif isinstance(rb.skip_connection, nn.Identity):
+            out = conv(n2, co, oc, res=x, gn_stats=stats, winograd=wino)
+        else:
+            skip = conv(x, rb.skip_connection, oc, cin0=x.C if x1 is not None else None, src1=x1)
+            out = conv(n2, co, oc, res=skip, gn_stats=stats, winograd=wino)
+            bld.free(skip)
+        bld.free(n2)
+        return out, dict(kind="res", rb=rb, r1=r1, r2=r2, x=x, x1=x1)
+
+    def attention(ab: AttentionBlock, x: Act) -> tuple[Act, dict]:
+        Cc = ab.channels
+        n_, rn = group_norm(x, ab.norm)
+        L = D * x.H * x.W
+        tok = n_.view(B, L, 1, Cc)  # (the normalised tokens: the same memory)
+        ch = Cc // ab.num_heads
+        chp = engine.attn_grad_padded_dim(ch) if keep else engine.attn_padded_dim(ch, bld.half)
+        order = "3HC" if ab.new_order else "H3C"
+        wq, bq, wp = ab.qkv.weight, ab.qkv.bias, ab.proj_out.weight
+        if chp != ch:  # a head size the kernels are not instantiated for: zero-padded heads (engine.ATTN_HEAD_DIMS; G24); the
+            wq, bq = engine.pad_qkv_heads(wq, bq, ab.num_heads, ch, chp, order)  # cotangents of the pad lanes meet zero weight columns
+            wp = engine.pad_proj_heads(wp, ab.num_heads, ch, chp)
+        qkv = bld.conv(tok, bld.pack_conv(wq, bq), 3 * ab.num_heads * chp)
+        rec = None
+        if keep:
+            bld.free(n_)
+            att, ra = bld.attention_keep(qkv, ab.num_heads, False, 1.0 / math.sqrt(ch), norm_dim=ch, order=order, skip_prep=True)
+            vq, vp_ = engine.LinearView(wq), engine.LinearView(wp)
+            plan._views += [vq, vp_]
+            rec = dict(kind="attn", rn=rn, ra=ra, vq=vq, vp=vp_, x=x)
+        else:
+            att = bld.attention(qkv, ab.num_heads, order, False, 1.0 / math.sqrt(ch), norm_dim=ch if chp != ch else 0)
+            bld.free(qkv)
+        o = bld.conv(att, bld.pack_conv(wp, ab.proj_out.bias), Cc, res=x.view(B, L, 1, Cc))
+        if not keep:
+            bld.free(att)
+            bld.free(n_)
+        return o.view(PB, x.H, x.W, pinned=False), rec
+
+    def run(block: nn.Sequential, h: Act, h1: Act | None = None) -> tuple[Act, list]:
+        recs = []
+        for layer in block:
+            if isinstance(layer, (nn.Conv1d, nn.Conv2d)) and h is x_in and getattr(plan, "planar", False):
+                nh, rec = bld.conv_stem(h.buf, B, cin, H, W, _packed(bld, layer), layer.out_channels, gn_stats=True), None
+            elif isinstance(layer, (nn.Conv1d, nn.Conv2d, nn.Conv3d)):
+                nh, rec = conv(h, layer, layer.out_channels, gn_stats=stats, winograd=wino), dict(kind="stem", conv=layer)
+            elif isinstance(layer, ResBlock):
+                nh, rec = resblock(layer, h, h1)
+            elif isinstance(layer, Downsample):
+                if layer.use_conv:
+                    nh = conv(h, layer.op, layer.out_channels, stride=down2)
+                else:  # AvgPoolNd(2, 2): the pooling form of the elementwise pass with S = 1, T = 0
+                    nh = bld.avgpool(h, pool2, D)
+                rec = dict(kind="down", layer=layer, hw=(h.H, h.W))
+            elif isinstance(layer, Upsample):
+                if layer.use_conv:  # nearest x2 is a read-side shift of the conv gather
+                    nh = conv(h, layer.conv, layer.out_channels, up0=up2, winograd=wino)
+                else:  # nearest x2 alone: the same gather under an identity 1x1 filter (exact: one product per output)
+                    eye = torch.eye(h.C, dtype=torch.float32, device=device)
+                    nh = bld.conv(h, bld.pack_conv(eye, None), h.C, up0=up2)
+                rec = dict(kind="up", layer=layer, hw=(h.H, h.W))
+            else:
+                nh, rec = attention(layer, h)
+            recs.append(rec)
+            if not keep and h1 is None and h not in hs and h is not x_in:
+                bld.free(h)
+            h, h1 = nh, None
+        return h, recs
+
+    hs: list[Act] = []
+    in_recs, out_recs = [], []
+    h = x_in
+    for block in net.input_blocks:
+        h, recs = run(block, h)
+        hs.append(h)
+        in_recs.append(recs)
+    skips = list(hs)
+    h, mid_recs = run(net.middle_block, h)
+    for block in net.output_blocks:
+        skip = skips.pop()
+        nh, recs = run(block, h, skip)
+        out_recs.append(recs)
+        if not keep:
+            if h not in hs:
+                bld.free(h)
+            bld.free(skip)
+        h = nh
+    co = net.out[2]
+    n_, r_head = group_norm(h, net.out[0], act=1)
+    if three_d:  # (the NCHW epilogue writes per-plane images: a volume's (C, D, H, W) order takes a pass of its own)
+        head = conv(n_, co, net.out_channels, winograd=wino)
+        bld.tape.add("az_nhwc_to_nchw_f32", plan.out.data_ptr(), head.ptr, B, net.out_channels, D * H * W, head.cs)
+    else:
+        bld.conv(n_, _packed(bld, co), net.out_channels, dst_nchw=plan.out, winograd=wino)
+    bld.free(n_)
+    if film_jobs:
+        from ..._lib import AzLinearGroup, lib
+
+        nj = len(film_jobs)
+        groups = (AzLinearGroup * nj)()
+        for i, (film, w, b_, n_out) in enumerate(film_jobs):
+            g = groups[i]
+            g.y, g.x, g.W, g.bias = film.data_ptr(), emb.data_ptr(), w.data_ptr(), b_.data_ptr()
+            g.ldy, g.ldx, g.N, g.K = n_out, E, n_out, E
+        gdev = torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(device)
+        bld.tape.keep.append(gdev)
+        bld.tape.ops.insert(film_at, (
+            lib().az_linear_small_grouped_f32, (gdev.data_ptr(), nj, max(j[3] for j in film_jobs), emb_rows, 1, 0),
+            "az_linear_small_grouped_f32",
+        ))
+    return in_recs, mid_recs, out_recs, r_head, len(hs)
+
+
 class ADMPlan:
     r"""Compiled forward for (batch, H, W, embedding rows).  ``emb_rows`` = 1 when all samples
     share the timestep and there are no labels, else the batch size."""
@@ -132,76 +417,10 @@ class ADMPlan:
         half_act = (net.dims != 3 and all(c % 128 == 0 for c in chans) and net.model_channels % 8 == 0
                     and (x_in is None or x_in.cs == pad8(net.in_channels)))  # (a shared input: the first program's, same stride)
         bld = self.bld = Builder(device, half=next(net.parameters()).dtype, half_act=half_act)
-        mc, E = net.model_channels, 4 * net.model_channels
-        self.versions = net._param_versions()
+        self.versions = param_versions(net)
         self.emb_rows = emb_rows
-        cin = net.in_channels
-        one_d = net.dims == 1  # (B, C, L) signals: H = 1, every resampling acts along the width alone
-        assert not one_d or H == 1
-        # dims = 3: a (B, C, D, H, W) volume is B * D channel-padded NHWC planes -- every `Act` below has batch PB = B * D.  The
-        # depth axis is never resampled (_src/unet.py:103-104,128: Upsample / Downsample act on the inner two axes), so a
-        # Conv3d is the sum over its depth taps of 2-D convolutions of depth-shifted planes (AzConvArgs.depth, one launch per
-        # tap accumulating through the residual operand, as nn/unet3d.py), the norms and elementwise passes see a sample as
-        # one (D H) x W image (`vol`), the attention blocks as D H W tokens.
-        three_d = net.dims == 3
-        assert three_d or D == 1
+        cin, three_d = net.in_channels, net.dims == 3
         PB = B * D
-        up2 = (0, 1) if one_d else 1  # log2 of the nearest upsampling per axis
-        down2 = (1, 2) if one_d else 2  # stride per axis
-        pool2 = 2 if one_d else 1  # az_affine_act_f32's pooling mode: 1x2 or 2x2
-        wino = False if one_d else None  # (a one-row map: the direct kernel; F(2x2, 3x3) would compute a second, discarded row)
-
-        def packed(conv, **kw):
-            r"""Filter of a ConvNd layer; a 3-tap Conv1d becomes the middle row of a 3x3 filter."""
-            w = conv.weight
-            if w.ndim == 3 and w.shape[-1] == 3:
-                w2 = torch.zeros(*w.shape[:2], 3, 3, dtype=w.dtype, device=w.device)
-                w2[:, :, 1, :] = w.detach()
-                w = w2
-            return bld.pack_conv(w, conv.bias, **kw)
-
-        def halved(a: Act) -> tuple[int, int]:
-            return (a.H, a.W // 2) if one_d else (a.H // 2, a.W // 2)
-
-        def vol(a: Act | None) -> Act | None:
-            r"""The B samples of a plane stack as (D H) x W images (same memory); the producing convolution's GroupNorm
-            partials, one set per plane, are D sets per sample."""
-            if a is None or not three_d:
-                return a
-            q = a.gn_quads
-            return a.view(B, D * a.H, gn_quads=(q[0], D * q[1], q[2]) if q is not None else None)
-
-        def planes(a: Act) -> Act:
-            r"""Inverse of `vol` for a pass's result (pooled or not): B (D H') x W' images -> B D planes of H' x W'."""
-            if not three_d:
-                return a
-            return a.view(PB, a.H // D, pinned=a.pinned)
-
-        def group_norm(x: Act, *args, x1: Act | None = None, **kw) -> Act:
-            return planes(bld.group_norm(vol(x), *args, x1=vol(x1), **kw))
-
-        def conv(src: Act, layer, cout: int, *, cin0=None, **kw) -> Act | None:
-            r"""conv_nd layer on `src` (| kw["src1"] concatenated).  Conv3d with three depth taps: the centre tap first (it exists for
-            every plane; bias, residual), the others accumulate in place; the moments for a following GroupNorm come from the last."""
-            w = layer.weight
-            if not (three_d and w.ndim == 5 and w.shape[2] > 1):
-                if w.ndim == 5:  # 1 x 1 x 1
-                    return bld.conv(src, bld.pack_conv(w[:, :, 0], layer.bias, cin0=cin0), cout, **kw)
-                return bld.conv(src, packed(layer, cin0=cin0), cout, **kw)
-            assert w.shape[2] == 3
-            gn_stats, dst = kw.pop("gn_stats", False), kw.pop("dst_nchw", None)
-            assert dst is None
-            res, res_up = kw.pop("res", None), kw.pop("res_up", 0)
-            # a depth tap that reads only padding (|j - 1| >= D: a single-plane volume) contributes zero and is not launched; the
-            # moments ride on the LAST tap that is
-            taps = [j for j in (0, 2) if abs(j - 1) < D]
-            out = bld.conv(src, bld.pack_conv(w[:, :, 1], layer.bias, cin0=cin0), cout, res=res, res_up=res_up, depth=(D, 0),
-                           gn_stats=gn_stats and not taps, **kw)
-            for j in taps:
-                bld.conv(src, bld.pack_conv(w[:, :, j], None, cin0=cin0), cout, res=out, out=out, depth=(D, j - 1),
-                         gn_stats=gn_stats and j == taps[-1], **kw)
-            return out
-
         c_first = net.input_blocks[0][0]
         # the first convolution reads the latent PLANAR (x_in = the loop's own (B, C, H, W) layout, channel stride 0): Builder.conv_stem
         self.planar = (engine.STEM_PLANAR and cin <= 4 and not three_d and isinstance(c_first, (nn.Conv1d, nn.Conv2d)) and c_first.weight.shape[-1] == 3
@@ -213,387 +432,33 @@ class ADMPlan:
         else:
             self.x_in = Act(torch.zeros(PB * H * W * bld.pad(cin), dtype=torch.float32, device=device), PB, H, W, cin, bld.pad(cin), True)
         self.out = torch.empty((B, net.out_channels) + ((D,) if three_d else ()) + (H, W), dtype=torch.float32, device=device)
-        self.table = bld.const(timestep_embedding_table(net.table_steps, mc))
-        self.t_idx = torch.zeros(emb_rows, dtype=torch.int64, device=device)
-        self.labels = torch.zeros(B, dtype=torch.int64, device=device) if net.num_classes is not None else None
-        temb = bld.empty(emb_rows, mc)
-        row0 = torch.zeros(B, dtype=torch.int64, device=device)  # index vector that replicates a single row per sample
-        bld.tape.keep.append(row0)  # (int64: Builder.const would cast it to fp32 and halve its size)
-        if coef_ptr is not None:  # fused sampling: row index = the step's time_index, read on the device
-            assert emb_rows == 1 or net.num_classes is not None
-            bld.tape.add("az_gather_step_row_f32", temb.data_ptr(), self.table.data_ptr(), coef_ptr, 0, mc, net.table_steps)
-            trow = 1
-        elif frac:  # fractional timesteps (_src/nn.py:90-108 "these may be fractional"): the sinusoid on the device, no table
-            assert mc % 2 == 0, "odd model_channels with fractional timesteps"
-            self.t_frac = torch.zeros(emb_rows, dtype=torch.float32, device=device)
-            bld.tape.add("az_timestep_embedding_f32", temb.data_ptr(), mc, self.t_frac.data_ptr(), 1, emb_rows, mc // 2, 10000.0)
-            trow = emb_rows
-        else:
-            bld.tape.add("az_gather_rows_f32", temb.data_ptr(), self.table.data_ptr(), self.t_idx.data_ptr(), emb_rows, mc, net.table_steps)
-            trow = emb_rows
-        te0, te2 = net.time_embed[0], net.time_embed[2]
-        hid = bld.empty(trow, E)
-        emb = bld.empty(emb_rows, E)
-        bld.linear_small(hid, E, temb, mc, bld.const(te0.weight), bld.const(te0.bias), trow, E, mc, 0, 1)
-        if net.num_classes is None:
-            bld.linear_small(emb, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), trow, E, E, 0, 0)
-        else:  # emb = time_embed(t) + label_emb(y), per sample (_src/unet.py:621-623)
-            tbase = bld.empty(trow, E)
-            bld.linear_small(tbase, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), trow, E, E, 0, 0)
-            lab = bld.empty(B, E)
-            lw = bld.const(net.label_emb.weight)
-            bld.tape.add("az_gather_rows_f32", lab.data_ptr(), lw.data_ptr(), self.labels.data_ptr(), B, E, net.num_classes)
-            ones = bld.const(torch.ones(1))
-            if trow == 1:
-                tb = bld.empty(B, E)
-                bld.tape.add("az_gather_rows_f32", tb.data_ptr(), tbase.data_ptr(), row0.data_ptr(), B, E, 1)
-                tbase = tb
-            bld.tape.add("az_axpby_f32", emb.data_ptr(), ones.data_ptr(), tbase.data_ptr(), ones.data_ptr(), lab.data_ptr(), 1, B * E, 0)
-        ebs = E if emb_rows > 1 else 0  # batch stride of emb rows
-        film_at = len(bld.tape.ops)  # every ResBlock's FiLM projection reads only `emb`: one grouped launch here
-        film_jobs: list[tuple] = []
-
-        def resblock(rb: ResBlock, x: Act, x1: Act | None = None) -> Act:
-            r"""x (| x1 concatenated) -> block output.  Does not free its inputs."""
-            oc, ocs = rb.out_channels, bld.pad(rb.out_channels)
-            gi, ci = rb.in_layers[0], rb.in_layers[2]
-            go, co = rb.out_layers[0], rb.out_layers[3]
-            # FiLM table: emb_layers = SiLU -> Linear(E, 2*oc); (scale | shift) padded to ocs each
-            lin = rb.emb_layers[1]
-            nf = 2 if rb.use_scale_shift_norm else 1  # (scale | shift), or the additive embedding alone
-            w = torch.zeros(nf * ocs, E, dtype=torch.float32, device=device)
-            b_ = torch.zeros(nf * ocs, dtype=torch.float32, device=device)
-            for n in range(nf):
-                w[n * ocs : n * ocs + oc] = lin.weight.detach()[n * oc : (n + 1) * oc]
-                b_[n * ocs : n * ocs + oc] = lin.bias.detach()[n * oc : (n + 1) * oc]
-            film = bld.empty(emb_rows, nf * ocs)
-            film_jobs.append((film, bld.const(w), bld.const(b_), nf * ocs))
-            fbs = nf * ocs if emb_rows > 1 else 0
-            # h = conv(updown(SiLU(GN(x))))
-            n1 = group_norm(x, 32, weight=bld.const(gi.weight), bias=bld.const(gi.bias), act=1, pool=pool2 if rb.down else 0, x1=x1)
-            h = conv(n1, ci, oc, up0=up2 if rb.up else 0, winograd=wino,
-                     gn_stats=rb.use_scale_shift_norm)  # -> out_layers' GroupNorm
-            bld.free(n1)
-            if rb.use_scale_shift_norm:  # h = SiLU(GN(h) * (1 + scale) + shift)
-                n2 = group_norm(h, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), scale=film, shift=film,
-                                scale_off=0, shift_off=ocs, bstride=fbs, act=1)
-            else:  # h = SiLU(GN(h + emb_out)), _src/unet.py:244-246: the statistics are those of the SUM -> one more pass
-                eb = film
-                if emb_rows == 1 and B > 1:  # the pass wants one row per sample
-                    eb = bld.empty(B, ocs)
-                    bld.tape.add("az_gather_rows_f32", eb.data_ptr(), film.data_ptr(),
-                                 row0.data_ptr(), B, ocs, 1)
-                he = bld.new_act(PB, h.H, h.W, oc)
-                bld._affine_act(he, h, None, 0, bld.const(torch.ones(B * ocs)).data_ptr(), eb.data_ptr(), B, D * h.H, h.W, ocs, 0, 0,
-                                bounded=False)
-                n2 = group_norm(he, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
-                bld.free(he)
-            bld.free(h)
-            # skip path
-            if rb.down:
-                assert x1 is None
-                ones, zeros = bld.const(torch.ones(B * x.cs)), bld.const(torch.zeros(B * x.cs))
-                xs = bld.new_act(PB, *halved(x), x.C)
-                bld._affine_act(xs, x, None, 0, ones.data_ptr(), zeros.data_ptr(), B, D * x.H, x.W, x.cs, 0, pool2, bounded=False)
-                out = conv(n2, co, oc, res=xs, gn_stats=True, winograd=wino)
-                bld.free(xs)
-            elif rb.up:
-                assert x1 is None
-                out = conv(n2, co, oc, res=x, res_up=1, gn_stats=True, winograd=wino)  # (one row: oh >> 1 = 0)
-            elif isinstance(rb.skip_connection, nn.Identity):
-                assert x1 is None
-                out = conv(n2, co, oc, res=x, gn_stats=True, winograd=wino)
-            else:
-                sc = rb.skip_connection
-                skip = conv(x, sc, oc, cin0=x.C if x1 is not None else None, src1=x1)
-                out = conv(n2, co, oc, res=skip, gn_stats=True, winograd=wino)
-                bld.free(skip)
-            bld.free(n2)
-            return out
-
-        def attention(ab: AttentionBlock, x: Act) -> Act:
-            Cc = ab.channels
-            n_ = group_norm(x, 32, weight=bld.const(ab.norm.weight), bias=bld.const(ab.norm.bias))
-            tok = n_.view(B, D * n_.H * n_.W, 1, Cc)  # (the normalised tokens: the same memory)
-            ch = Cc // ab.num_heads
-            chp = engine.attn_padded_dim(ch, bld.half)
-            order = "3HC" if ab.new_order else "H3C"
-            xt = x.view(B, D * x.H * x.W, 1, Cc)
-            if chp != ch:  # a head size the kernels are not instantiated for: zero-padded heads (engine.ATTN_HEAD_DIMS; G24)
-                wq, bq = engine.pad_qkv_heads(ab.qkv.weight, ab.qkv.bias, ab.num_heads, ch, chp, order)
-                qkv = bld.conv(tok, bld.pack_conv(wq, bq), 3 * ab.num_heads * chp)
-                att = bld.attention(qkv, ab.num_heads, order, False, 1.0 / math.sqrt(ch), norm_dim=ch)
-                bld.free(qkv)
-                o = bld.conv(att, bld.pack_conv(engine.pad_proj_heads(ab.proj_out.weight, ab.num_heads, ch, chp), ab.proj_out.bias), Cc, res=xt)
-            else:
-                qkv = bld.conv(tok, bld.pack_conv(ab.qkv.weight, ab.qkv.bias), 3 * Cc)
-                att = bld.attention(qkv, ab.num_heads, order, False, 1.0 / math.sqrt(ch))
-                bld.free(qkv)
-                o = bld.conv(att, bld.pack_conv(ab.proj_out.weight, ab.proj_out.bias), Cc, res=xt)
-            bld.free(att)
-            bld.free(n_)
-            return o.view(PB, x.H, x.W, pinned=False)
-
-        def run(block: nn.Sequential, h: Act, h1: Act | None = None) -> Act:
-            for layer in block:
-                if isinstance(layer, (nn.Conv1d, nn.Conv2d)) and h is self.x_in and self.planar:
-                    nh = bld.conv_stem(h.buf, B, cin, H, W, packed(layer), layer.out_channels, gn_stats=True)
-                elif isinstance(layer, (nn.Conv1d, nn.Conv2d, nn.Conv3d)):
-                    nh = conv(h, layer, layer.out_channels, gn_stats=True, winograd=wino)
-                elif isinstance(layer, ResBlock):
-                    nh = resblock(layer, h, h1)
-                elif isinstance(layer, Downsample):
-                    if layer.use_conv:
-                        nh = conv(h, layer.op, layer.out_channels, stride=down2)
-                    else:  # AvgPoolNd(2, 2): the pooling form of the elementwise pass with S = 1, T = 0
-                        nh = bld.new_act(PB, *halved(h), h.C)
-                        bld._affine_act(nh, h, None, 0, bld.const(torch.ones(B * h.cs)).data_ptr(),
-                                        bld.const(torch.zeros(B * h.cs)).data_ptr(), B, D * h.H, h.W, h.cs, 0, pool2, bounded=False)
-                elif isinstance(layer, Upsample):
-                    if layer.use_conv:  # nearest x2 is a read-side shift of the conv gather
-                        nh = conv(h, layer.conv, layer.out_channels, up0=up2, winograd=wino)
-                    else:  # nearest x2 alone: the same gather under an identity 1x1 filter (exact: one product per output)
-                        eye = torch.eye(h.C, dtype=torch.float32, device=device)
-                        nh = bld.conv(h, bld.pack_conv(eye, None), h.C, up0=up2)
-                else:
-                    nh = attention(layer, h)
-                if h1 is None and h not in hs and h is not self.x_in:
-                    bld.free(h)
-                h, h1 = nh, None
-            return h
-
-        hs: list[Act] = []
-        h = self.x_in
-        for block in net.input_blocks:
-            h = run(block, h)
-            hs.append(h)
-        hs_keep = list(hs)
-        h = run(net.middle_block, h)
-        for block in net.output_blocks:
-            skip = hs.pop()
-            nh = run(block, h, skip)
-            if h not in hs_keep:
-                bld.free(h)
-            bld.free(skip)
-            h = nh
-        go, co = net.out[0], net.out[2]
-        n_ = group_norm(h, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
-        if three_d:  # (the NCHW epilogue writes per-plane images: a volume's (C, D, H, W) order takes a pass of its own)
-            head = conv(n_, co, net.out_channels, winograd=wino)
-            bld.tape.add("az_nhwc_to_nchw_f32", self.out.data_ptr(), head.ptr, B, net.out_channels, D * H * W, head.cs)
-        else:
-            bld.conv(n_, packed(co), net.out_channels, dst_nchw=self.out, winograd=wino)
+        _emit_forward(self, net, self.x_in, B, H, W, emb_rows, coef_ptr=coef_ptr, frac=frac, D=D)
         bld.finish()
-        if film_jobs:
-            from ..._lib import AzLinearGroup, lib
-
-            nj = len(film_jobs)
-            groups = (AzLinearGroup * nj)()
-            for i, (film, w, b_, n_out) in enumerate(film_jobs):
-                g = groups[i]
-                g.y, g.x, g.W, g.bias = film.data_ptr(), emb.data_ptr(), w.data_ptr(), b_.data_ptr()
-                g.ldy, g.ldx, g.N, g.K = n_out, E, n_out, E
-            gdev = torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(device)
-            bld.tape.keep.append(gdev)
-            bld.tape.ops.insert(film_at, (
-                lib().az_linear_small_grouped_f32, (gdev.data_ptr(), nj, max(j[3] for j in film_jobs), emb_rows, 1, 0),
-                "az_linear_small_grouped_f32",
-            ))
         self.tape = bld.tape
 
 
 class ADMGradPlan(_GradTapes):
     r"""Gradient plan of a :class:`UNetModel` for one (batch, H, W, embedding rows) signature: the forward-keep and backward tapes
-    of :class:`azula_amd.nn.unet._GradTapes`, mirroring :class:`ADMPlan`'s walk.  A different plan from :class:`ADMPlan`, whose
-    launches it leaves untouched.  The forward-keep tape keeps, per norm pass, its input and its statistics (``Builder.
-    group_norm_keep``) -- no pre-activation, no SiLU pass of its own: the pullback recomputes ``silu'`` from the input --, per
-    attention block q | k | v and the attention output; the embedding (time, label, FiLM tables) is a constant of the pullback.
-    ``dims`` 1 and 2, fp32."""
+    of :class:`azula_amd.gradplan._GradTapes`.  The forward-keep tape is :class:`ADMPlan`'s walk in its keep form
+    (:func:`_emit_forward`), which leaves that plan's launches untouched; the embedding (time, label, FiLM tables) is a constant of
+    the pullback.  ``dims`` 1 and 2, fp32."""
 
     def __init__(self, net: "UNetModel", B: int, H: int, W: int, emb_rows: int, device, frac: bool = False) -> None:
-        super().__init__(device, B, net.in_channels, net.out_channels, H, W, 0, 0, net._param_versions())
+        super().__init__(device, B, net.in_channels, net.out_channels, H, W, 0, 0, param_versions(net))
         bld = self.bld
-        mc, E = net.model_channels, 4 * net.model_channels
-        cin = net.in_channels
         one_d = net.dims == 1
         assert net.dims in (1, 2) and (not one_d or H == 1)
-        up2 = (0, 1) if one_d else 1
-        down2 = (1, 2) if one_d else 2
         pool2 = 2 if one_d else 1
         sh, sw = (1, 2) if one_d else (2, 2)
         wino = False if one_d else None
         cache: dict = {}
         self._views: list = []  # LinearView objects (Builder.conv_dgrad keys its packed weights by their identity)
 
-        def packed(conv, **kw):
-            w = conv.weight
-            if w.ndim == 3 and w.shape[-1] == 3:
-                w2 = torch.zeros(*w.shape[:2], 3, 3, dtype=w.dtype, device=w.device)
-                w2[:, :, 1, :] = w.detach()
-                w = w2
-            return bld.pack_conv(w, conv.bias, **kw)
-
         def dgrad(g: Act, conv, **kw):
             return bld.conv_dgrad(g, conv, cache=cache, winograd=wino, **kw)
 
-        # ---- embedding (a constant of the pullback): ADMPlan's launches
-        self.table = bld.const(timestep_embedding_table(net.table_steps, mc))
-        self.t_idx = torch.zeros(emb_rows, dtype=torch.int64, device=device)
-        self.t_frac = torch.zeros(emb_rows, dtype=torch.float32, device=device) if frac else None
-        self.labels = torch.zeros(B, dtype=torch.int64, device=device) if net.num_classes is not None else None
-        temb = bld.empty(emb_rows, mc)
-        row0 = torch.zeros(B, dtype=torch.int64, device=device)
-        bld.tape.keep.append(row0)
-        if frac:
-            assert mc % 2 == 0, "odd model_channels with fractional timesteps"
-            bld.tape.add("az_timestep_embedding_f32", temb.data_ptr(), mc, self.t_frac.data_ptr(), 1, emb_rows, mc // 2, 10000.0)
-        else:
-            bld.tape.add("az_gather_rows_f32", temb.data_ptr(), self.table.data_ptr(), self.t_idx.data_ptr(), emb_rows, mc, net.table_steps)
-        te0, te2 = net.time_embed[0], net.time_embed[2]
-        hid = bld.empty(emb_rows, E)
-        emb = bld.empty(emb_rows, E)
-        bld.linear_small(hid, E, temb, mc, bld.const(te0.weight), bld.const(te0.bias), emb_rows, E, mc, 0, 1)
-        if net.num_classes is None:
-            bld.linear_small(emb, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), emb_rows, E, E, 0, 0)
-        else:
-            tbase = bld.empty(emb_rows, E)
-            bld.linear_small(tbase, E, hid, E, bld.const(te2.weight), bld.const(te2.bias), emb_rows, E, E, 0, 0)
-            lab = bld.empty(B, E)
-            lw = bld.const(net.label_emb.weight)
-            bld.tape.add("az_gather_rows_f32", lab.data_ptr(), lw.data_ptr(), self.labels.data_ptr(), B, E, net.num_classes)
-            ones = bld.const(torch.ones(1))
-            assert emb_rows == B
-            bld.tape.add("az_axpby_f32", emb.data_ptr(), ones.data_ptr(), tbase.data_ptr(), ones.data_ptr(), lab.data_ptr(), 1, B * E, 0)
-        film_at = len(bld.tape.ops)
-        film_jobs: list[tuple] = []
-
-        # ---- forward-keep layers: (output, record); nothing a pullback reads is handed back to the pool
-        def resblock(rb: ResBlock, x: Act, x1: Act | None):
-            oc, ocs = rb.out_channels, bld.pad(rb.out_channels)
-            gi, ci = rb.in_layers[0], rb.in_layers[2]
-            go, co = rb.out_layers[0], rb.out_layers[3]
-            lin = rb.emb_layers[1]
-            nf = 2 if rb.use_scale_shift_norm else 1
-            w = torch.zeros(nf * ocs, E, dtype=torch.float32, device=device)
-            b_ = torch.zeros(nf * ocs, dtype=torch.float32, device=device)
-            for n in range(nf):
-                w[n * ocs : n * ocs + oc] = lin.weight.detach()[n * oc : (n + 1) * oc]
-                b_[n * ocs : n * ocs + oc] = lin.bias.detach()[n * oc : (n + 1) * oc]
-            film = bld.empty(emb_rows, nf * ocs)
-            film_jobs.append((film, bld.const(w), bld.const(b_), nf * ocs))
-            fbs = nf * ocs if emb_rows > 1 else 0
-            n1, r1 = bld.group_norm_keep(x, 32, weight=bld.const(gi.weight), bias=bld.const(gi.bias), act=1,
-                                         pool=pool2 if rb.down else 0, x1=x1)
-            h = bld.conv(n1, packed(ci), oc, up0=up2 if rb.up else 0, winograd=wino)
-            bld.free(n1)
-            if rb.use_scale_shift_norm:
-                n2, r2 = bld.group_norm_keep(h, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), scale=film, shift=film,
-                                             scale_off=0, shift_off=ocs, bstride=fbs, act=1)
-            else:  # SiLU(GN(h + emb_out)): the kept tensor is the sum
-                eb = film
-                if emb_rows == 1 and B > 1:
-                    eb = bld.empty(B, ocs)
-                    bld.tape.add("az_gather_rows_f32", eb.data_ptr(), film.data_ptr(), row0.data_ptr(), B, ocs, 1)
-                he = bld.new_act(B, h.H, h.W, oc)
-                bld._affine_act(he, h, None, 0, bld.const(torch.ones(B * ocs)).data_ptr(), eb.data_ptr(), B, h.H, h.W, ocs, 0, 0,
-                                bounded=False)
-                bld.free(h)
-                n2, r2 = bld.group_norm_keep(he, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
-            if rb.down:
-                xs = bld.avgpool(x, pool2)
-                out = bld.conv(n2, packed(co), oc, res=xs, winograd=wino)
-                bld.free(xs)
-            elif rb.up:
-                out = bld.conv(n2, packed(co), oc, res=x, res_up=1, winograd=wino)
-            elif isinstance(rb.skip_connection, nn.Identity):
-                out = bld.conv(n2, packed(co), oc, res=x, winograd=wino)
-            else:
-                skip = bld.conv(x, packed(rb.skip_connection, cin0=x.C if x1 is not None else None), oc, src1=x1)
-                out = bld.conv(n2, packed(co), oc, res=skip, winograd=wino)
-                bld.free(skip)
-            bld.free(n2)
-            return out, dict(kind="res", rb=rb, r1=r1, r2=r2, x=x, x1=x1)
-
-        def attention(ab: AttentionBlock, x: Act):
-            Cc = ab.channels
-            n_, rn = bld.group_norm_keep(x, 32, weight=bld.const(ab.norm.weight), bias=bld.const(ab.norm.bias))
-            L = x.H * x.W
-            tok = n_.view(B, L, 1, Cc)
-            ch = Cc // ab.num_heads
-            chp = engine.attn_grad_padded_dim(ch)
-            order = "3HC" if ab.new_order else "H3C"
-            wq, bq, wp = ab.qkv.weight, ab.qkv.bias, ab.proj_out.weight
-            if chp != ch:  # zero-padded heads: the cotangents of the pad lanes meet zero weight columns in the data gradient
-                wq, bq = engine.pad_qkv_heads(wq, bq, ab.num_heads, ch, chp, order)
-                wp = engine.pad_proj_heads(wp, ab.num_heads, ch, chp)
-            vq, vp_ = engine.LinearView(wq), engine.LinearView(wp)
-            self._views += [vq, vp_]
-            qkv = bld.conv(tok, bld.pack_conv(wq, bq), 3 * ab.num_heads * chp)
-            bld.free(n_)
-            att, ra = bld.attention_keep(qkv, ab.num_heads, False, 1.0 / math.sqrt(ch), norm_dim=ch, order=order, skip_prep=True)
-            o = bld.conv(att, bld.pack_conv(wp, ab.proj_out.bias), Cc, res=x.view(B, L, 1, Cc))
-            return o.view(B, x.H, x.W, pinned=False), dict(kind="attn", rn=rn, ra=ra, vq=vq, vp=vp_, x=x)
-
-        def run(block, h: Act, h1: Act | None):
-            recs = []
-            for layer in block:
-                if isinstance(layer, (nn.Conv1d, nn.Conv2d)):
-                    nh, rec = bld.conv(h, packed(layer), layer.out_channels, winograd=wino), dict(kind="stem", conv=layer)
-                elif isinstance(layer, ResBlock):
-                    nh, rec = resblock(layer, h, h1)
-                elif isinstance(layer, Downsample):
-                    if layer.use_conv:
-                        nh = bld.conv(h, packed(layer.op), layer.out_channels, stride=down2)
-                    else:
-                        nh = bld.avgpool(h, pool2)
-                    rec = dict(kind="down", layer=layer, hw=(h.H, h.W))
-                elif isinstance(layer, Upsample):
-                    if layer.use_conv:
-                        nh = bld.conv(h, packed(layer.conv), layer.out_channels, up0=up2, winograd=wino)
-                    else:
-                        eye = torch.eye(h.C, dtype=torch.float32, device=device)
-                        nh = bld.conv(h, bld.pack_conv(eye, None), h.C, up0=up2)
-                    rec = dict(kind="up", layer=layer, hw=(h.H, h.W))
-                else:
-                    nh, rec = attention(layer, h)
-                recs.append(rec)
-                h, h1 = nh, None
-            return h, recs
-
-        cur = bld.new_act(B, H, W, cin, pinned=True)
-        bld.tape.add("az_nchw_to_nhwc_f32", cur.ptr, self.x_in.data_ptr(), None, B, cin, H * W, cur.cs)
-        bld.wrote(cur, bounded=False)
-        hs: list[Act] = []
-        in_recs, out_recs = [], []
-        h = cur
-        for block in net.input_blocks:
-            h, recs = run(block, h, None)
-            hs.append(h)
-            in_recs.append(recs)
-        h, mid_recs = run(net.middle_block, h, None)
-        skips = list(hs)
-        for block in net.output_blocks:
-            h, recs = run(block, h, skips.pop())
-            out_recs.append(recs)
-        go, co = net.out[0], net.out[2]
-        n_, r_head = bld.group_norm_keep(h, 32, weight=bld.const(go.weight), bias=bld.const(go.bias), act=1)
-        bld.conv(n_, packed(co), net.out_channels, dst_nchw=self.out, winograd=wino)
-        bld.free(n_)
-        if film_jobs:
-            from ..._lib import AzLinearGroup, lib
-
-            nj = len(film_jobs)
-            groups = (AzLinearGroup * nj)()
-            for i, (film, w, b_, n_out) in enumerate(film_jobs):
-                g = groups[i]
-                g.y, g.x, g.W, g.bias = film.data_ptr(), emb.data_ptr(), w.data_ptr(), b_.data_ptr()
-                g.ldy, g.ldx, g.N, g.K = n_out, E, n_out, E
-            gdev = torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(device)
-            bld.tape.keep.append(gdev)
-            bld.tape.ops.insert(film_at, (
-                lib().az_linear_small_grouped_f32, (gdev.data_ptr(), nj, max(j[3] for j in film_jobs), emb_rows, 1, 0),
-                "az_linear_small_grouped_f32",
-            ))
+        in_recs, mid_recs, out_recs, r_head, n_hs = _emit_forward(self, net, None, B, H, W, emb_rows, frac=frac, keep=True)
+        co = net.out[2]
         self.end_forward([])
 
         # ---- backward: the same graph from the output to the input.  `extra`: the cotangent a second consumer of the layer's
@@ -692,9 +557,9 @@ class ADMGradPlan(_GradTapes):
         g = t
         g_skip: dict[int, Act] = {}  # index into hs -> the skip connection's share of that tensor's cotangent
         for j in range(len(out_recs) - 1, -1, -1):  # (the decoder popped hs[n - 1] first: output block j read hs[n - 1 - j])
-            g, g_skip[len(hs) - 1 - j] = block_bwd(g, out_recs[j], None)
-        g, _ = block_bwd(g, mid_recs, g_skip[len(hs) - 1])
-        bld.free(g_skip[len(hs) - 1])
+            g, g_skip[n_hs - 1 - j] = block_bwd(g, out_recs[j], None)
+        g, _ = block_bwd(g, mid_recs, g_skip[n_hs - 1])
+        bld.free(g_skip[n_hs - 1])
         for i in range(len(in_recs) - 1, 0, -1):
             g, _ = block_bwd(g, in_recs[i], g_skip[i - 1])
             bld.free(g_skip[i - 1])
@@ -797,14 +662,11 @@ class UNetModel(nn.Module):
         self.out = nn.Sequential(nn.GroupNorm(32, ch), nn.SiLU(), _zero(conv(ch, out_channels, 3, padding=1)))
         self._plans: dict = {}
 
-    def _param_versions(self) -> tuple:
-        return tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-
     def plan(self, B, H, W, emb_rows, device, x_in: Act | None = None, coef_ptr: int | None = None, tag=None, frac=False,
              D: int = 1) -> ADMPlan:
         key = (B, D, H, W, emb_rows, str(device), x_in.ptr if x_in is not None else None, coef_ptr, tag, frac)
         p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
+        if p is None or p.versions != param_versions(self):
             p = ADMPlan(self, B, H, W, emb_rows, device, x_in=x_in, coef_ptr=coef_ptr, frac=frac, D=D)
             self._plans[key] = p
         return p
@@ -813,7 +675,7 @@ class UNetModel(nn.Module):
     def grad_plan(self, B, H, W, emb_rows, device, frac=False) -> ADMGradPlan:
         key = ("vjp", B, H, W, emb_rows, str(device), frac)
         p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
+        if p is None or p.versions != param_versions(self):
             p = ADMGradPlan(self, B, H, W, emb_rows, device, frac=frac)
             self._plans[key] = p
         return p

@@ -31,8 +31,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder, LinearView
-from ...nn.unet import _GradTapes
+from ...engine import Act, Builder, LinearView, SharedResidual, param_versions
+from ...gradplan import _GradTapes
 
 __all__ = ["JiT", "JiTGradPlan", "JiT_models"]
 
@@ -120,6 +120,168 @@ def rotary_tables(head_dim: int, heads: int, grid: int, ctx: int) -> tuple[Tenso
     return expand(cos), expand(sin)
 
 
+def _emit_forward(plan, net: "JiT", B: int, t_shared: bool, x_nchw: Tensor, out_nchw: Tensor, keep: bool = False) -> dict:
+    r"""The network on ``plan.bld``'s tape, from the planar ``x_nchw`` to the planar ``out_nchw``: the conditioning front and its
+    one modulation GEMM, the patch embedding, the blocks with the class tokens joining and leaving, the final layer.  Sets the
+    plan's ``t`` and ``labels`` inputs.
+
+    ``keep``: the forward-keep tape of :class:`JiTGradPlan` (fp32).  Kept per block: the block input (``norm1``'s pullback), the
+    attention record -- raw qkv, q^ | k^ from ``az_qk_prep_w_f32`` (``Builder.attention_keep`` with the gains; the qkv projection
+    runs without its q / k epilogue, heads padded to the backward kernels' sizes), the attention output --, ``x2`` (``norm2``) and
+    the w12 pre-activation (SwiGLU is a pass of its own behind it).  Returns what the backward tape reads."""
+    bld, device = plan.bld, plan.bld.device
+    tape = bld.tape
+    Hd, heads, p, Z = net.hidden_size, net.num_heads, net.patch_size, net.in_channels
+    S = net.input_size
+    grid = S // p
+    L, Lc = grid * grid, net.in_context_len
+    hd = Hd // heads
+    depth, start = len(net.blocks), net.in_context_start
+    joins = bool(Lc) and start < depth  # (the class tokens enter the sequence at block `start`)
+    plan.t = torch.zeros(1 if t_shared else B, dtype=torch.float32, device=device)
+    plan.labels = torch.zeros(B, dtype=torch.int64, device=device)
+
+    # ---- conditioning: c = t_embedder(t) + y_embedder(y)     (_src/model.py:353-355); constants of a pullback
+    F_ = net.t_embedder.frequency_embedding_size
+    m0, m2 = net.t_embedder.mlp[0], net.t_embedder.mlp[2]
+    table = net.y_embedder.embedding_table.weight
+    freq, hid, t_emb, y_emb, c = (bld.empty(B, n) for n in (F_, Hd, Hd, Hd, Hd))
+    ones = bld.const(torch.ones(1))
+    tape.add("az_timestep_embedding_f32", freq.data_ptr(), F_, plan.t.data_ptr(), 0 if t_shared else 1, B, F_ // 2, 10000.0)
+    bld.linear_small(hid, Hd, freq, F_, bld.const(m0.weight), bld.const(m0.bias), B, Hd, F_, 0, 1)
+    bld.linear_small(t_emb, Hd, hid, Hd, bld.const(m2.weight), bld.const(m2.bias), B, Hd, Hd, 0, 0)
+    tape.add("az_gather_rows_f32", y_emb.data_ptr(), bld.const(table).data_ptr(), plan.labels.data_ptr(), B, Hd, table.shape[0])
+    tape.add("az_axpby_f32", c.data_ptr(), ones.data_ptr(), t_emb.data_ptr(), ones.data_ptr(), y_emb.data_ptr(), 1, B * Hd, 0)
+    # every adaLN projection reads only SiLU(c): the 6-way projections of all blocks and the final layer's
+    # 2-way one are ONE GEMM (B x Hd) @ (Hd x (6 depth + 2) Hd) on the MFMA kernel, issued once per forward
+    heads_ = [blk.adaLN_modulation[1] for blk in net.blocks] + [net.final_layer.adaLN_modulation[1]]
+    w_all = torch.cat([m.weight.detach() for m in heads_]).to(device)
+    b_all = torch.cat([m.bias.detach() for m in heads_]).to(device)
+    c_act = Act(bld.empty(B * Hd), 1, B, 1, Hd, Hd, True)
+    tape.add("az_silu_f32", c_act.ptr, c.data_ptr(), B * Hd)
+    bld.wrote(c_act, bounded=False)
+    mods = bld.conv(c_act, bld.pack_conv(w_all, b_all), w_all.shape[0], out_f32=True)  # (the modulation table stays fp32)
+    mods.pinned = True
+    mod, MS = mods.buf, mods.cs  # row stride of the modulation table
+
+    # ---- bottleneck patch embedding + fixed positional table  (_src/model.py:16-43,358-359)
+    e = net.x_embedder
+    tokens = bld.new_act(B, L, 1, Z * p * p, pinned=True, f32=True)  # (the plan's input stays fp32)
+    tape.add("az_patchify_f32", tokens.ptr, x_nchw.data_ptr(), None, B, Z, S, S, p, tokens.cs)
+    bld.wrote(tokens, bounded=False)
+    low = bld.conv(tokens, bld.pack_conv(e.proj1.weight.detach().reshape(e.proj1.out_channels, -1), None), e.proj1.out_channels)
+    pos_t = bld.const(net.pos_embed.detach().reshape(-1))
+    if bld.half_act:  # (the residual operand has the destination's element type)
+        pos_t = pos_t.to(bld.half)
+        tape.keep.append(pos_t)
+    x = bld.conv(low, bld.pack_conv(e.proj2.weight.detach().reshape(Hd, -1), e.proj2.bias), Hd,
+                 res=SharedResidual(Act(pos_t, 1, L, 1, Hd, Hd, True)))
+    bld.free(low)
+
+    # a head size the kernels are not instantiated for: zero-padded heads (engine.ATTN_HEAD_DIMS)
+    hdp = engine.attn_grad_padded_dim(hd) if keep else engine.attn_padded_dim(hd, bld.half)
+
+    def rope_tables(ctx: int) -> tuple:
+        cos, sin = rotary_tables(hd, heads, grid, ctx)  # (tokens, heads, hd / 2)
+        if hdp != hd:  # padded pairs do not turn
+            cos = torch.cat([cos, cos.new_ones(*cos.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
+            sin = torch.cat([sin, sin.new_zeros(*sin.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
+        return bld.const(cos), bld.const(sin)
+
+    rope_img = rope_tables(0)
+    rope_ctx = rope_tables(Lc) if Lc else rope_img
+    recs = []
+    for i, blk in enumerate(net.blocks):
+        if joins and i == start:  # prepend the class tokens (_src/model.py:364-367); no pullback reads the narrow copy
+            wide = bld.new_act(B, L + Lc, 1, Hd)
+            ctx_pos = bld.const(net.in_context_posemb.detach().reshape(-1))
+            if wide.half:  # 2-byte tokens: typed fill; the copy moves Hd / 2 floats per token
+                tape.add("az_token_fill_h16", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd, 2 if bld.half == torch.float16 else 1)
+                tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd // 2)
+            else:
+                tape.add("az_token_fill_f32", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd)
+                tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd)
+            bld.wrote(wide, bounded=False)
+            bld.free(x)
+            x = wide
+        m0_ = 6 * Hd * i  # this block's columns: shift_a | scale_a | gate_a | shift_m | scale_m | gate_m
+        at = blk.attn
+        norm1, norm2 = bld.const(blk.norm1.weight), bld.const(blk.norm2.weight)
+        n1 = bld.row_norm(x, 1, weight=norm1, scale=mod, shift=mod, scale_off=m0_ + Hd, shift_off=m0_, bstride=MS, eps=1e-6)
+        rope_i = rope_img if i < start else rope_ctx
+        wq, bq, wp = at.qkv.weight.detach(), at.qkv.bias, at.proj.weight.detach()
+        if hdp != hd:  # gain 1 on the pad lanes
+            pad1 = torch.ones(hdp - hd)
+            gains = tuple(bld.const(torch.cat([w_.detach().float().cpu(), pad1])) for w_ in (at.q_norm.weight, at.k_norm.weight))
+            wq, bq = engine.pad_qkv_heads(wq, bq, heads, hd, hdp, "3HC")
+            wp = engine.pad_proj_heads(wp, heads, hd, hdp)
+        else:
+            gains = (bld.const(at.q_norm.weight), bld.const(at.k_norm.weight))
+        scale, norm_dim = 1.0 / math.sqrt(hd), (hd if hdp != hd else 0)
+        if keep:
+            qkv = bld.conv(n1, bld.pack_conv(wq, bq), 3 * heads * hdp)
+            bld.free(n1)
+            att, arec = bld.attention_keep(qkv, heads, True, scale, eps=1e-6, rope=rope_i, norm_dim=norm_dim, order="3HC", qk_weight=gains)
+        else:
+            # q / k RMS norm, gains and RoPE in the projection's epilogue, once per layer (padded heads -- head_dim 80 of JiT-H --: in
+            # the attention kernel)
+            prep = dict(heads=heads, head_dim=hd, rmsnorm=True, eps=1e-6, rope=rope_i, weight=gains) if hdp == hd else None
+            qkv = bld.conv(n1, bld.pack_conv(wq, bq), 3 * heads * hdp, qk_prep=prep)
+            bld.free(n1)
+            att = bld.attention(qkv, heads, "3HC", True, scale, eps=1e-6, rope=rope_i, qk_weight=gains, norm_dim=norm_dim)
+            bld.free(qkv)
+        x2 = bld.conv(att, bld.pack_conv(wp, at.proj.bias), Hd, gate=mod, gate_off=m0_ + 2 * Hd, gate_bstride=MS, res=x)
+        if not keep:
+            bld.free(att)
+            bld.free(x)
+        n2 = bld.row_norm(x2, 1, weight=norm2, scale=mod, shift=mod, scale_off=m0_ + 4 * Hd, shift_off=m0_ + 3 * Hd, bstride=MS, eps=1e-6)
+        # silu(x1) * x2 over halves (_src/model.py:159-162) -> interleave rows: pair (x2_c, x1_c)
+        w12, b12 = blk.mlp.w12.weight.detach(), blk.mlp.w12.bias.detach()
+        half = w12.shape[0] // 2
+        w12i = torch.stack((w12[half:], w12[:half]), dim=1).reshape(2 * half, -1).contiguous()
+        b12i = torch.stack((b12[half:], b12[:half]), dim=1).reshape(-1).contiguous()
+        # SwiGLU in the GEMM's epilogue (AzConvArgs.act = 4): no separate pass over the 4096-wide tensor
+        fused = not keep and half % 4 == 0
+        h = bld.conv(n2, bld.pack_conv(w12i, b12i), 2 * half, act=4 if fused else 0)
+        bld.free(n2)
+        glu = h
+        if not fused:
+            glu = bld.swiglu(h)
+            if not keep:
+                bld.free(h)
+        out = bld.conv(glu, bld.pack_conv(blk.mlp.w3.weight, blk.mlp.w3.bias), Hd, gate=mod, gate_off=m0_ + 5 * Hd, gate_bstride=MS,
+                       res=x2)
+        bld.free(glu)
+        if keep:
+            recs.append(dict(x=x, attn=arec, x2=x2, h=h, m0=m0_, norm1=norm1, norm2=norm2, wqkv=LinearView(wq), wproj=LinearView(wp),
+                             w12=LinearView(w12i), w3=LinearView(blk.mlp.w3.weight)))
+        else:
+            bld.free(x2)
+        x = out
+    if joins:  # x[:, in_context_len:]
+        body = bld.new_act(B, L, 1, Hd)
+        tape.add("az_token_copy_f32", body.ptr, L, 0, x.ptr, L + Lc, Lc, L, B, Hd // 2 if body.half else Hd)
+        bld.wrote(body, bounded=False)
+        bld.free(x)
+        x = body
+
+    # ---- final layer + unpatchify 'nhwpqc->nchpwq'          (_src/model.py:166-184,331-344)
+    fl = net.final_layer
+    mf = 6 * Hd * depth  # final layer's columns: shift | scale
+    norm_f = bld.const(fl.norm_final.weight)
+    n = bld.row_norm(x, 1, weight=norm_f, scale=mod, shift=mod, scale_off=mf + Hd, shift_off=mf, bstride=MS, eps=1e-6)
+    if not keep:  # (kept: norm_final's pullback reads it)
+        bld.free(x)
+    wl = fl.linear.weight.detach().reshape(p * p, Z, Hd).transpose(0, 1).reshape(Z * p * p, Hd).contiguous()
+    bl = fl.linear.bias.detach().reshape(p * p, Z).t().reshape(-1).contiguous()
+    o = bld.conv(n, bld.pack_conv(wl, bl), Z * p * p, out_f32=True)  # (the plan's output: fp32 tokens for the unpatchify pass)
+    bld.free(n)
+    tape.add("az_unpatchify_f32", out_nchw.data_ptr(), o.ptr, B, Z, S, S, p, o.cs)
+    bld.free(o)
+    return dict(recs=recs, x_last=x, norm_f=norm_f, wl=wl, w1=LinearView(e.proj1.weight), w2=LinearView(e.proj2.weight), mods=mods, mf=mf,
+                joins=joins)
+
+
 class JiTPlan:
     r"""Compiled forward for one (batch, shared/per-sample time) signature."""
 
@@ -128,283 +290,37 @@ class JiTPlan:
         # SwiGLU through the GEMM's epilogue
         half_act = net.hidden_size % 8 == 0 and all((blk.mlp.w12.weight.shape[0] // 2) % 8 == 0 for blk in net.blocks) and net.hidden_size <= 4096
         bld = self.bld = Builder(device, half=net.pos_embed.dtype, half_act=half_act)
-        Hd, heads, p, Z = net.hidden_size, net.num_heads, net.patch_size, net.in_channels
-        S = net.input_size
-        grid = S // p
-        L, Lc = grid * grid, net.in_context_len
-        hd = Hd // heads
-        self.versions = net._param_versions()
-        f32 = dict(dtype=torch.float32, device=device)
-        self.x_nchw = torch.empty(B, Z, S, S, **f32)
-        self.t = torch.zeros(1 if t_shared else B, **f32)
-        self.labels = torch.zeros(B, dtype=torch.int64, device=device)
-        self.out = torch.empty(B, Z, S, S, **f32)
-        tape = bld.tape
-
-        # ---- conditioning: c = t_embedder(t) + y_embedder(y)     (_src/model.py:353-355)
-        F_ = net.t_embedder.frequency_embedding_size
-        m0, m2 = net.t_embedder.mlp[0], net.t_embedder.mlp[2]
-        table = net.y_embedder.embedding_table.weight
-        freq, hid, t_emb, y_emb, c = (bld.empty(B, n) for n in (F_, Hd, Hd, Hd, Hd))
-        ones = bld.const(torch.ones(1))
-        tape.add("az_timestep_embedding_f32", freq.data_ptr(), F_, self.t.data_ptr(), 0 if t_shared else 1, B, F_ // 2, 10000.0)
-        bld.linear_small(hid, Hd, freq, F_, bld.const(m0.weight), bld.const(m0.bias), B, Hd, F_, 0, 1)
-        bld.linear_small(t_emb, Hd, hid, Hd, bld.const(m2.weight), bld.const(m2.bias), B, Hd, Hd, 0, 0)
-        tape.add("az_gather_rows_f32", y_emb.data_ptr(), bld.const(table).data_ptr(), self.labels.data_ptr(), B, Hd, table.shape[0])
-        tape.add("az_axpby_f32", c.data_ptr(), ones.data_ptr(), t_emb.data_ptr(), ones.data_ptr(), y_emb.data_ptr(), 1, B * Hd, 0)
-        # every adaLN projection reads only SiLU(c): the 6-way projections of all blocks and the final layer's
-        # 2-way one are ONE GEMM (B x Hd) @ (Hd x (6 depth + 2) Hd) on the MFMA kernel, issued once per forward
-        heads_ = [blk.adaLN_modulation[1] for blk in net.blocks] + [net.final_layer.adaLN_modulation[1]]
-        w_all = torch.cat([m.weight.detach() for m in heads_]).to(device)
-        b_all = torch.cat([m.bias.detach() for m in heads_]).to(device)
-        c_act = Act(bld.empty(B * Hd), 1, B, 1, Hd, Hd, True)
-        tape.add("az_silu_f32", c_act.ptr, c.data_ptr(), B * Hd)
-        bld.wrote(c_act, bounded=False)
-        mods = bld.conv(c_act, bld.pack_conv(w_all, b_all), w_all.shape[0], out_f32=True)  # (the modulation table stays fp32)
-        mods.pinned = True
-        mod, MS = mods.buf, mods.cs  # row stride of the modulation table
-
-        # ---- bottleneck patch embedding + fixed positional table  (_src/model.py:16-43,358-359)
-        e = net.x_embedder
-        tokens = bld.new_act(B, L, 1, Z * p * p, pinned=True, f32=True)  # (the plan's input stays fp32)
-        tape.add("az_patchify_f32", tokens.ptr, self.x_nchw.data_ptr(), None, B, Z, S, S, p, tokens.cs)
-        bld.wrote(tokens, bounded=False)
-        low = bld.conv(tokens, bld.pack_conv(e.proj1.weight.detach().reshape(e.proj1.out_channels, -1), None), e.proj1.out_channels)
-        pos_t = bld.const(net.pos_embed.detach().reshape(-1))
-        if bld.half_act:  # (the residual operand has the destination's element type)
-            pos_t = pos_t.to(bld.half)
-            tape.keep.append(pos_t)
-        pos = Act(pos_t, 1, L, 1, Hd, Hd, True)
-        x = bld.conv(low, bld.pack_conv(e.proj2.weight.detach().reshape(Hd, -1), e.proj2.bias), Hd, res=_Shared(pos))
-        bld.free(low)
-
-        hdp = engine.attn_padded_dim(hd, bld.half)
-
-        def rope_tables(ctx: int) -> tuple:
-            cos, sin = rotary_tables(hd, heads, grid, ctx)  # (tokens, heads, hd / 2)
-            if hdp != hd:  # padded pairs do not turn
-                cos = torch.cat([cos, cos.new_ones(*cos.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
-                sin = torch.cat([sin, sin.new_zeros(*sin.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
-            return bld.const(cos), bld.const(sin)
-
-        rope_img = rope_tables(0)
-        rope_ctx = rope_tables(Lc) if Lc else rope_img
-        for i, blk in enumerate(net.blocks):
-            if Lc and i == net.in_context_start:  # prepend the class tokens (_src/model.py:364-367)
-                wide = bld.new_act(B, L + Lc, 1, Hd)
-                ctx_pos = bld.const(net.in_context_posemb.detach().reshape(-1))
-                if wide.half:  # 2-byte tokens: typed fill; the copy moves Hd / 2 floats per token
-                    tape.add("az_token_fill_h16", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd, 2 if bld.half == torch.float16 else 1)
-                    tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd // 2)
-                else:
-                    tape.add("az_token_fill_f32", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd)
-                    tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd)
-                bld.wrote(wide, bounded=False)
-                bld.free(x)
-                x = wide
-            m0_ = 6 * Hd * i  # this block's columns: shift_a | scale_a | gate_a | shift_m | scale_m | gate_m
-            n1 = bld.row_norm(x, 1, weight=bld.const(blk.norm1.weight), scale=mod, shift=mod, scale_off=m0_ + Hd,
-                              shift_off=m0_, bstride=MS, eps=1e-6)
-            at = blk.attn
-            rope_i = rope_img if i < net.in_context_start else rope_ctx
-            gains = (bld.const(at.q_norm.weight), bld.const(at.k_norm.weight))
-            # q / k RMS norm, gains and RoPE in the projection's epilogue, once per layer (head_dim 80 of JiT-H: in the attention kernel)
-            if hdp != hd:  # a head size the kernels are not instantiated for: zero-padded heads (engine.ATTN_HEAD_DIMS)
-                ones = torch.ones(hdp - hd)
-                gains = tuple(bld.const(torch.cat([w_.detach().float().cpu(), ones])) for w_ in (at.q_norm.weight, at.k_norm.weight))
-                wq, bq = engine.pad_qkv_heads(at.qkv.weight, at.qkv.bias, heads, hd, hdp, "3HC")
-                qkv = bld.conv(n1, bld.pack_conv(wq, bq), 3 * heads * hdp)
-                bld.free(n1)
-                att = bld.attention(qkv, heads, "3HC", True, 1.0 / math.sqrt(hd), eps=1e-6, rope=rope_i, qk_weight=gains, norm_dim=hd)
-                bld.free(qkv)
-                x2 = bld.conv(att, bld.pack_conv(engine.pad_proj_heads(at.proj.weight, heads, hd, hdp), at.proj.bias), Hd,
-                              gate=mod, gate_off=m0_ + 2 * Hd, gate_bstride=MS, res=x)
-            else:
-                qkv = bld.conv(n1, bld.pack_conv(at.qkv.weight, at.qkv.bias), 3 * Hd,
-                               qk_prep=dict(heads=heads, head_dim=hd, rmsnorm=True, eps=1e-6, rope=rope_i, weight=gains))
-                bld.free(n1)
-                att = bld.attention(qkv, heads, "3HC", True, 1.0 / math.sqrt(hd), eps=1e-6, rope=rope_i, qk_weight=gains)
-                bld.free(qkv)
-                x2 = bld.conv(att, bld.pack_conv(at.proj.weight, at.proj.bias), Hd, gate=mod, gate_off=m0_ + 2 * Hd, gate_bstride=MS, res=x)
-            bld.free(att)
-            bld.free(x)
-            n2 = bld.row_norm(x2, 1, weight=bld.const(blk.norm2.weight), scale=mod, shift=mod, scale_off=m0_ + 4 * Hd,
-                              shift_off=m0_ + 3 * Hd, bstride=MS, eps=1e-6)
-            # silu(x1) * x2 over halves (_src/model.py:159-162) -> interleave rows: pair (x2_c, x1_c)
-            w12, b12 = blk.mlp.w12.weight.detach(), blk.mlp.w12.bias.detach()
-            half = w12.shape[0] // 2
-            w12i = torch.stack((w12[half:], w12[:half]), dim=1).reshape(2 * half, -1).contiguous()
-            b12i = torch.stack((b12[half:], b12[:half]), dim=1).reshape(-1).contiguous()
-            if half % 4 == 0:  # SwiGLU in the GEMM's epilogue (AzConvArgs.act = 4): no separate pass over the 4096-wide tensor
-                glu = bld.conv(n2, bld.pack_conv(w12i, b12i), 2 * half, act=4)
-                bld.free(n2)
-            else:
-                f1 = bld.conv(n2, bld.pack_conv(w12i, b12i), 2 * half)
-                bld.free(n2)
-                glu = bld.new_act(f1.B, f1.H, f1.W, half)
-                tape.add("az_swiglu_f32", glu.ptr, f1.ptr, f1.B * f1.H * f1.W, half, f1.cs, glu.cs)
-                bld.wrote(glu, bounded=False)
-                bld.free(f1)
-            x = bld.conv(glu, bld.pack_conv(blk.mlp.w3.weight, blk.mlp.w3.bias), Hd, gate=mod, gate_off=m0_ + 5 * Hd,
-                         gate_bstride=MS, res=x2)
-            bld.free(glu)
-            bld.free(x2)
-        if Lc and net.in_context_start < len(net.blocks):  # x[:, in_context_len:]
-            body = bld.new_act(B, L, 1, Hd)
-            tape.add("az_token_copy_f32", body.ptr, L, 0, x.ptr, L + Lc, Lc, L, B, Hd // 2 if body.half else Hd)
-            bld.wrote(body, bounded=False)
-            bld.free(x)
-            x = body
-
-        # ---- final layer + unpatchify 'nhwpqc->nchpwq'          (_src/model.py:166-184,331-344)
-        fl = net.final_layer
-        mf = 6 * Hd * len(net.blocks)  # final layer's columns: shift | scale
-        n = bld.row_norm(x, 1, weight=bld.const(fl.norm_final.weight), scale=mod, shift=mod, scale_off=mf + Hd, shift_off=mf,
-                         bstride=MS, eps=1e-6)
-        bld.free(x)
-        wl = fl.linear.weight.detach().reshape(p * p, Z, Hd).transpose(0, 1).reshape(Z * p * p, Hd).contiguous()
-        bl = fl.linear.bias.detach().reshape(p * p, Z).t().reshape(-1).contiguous()
-        o = bld.conv(n, bld.pack_conv(wl, bl), Z * p * p, out_f32=True)  # (the plan's output: fp32 tokens for the unpatchify pass)
-        bld.free(n)
-        tape.add("az_unpatchify_f32", self.out.data_ptr(), o.ptr, B, Z, S, S, p, o.cs)
+        Z, S = net.in_channels, net.input_size
+        self.versions = param_versions(net)
+        self.x_nchw = torch.empty(B, Z, S, S, dtype=torch.float32, device=device)
+        self.out = torch.empty(B, Z, S, S, dtype=torch.float32, device=device)
+        _emit_forward(self, net, B, t_shared, self.x_nchw, self.out)
         bld.finish()
-        self.tape = tape
+        self.tape = bld.tape
 
 
 class JiTGradPlan(_GradTapes):
     r"""Gradient plan of a :class:`JiT` for one (batch, shared/per-sample time) signature, alongside ``DiTGradPlan``: the
-    forward-keep tape (the order of :class:`JiTPlan`, nothing the pullback reads released) and the backward tape, on planar
+    forward-keep tape (:class:`JiTPlan`'s walk in its keep form, :func:`_emit_forward`) and the backward tape, on planar
     (B, C, S, S) buffers.  ``t`` and ``y`` are constants of the pullback, so the modulation table is one.
 
-    Kept per block: the block input (``norm1``'s pullback), the attention record -- raw qkv, q^ | k^ from ``az_qk_prep_w_f32``
-    (the qkv projection runs without its q / k epilogue), the attention output --, ``x2`` (``norm2``) and the w12
-    pre-activation (SwiGLU is a pass of its own behind it, the w12 rows interleaved as in the forward plan).  The backward tape
-    reads a block right to left: gate, w3 and w12 data gradients around ``az_swiglu_bwd_f32``, ``az_rownorm_bwd_w_f32`` with
-    ``res = g``; gate, proj data gradient, ``az_attention_bwd_f32`` + ``az_qk_prep_bwd_w_f32``, qkv data gradient,
-    ``az_rownorm_bwd_w_f32`` with the residual path's cotangent as ``res``.  The class tokens do not depend on x: where they
-    join, the cotangent drops their rows; where they leave, it is copied behind zeroed rows.  Unpatchify and patchify are each
+    The backward tape reads a block right to left: gate, w3 and w12 data gradients around ``az_swiglu_bwd_f32``,
+    ``az_rownorm_bwd_w_f32`` with ``res = g``; gate, proj data gradient, ``az_attention_bwd_f32`` + ``az_qk_prep_bwd_w_f32``, qkv data
+    gradient, ``az_rownorm_bwd_w_f32`` with the residual path's cotangent as ``res``.  The class tokens do not depend on x: where
+    they join, the cotangent drops their rows; where they leave, it is copied behind zeroed rows.  Unpatchify and patchify are each
     other's adjoints.  Plain ``Tape.run``, no graph capture; ``saved_bytes`` reports the pool."""
 
     def __init__(self, net: "JiT", B: int, t_shared: bool, device) -> None:
-        Hd, heads, p, Z = net.hidden_size, net.num_heads, net.patch_size, net.in_channels
+        Hd, p, Z = net.hidden_size, net.patch_size, net.in_channels
         S = net.input_size
-        super().__init__(device, B, Z, Z, S, S, 0, 0, net._param_versions())
+        super().__init__(device, B, Z, Z, S, S, 0, 0, param_versions(net))
         self._net = weakref.ref(net)
         bld = self.bld
-        grid = S // p
-        L, Lc = grid * grid, net.in_context_len
-        hd = Hd // heads
-        depth = len(net.blocks)
-        start = net.in_context_start
-        joins = bool(Lc) and start < depth  # (the class tokens enter the sequence at block `start`)
-        f32 = dict(dtype=torch.float32, device=device)
-        self.t = torch.zeros(1 if t_shared else B, **f32)
-        self.labels = torch.zeros(B, dtype=torch.int64, device=device)
-        tape = bld.tape
-
-        # ---- conditioning, as JiTPlan: constants of the pullback
-        F_ = net.t_embedder.frequency_embedding_size
-        m0, m2 = net.t_embedder.mlp[0], net.t_embedder.mlp[2]
-        table = net.y_embedder.embedding_table.weight
-        freq, hid, t_emb, y_emb, c = (bld.empty(B, n) for n in (F_, Hd, Hd, Hd, Hd))
-        ones = bld.const(torch.ones(1))
-        tape.add("az_timestep_embedding_f32", freq.data_ptr(), F_, self.t.data_ptr(), 0 if t_shared else 1, B, F_ // 2, 10000.0)
-        bld.linear_small(hid, Hd, freq, F_, bld.const(m0.weight), bld.const(m0.bias), B, Hd, F_, 0, 1)
-        bld.linear_small(t_emb, Hd, hid, Hd, bld.const(m2.weight), bld.const(m2.bias), B, Hd, Hd, 0, 0)
-        tape.add("az_gather_rows_f32", y_emb.data_ptr(), bld.const(table).data_ptr(), self.labels.data_ptr(), B, Hd, table.shape[0])
-        tape.add("az_axpby_f32", c.data_ptr(), ones.data_ptr(), t_emb.data_ptr(), ones.data_ptr(), y_emb.data_ptr(), 1, B * Hd, 0)
-        heads_ = [blk.adaLN_modulation[1] for blk in net.blocks] + [net.final_layer.adaLN_modulation[1]]
-        w_all = torch.cat([m.weight.detach() for m in heads_]).to(device)
-        b_all = torch.cat([m.bias.detach() for m in heads_]).to(device)
-        c_act = Act(bld.empty(B * Hd), 1, B, 1, Hd, Hd, True)
-        tape.add("az_silu_f32", c_act.ptr, c.data_ptr(), B * Hd)
-        bld.wrote(c_act, bounded=False)
-        mods = bld.conv(c_act, bld.pack_conv(w_all, b_all), w_all.shape[0], out_f32=True)
-        mods.pinned = True
+        L, Lc = (S // p) ** 2, net.in_context_len
+        depth, start = len(net.blocks), net.in_context_start
+        kept = _emit_forward(self, net, B, t_shared, self.x_in, self.out, keep=True)
+        recs, x_last, norm_f, wl, w1, w2, mods, mf, joins = (kept[k] for k in ("recs", "x_last", "norm_f", "wl", "w1", "w2", "mods", "mf", "joins"))
         mod, MS = mods.buf, mods.cs
-
-        # ---- forward-keep
-        e = net.x_embedder
-        tokens = bld.new_act(B, L, 1, Z * p * p, pinned=True)
-        tape.add("az_patchify_f32", tokens.ptr, self.x_in.data_ptr(), None, B, Z, S, S, p, tokens.cs)
-        bld.wrote(tokens, bounded=False)
-        w1 = LinearView(e.proj1.weight)
-        w2 = LinearView(e.proj2.weight)
-        low = bld.conv(tokens, bld.pack_conv(e.proj1.weight.detach().reshape(e.proj1.out_channels, -1), None), e.proj1.out_channels)
-        pos = Act(bld.const(net.pos_embed.detach().reshape(-1)), 1, L, 1, Hd, Hd, True)
-        x = bld.conv(low, bld.pack_conv(e.proj2.weight.detach().reshape(Hd, -1), e.proj2.bias), Hd, res=_Shared(pos))
-        bld.free(low)
-
-        hdp = engine.attn_grad_padded_dim(hd)
-
-        def rope_tables(ctx: int) -> tuple:
-            cos, sin = rotary_tables(hd, heads, grid, ctx)
-            if hdp != hd:  # padded pairs do not turn
-                cos = torch.cat([cos, cos.new_ones(*cos.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
-                sin = torch.cat([sin, sin.new_zeros(*sin.shape[:-1], (hdp - hd) // 2)], dim=-1).contiguous()
-            return bld.const(cos), bld.const(sin)
-
-        rope_img = rope_tables(0)
-        rope_ctx = rope_tables(Lc) if Lc else rope_img
-        recs = []
-        for i, blk in enumerate(net.blocks):
-            if joins and i == start:
-                wide = bld.new_act(B, L + Lc, 1, Hd)
-                ctx_pos = bld.const(net.in_context_posemb.detach().reshape(-1))
-                tape.add("az_token_fill_f32", wide.ptr, L + Lc, 0, Lc, y_emb.data_ptr(), Hd, ctx_pos.data_ptr(), B, Hd)
-                tape.add("az_token_copy_f32", wide.ptr, L + Lc, Lc, x.ptr, L, 0, L, B, Hd)
-                bld.wrote(wide, bounded=False)
-                bld.free(x)  # (no pullback reads the narrow copy)
-                x = wide
-            m0_ = 6 * Hd * i  # shift_a | scale_a | gate_a | shift_m | scale_m | gate_m
-            at = blk.attn
-            norm1, norm2 = bld.const(blk.norm1.weight), bld.const(blk.norm2.weight)
-            n1 = bld.row_norm(x, 1, weight=norm1, scale=mod, shift=mod, scale_off=m0_ + Hd, shift_off=m0_, bstride=MS, eps=1e-6)
-            if hdp != hd:  # zero-padded heads: gain 1 on the pad lanes, the padded projections of the forward plan
-                pad1 = torch.ones(hdp - hd)
-                gains = tuple(bld.const(torch.cat([w_.detach().float().cpu(), pad1])) for w_ in (at.q_norm.weight, at.k_norm.weight))
-                wq, bq = engine.pad_qkv_heads(at.qkv.weight, at.qkv.bias, heads, hd, hdp, "3HC")
-                wp = engine.pad_proj_heads(at.proj.weight, heads, hd, hdp)
-            else:
-                gains = (bld.const(at.q_norm.weight), bld.const(at.k_norm.weight))
-                wq, bq, wp = at.qkv.weight.detach(), at.qkv.bias, at.proj.weight.detach()
-            qkv = bld.conv(n1, bld.pack_conv(wq, bq), 3 * heads * hdp)
-            bld.free(n1)
-            att, arec = bld.attention_keep(qkv, heads, True, 1.0 / math.sqrt(hd), eps=1e-6, rope=rope_img if i < start else rope_ctx,
-                                           norm_dim=hd if hdp != hd else 0, order="3HC", qk_weight=gains)
-            x2 = bld.conv(att, bld.pack_conv(wp, at.proj.bias), Hd, gate=mod, gate_off=m0_ + 2 * Hd, gate_bstride=MS, res=x)
-            n2 = bld.row_norm(x2, 1, weight=norm2, scale=mod, shift=mod, scale_off=m0_ + 4 * Hd, shift_off=m0_ + 3 * Hd, bstride=MS,
-                              eps=1e-6)
-            w12, b12 = blk.mlp.w12.weight.detach(), blk.mlp.w12.bias.detach()
-            half = w12.shape[0] // 2  # pair (x2_c, x1_c): silu(x1) * x2 (_src/model.py:159-162)
-            w12i = torch.stack((w12[half:], w12[:half]), dim=1).reshape(2 * half, -1).contiguous()
-            b12i = torch.stack((b12[half:], b12[:half]), dim=1).reshape(-1).contiguous()
-            h = bld.conv(n2, bld.pack_conv(w12i, b12i), 2 * half)
-            bld.free(n2)
-            glu = bld.swiglu(h)
-            out = bld.conv(glu, bld.pack_conv(blk.mlp.w3.weight, blk.mlp.w3.bias), Hd, gate=mod, gate_off=m0_ + 5 * Hd,
-                           gate_bstride=MS, res=x2)
-            bld.free(glu)
-            recs.append(dict(x=x, attn=arec, x2=x2, h=h, m0=m0_, norm1=norm1, norm2=norm2, wqkv=LinearView(wq), wproj=LinearView(wp),
-                             w12=LinearView(w12i), w3=LinearView(blk.mlp.w3.weight)))
-            x = out
-        if joins:  # x[:, in_context_len:]
-            body = bld.new_act(B, L, 1, Hd)
-            tape.add("az_token_copy_f32", body.ptr, L, 0, x.ptr, L + Lc, Lc, L, B, Hd)
-            bld.wrote(body, bounded=False)
-            bld.free(x)
-            x = body
-        fl = net.final_layer
-        mf = 6 * Hd * depth  # shift | scale
-        norm_f = bld.const(fl.norm_final.weight)
-        n = bld.row_norm(x, 1, weight=norm_f, scale=mod, shift=mod, scale_off=mf + Hd, shift_off=mf, bstride=MS, eps=1e-6)
-        x_last = x  # (kept: norm_final's pullback reads it)
-        wl = fl.linear.weight.detach().reshape(p * p, Z, Hd).transpose(0, 1).reshape(Z * p * p, Hd).contiguous()
-        bl = fl.linear.bias.detach().reshape(p * p, Z).t().reshape(-1).contiguous()
-        o = bld.conv(n, bld.pack_conv(wl, bl), Z * p * p, out_f32=True)
-        bld.free(n)
-        tape.add("az_unpatchify_f32", self.out.data_ptr(), o.ptr, B, Z, S, S, p, o.cs)
-        bld.free(o)
         self.end_forward([])
 
         # ---- backward
@@ -474,19 +390,12 @@ class JiTGradPlan(_GradTapes):
             # the tapes read the norm gains, biases and tables where the module keeps them, the GEMM weights from packed copies:
             # after an in-place parameter change the saved tensors no longer belong to what the backward tape would read
             m = net()
-            if m is None or m._param_versions() != self.versions:
+            if m is None or param_versions(m) != self.versions:
                 raise RuntimeError("this pullback belongs to an earlier vjp call: the module's parameters have changed since, "
                                    "and its saved tensors belong to the old ones")
             return pull(v)
 
         return out, pullback
-
-
-class _Shared:
-    r"""Marks a residual as batch-shared (``Builder.conv`` epilogue ``res_bcast``)."""
-
-    def __init__(self, act: Act) -> None:
-        self.act = act
 
 
 class _TimestepEmbedder(nn.Module):
@@ -564,13 +473,10 @@ class JiT(nn.Module):
                 nn.init.zeros_(lin.bias)
         self._plans: dict = {}
 
-    def _param_versions(self) -> tuple:
-        return tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-
     def plan(self, B: int, t_shared: bool, device) -> JiTPlan:
         key = (B, t_shared, str(device))
         p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
+        if p is None or p.versions != param_versions(self):
             p = self._plans[key] = JiTPlan(self, B, t_shared, device)
         return p
 
@@ -578,7 +484,7 @@ class JiT(nn.Module):
     def grad_plan(self, B: int, t_shared: bool, device) -> JiTGradPlan:
         key = ("vjp", B, t_shared, str(device))
         p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
+        if p is None or p.versions != param_versions(self):
             p = self._plans[key] = JiTGradPlan(self, B, t_shared, device)
         return p
 
