@@ -400,6 +400,11 @@ PROTOTYPES: dict[str, list] = {
     "az_transition_f32": [C.POINTER(AzTransitionArgs), c_stream],
     "az_multistep_f32": [C.POINTER(AzMultistepArgs), c_stream],
     "az_repaint_f32": [C.POINTER(AzRepaintArgs), c_stream],
+    "az_op_mul_f32": [vp, vp, vp, i64, i64, c_stream],
+    "az_op_avgpool_f32": [vp, vp, i64, i64, i64, i32, i32, c_stream],
+    "az_op_avgpool_adj_f32": [vp, vp, i64, i64, i64, i32, i32, f32, c_stream],
+    "az_op_blur_f32": [vp, vp, vp, i32, vp, i32, i64, i64, i64, i32, c_stream],
+    "az_op_blur_tile": [i32, i32, C.POINTER(i32), C.POINTER(i32)],
     "az_tds_chunks": [i64, i64],
     "az_tds_resample_f32": [vp, vp, vp, vp, vp, i64, c_stream],
     "az_tds_propose_f32": [C.POINTER(AzTdsProposeArgs), c_stream],

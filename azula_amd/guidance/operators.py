@@ -1,0 +1,425 @@
+r"""Measurement operators for the guidance methods: pixel mask, average-pool downsampling and separable blur, with exact
+adjoints and (where one exists) the pseudo-inverse.
+
+The guidance classes take the operator :math:`A` of :math:`y = A x + n` as a callable and differentiate it with
+``torch.autograd.grad`` (DPS, TMPD, MMPS, JFPS, DiffPIR) and ``torch.func.jvp`` (MMPS, JFPS).  The operators below are such
+callables whose three maps are kernels of ``csrc/operators.hip``: no autograd graph of torch ops, no atomics (two runs give the
+same bits) and a fixed launch sequence.  The project's own extension: the reference has no operator library.
+
+    A = DownsampleOperator(2, flatten=True) @ BlurOperator.gaussian(1.0, 5)
+    DiffPIRDenoiser(denoiser, y, A, var_y)              # y: (B, D)
+    PGDMSampler(denoiser, y, M, M.pinv)                 # M = MaskOperator(mask)
+
+Two paths, as ``RePaintSampler`` has them:
+
+* contiguous fp32 device tensors: the kernels, through ONE ``torch.autograd.Function`` whose ``backward`` and ``jvp`` are
+  applications of itself (the maps are linear), so ``autograd.grad``, ``torch.func.jvp`` / ``vjp`` and double differentiation all
+  end in the same launches;
+* everything else (host tensors, fp64 and half tensors): a plain torch op sequence in the tensor's own dtype -- padding, slices,
+  reshapes and elementwise ops -- which torch differentiates itself.
+"""
+
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+import math
+from collections.abc import Sequence
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor
+
+from .. import _lib
+from .repaint import _aligned, _broadcasts_to
+
+__all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps"]
+
+MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_blur_f32)
+
+
+def _launch(name: str, *args) -> None:
+    r"""Every kernel launch of this module: entry ``name`` of the C ABI on torch's current stream."""
+    _lib.call(name, *args, _lib.stream_ptr())
+
+
+def _use_kernels(x: Tensor) -> bool:
+    return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+
+
+def _device_of(x: Tensor):
+    r"""The context ``_lib.on_device`` gives a method: launches go to the current device's stream, so ``x``'s is made current."""
+    if x.is_cuda and x.device.index != torch.cuda.current_device():
+        return torch.cuda.device(x.device)
+    return contextlib.nullcontext()
+
+
+class _Apply(torch.autograd.Function):
+    r"""``op``'s map ``mode`` ("apply", "adjoint" or "pinv") on the kernels.
+
+    ``forward`` always receives plain tensors.  ``backward`` and ``jvp`` do NOT: under ``torch.func.jvp`` / ``vjp`` theirs are
+    functorch wrappers without storage, so neither may launch on what it receives.  Both are applications of this Function --
+    the tangent map of a linear map is the map, its pullback the transposed map -- which unwraps level by level down to
+    ``forward``."""
+
+    @staticmethod
+    def forward(x: Tensor, op: LinearOperator, mode: str) -> Tensor:
+        with _device_of(x):
+            return op._kernel(_aligned(x.contiguous(), 16), mode)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output) -> None:
+        _, ctx.op, ctx.mode = inputs
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return ctx.op._transposed(g, ctx.mode), None, None
+
+    @staticmethod
+    def jvp(ctx, tx: Tensor, *_):
+        return _Apply.apply(tx, ctx.op, ctx.mode)
+
+
+class LinearOperator:
+    r"""A linear map on images :math:`(B, C, H, W)` with its adjoint.
+
+    Arguments:
+        flatten: Whether the observation is flattened to :math:`(B, D)`, the convention of ``MMPSDenoiser``, ``JFPSDenoiser``
+            and ``DiffPIRDenoiser``.  ``adjoint`` and ``pinv`` then accept the flat or the image shape.
+        in_shape: The shape :math:`(C, H, W)` of an input, needed to un-flatten an observation.  Taken from the last forward
+            call when not given.
+
+    ``A(x)`` applies the operator, ``A.adjoint(v)`` its transpose, ``A.T`` is the transposed operator, ``A.pinv(y)`` the
+    pseudo-inverse where one is defined, and ``A2 @ A1`` the composition :math:`x \mapsto A_2(A_1(x))`.
+    """
+
+    def __init__(self, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        self.flatten = bool(flatten)
+        self.in_shape = None if in_shape is None else tuple(int(s) for s in in_shape)
+        if self.in_shape is not None and len(self.in_shape) != 3:
+            raise ValueError(f"in_shape is (C, H, W), got {self.in_shape}")
+
+    # -- what a subclass defines ----------------------------------------------------------------------------------------
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        r"""(C', H', W') of the observation of a (C, H, W) input; raises ``ValueError`` for an input the operator cannot take."""
+        return in_shape
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        r"""(C, H, W) of the input whose observation is (C', H', W')."""
+        return out_shape
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        r"""The map ``mode`` of a contiguous, 16-byte aligned fp32 tensor, as launches through :func:`_launch`."""
+        raise NotImplementedError
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        r"""The same map as torch ops in ``x``'s dtype."""
+        raise NotImplementedError
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        r"""The transpose of the map ``mode`` applied to ``g``, as applications of :class:`_Apply`."""
+        if mode == "pinv":
+            raise NotImplementedError(f"{type(self).__name__} has no pseudo-inverse")
+        return _Apply.apply(g, self, "adjoint" if mode == "apply" else "apply")
+
+    # -- the public maps ------------------------------------------------------------------------------------------------
+    def _run(self, x: Tensor, mode: str) -> Tensor:
+        return _Apply.apply(x, self, mode) if _use_kernels(x) else self._torch(x, mode)
+
+    def _image(self, v: Tensor, what: str) -> Tensor:
+        r"""An observation in its image shape: (B, C', H', W') as it is, (B, D) un-flattened with the recorded input shape."""
+        if v.ndim == 4:
+            return v
+        if v.ndim != 2:
+            raise ValueError(f"{what} takes a (B, C, H, W) or a flat (B, D) tensor, got {tuple(v.shape)}")
+        if self.in_shape is None:
+            raise ValueError(f"{what} of a flat {tuple(v.shape)} tensor needs the image shape: call the operator once or pass "
+                             "in_shape=(C, H, W)")
+        out = self._out_shape(self.in_shape)
+        if v.shape[1] != math.prod(out):
+            raise ValueError(f"{what}: {tuple(v.shape)} is not a flattened (B, {', '.join(map(str, out))}) observation")
+        return v.unflatten(1, out)
+
+    def __call__(self, x: Tensor) -> Tensor:
+        if x.ndim != 4:
+            raise ValueError(f"{type(self).__name__} takes a (B, C, H, W) tensor, got {tuple(x.shape)}")
+        self._out_shape(tuple(x.shape[1:]))
+        self.in_shape = tuple(x.shape[1:])
+        y = self._run(x, "apply")
+        return y.flatten(1) if self.flatten else y
+
+    def adjoint(self, v: Tensor) -> Tensor:
+        v = self._image(v, "adjoint")
+        self._out_shape(self._in_shape_of(tuple(v.shape[1:])))
+        return self._run(v, "adjoint")
+
+    def pinv(self, y: Tensor) -> Tensor:
+        raise NotImplementedError(f"{type(self).__name__} has no pseudo-inverse")
+
+    @property
+    def T(self) -> LinearOperator:
+        return _Transposed(self)
+
+    def __matmul__(self, other: LinearOperator) -> LinearOperator:
+        if not isinstance(other, LinearOperator):
+            return NotImplemented
+        return _Composition(self, other)
+
+
+class _Transposed(LinearOperator):
+    r"""``A.T``: the call is ``A.adjoint``, the adjoint is ``A``, and ``.T`` is ``A`` itself."""
+
+    def __init__(self, base: LinearOperator) -> None:
+        super().__init__()
+        self.base = base
+
+    def __call__(self, v: Tensor) -> Tensor:
+        return self.base.adjoint(v)
+
+    def adjoint(self, x: Tensor) -> Tensor:
+        return self.base(x)
+
+    @property
+    def T(self) -> LinearOperator:
+        return self.base
+
+
+class _Composition(LinearOperator):
+    r"""``A2 @ A1``: :math:`x \mapsto A_2(A_1(x))`; the adjoint runs the two adjoints in reverse.  No pseudo-inverse."""
+
+    def __init__(self, outer: LinearOperator, inner: LinearOperator) -> None:
+        super().__init__()
+        self.outer, self.inner = outer, inner
+
+    def __call__(self, x: Tensor) -> Tensor:
+        return self.outer(self.inner(x))
+
+    def adjoint(self, v: Tensor) -> Tensor:
+        return self.inner.adjoint(self.outer.adjoint(v))
+
+
+# ------------------------------------------------------------------------------------------------------------------ mask
+class MaskOperator(LinearOperator):
+    r"""Creates the pixel mask :math:`x \mapsto m \odot x` (inpainting).  Self-adjoint.
+
+    Arguments:
+        mask: The mask :math:`m`, bool or float, broadcastable to the input.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    ``pinv`` multiplies by :math:`1 / m` where :math:`m \neq 0` and by 0 elsewhere.  The factor is made once per device, dtype
+    and (where it has to be expanded) input shape: build a new operator for a new mask rather than editing ``mask`` in place.
+    """
+
+    def __init__(self, mask: Tensor, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        if not torch.is_tensor(mask) or mask.ndim > 4:
+            raise ValueError("mask is a tensor of at most 4 dimensions")
+        self.mask = mask
+        self._cache: dict = {}
+
+    def _factor(self, x: Tensor, inverse: bool) -> Tensor:
+        r"""The factor in ``x``'s dtype, on ``x``'s device.  fp32 device tensors: contiguous and either a suffix of ``x``'s shape
+        (the kernel indexes it modulo its size) or expanded to ``x``'s shape; made once per device and shape."""
+        core = tuple(self.mask.shape)
+        while core and core[0] == 1:
+            core = core[1:]
+        kernels = _use_kernels(x)
+        suffix = core == tuple(x.shape[x.ndim - len(core):])
+        key = (x.device, x.dtype, inverse, kernels, tuple(x.shape) if kernels and not suffix else None)
+        m = self._cache.get(key)
+        if m is None:
+            m = self.mask.to(device=x.device, dtype=x.dtype)
+            if inverse:
+                m = torch.where(m != 0, 1 / torch.where(m != 0, m, torch.ones_like(m)), torch.zeros_like(m))
+            if kernels:
+                m = _aligned((m.reshape(core) if suffix else m.expand(x.shape)).contiguous(), 16)
+            self._cache[key] = m
+        return m
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        if not _broadcasts_to(self.mask.shape[-3:], in_shape):  # (the batch dimension: _check_batch)
+            raise ValueError(f"a mask of shape {tuple(self.mask.shape)} does not broadcast to (B, {', '.join(map(str, in_shape))})")
+        return in_shape
+
+    def _check_batch(self, x: Tensor) -> None:
+        if not _broadcasts_to(self.mask.shape, x.shape):
+            raise ValueError(f"a mask of shape {tuple(self.mask.shape)} does not broadcast to {tuple(x.shape)}")
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        self._check_batch(x)
+        m = self._factor(x, mode == "pinv")
+        y = torch.empty_like(x)
+        if x.numel():
+            _launch("az_op_mul_f32", y.data_ptr(), x.data_ptr(), m.data_ptr(), x.numel(), m.numel())
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        self._check_batch(x)
+        return x * self._factor(x, mode == "pinv")
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        return _Apply.apply(g, self, mode if mode == "pinv" else "apply")  # (diagonal maps: each is its own transpose)
+
+    def adjoint(self, v: Tensor) -> Tensor:
+        v = self._image(v, "adjoint")
+        self._out_shape(tuple(v.shape[1:]))
+        return self._run(v, "apply")
+
+    def pinv(self, y: Tensor) -> Tensor:
+        y = self._image(y, "pinv")
+        self._out_shape(tuple(y.shape[1:]))
+        return self._run(y, "pinv")
+
+
+# ------------------------------------------------------------------------------------------------------------ downsample
+class DownsampleOperator(LinearOperator):
+    r"""Creates the average-pool downsampling by ``factor`` (super-resolution).
+
+    Arguments:
+        factor: The factor, an int or ``(fh, fw)``, each in 1 .. 16.  The input's height and width are multiples of it.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    ``pinv`` is nearest up-sampling, :math:`f_h f_w` times the adjoint.
+    """
+
+    def __init__(self, factor: int | Sequence[int], flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        fh, fw = (factor, factor) if isinstance(factor, int) else factor
+        if not (isinstance(fh, int) and isinstance(fw, int) and 1 <= fh <= MAX_FACTOR and 1 <= fw <= MAX_FACTOR):
+            raise ValueError(f"factor is an int or a pair of ints in 1 .. {MAX_FACTOR}, got {factor}")
+        self.factor = (fh, fw)
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        (c, h, w), (fh, fw) = in_shape, self.factor
+        if h % fh or w % fw:
+            raise ValueError(f"downsampling by {self.factor} needs a height and width that are multiples of it, got {h} x {w}")
+        return (c, h // fh, w // fw)
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        return (out_shape[0], out_shape[1] * self.factor[0], out_shape[2] * self.factor[1])
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        (B, c, h, w), (fh, fw) = x.shape, self.factor
+        if mode == "apply":
+            y = x.new_empty(B, c, h // fh, w // fw)
+            if y.numel():
+                _launch("az_op_avgpool_f32", y.data_ptr(), x.data_ptr(), B * c, h, w, fh, fw)
+            return y
+        y = x.new_empty(B, c, h * fh, w * fw)
+        if y.numel():
+            scale = 1.0 if mode == "pinv" else 1.0 / (fh * fw)
+            _launch("az_op_avgpool_adj_f32", y.data_ptr(), x.data_ptr(), B * c, h * fh, w * fw, fh, fw, scale)
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        (B, c, h, w), (fh, fw) = x.shape, self.factor
+        if mode == "apply":
+            win = x.reshape(B, c, h // fh, fh, w // fw, fw)
+            acc = None
+            for a in range(fh):  # (the kernel's order of summation)
+                for b in range(fw):
+                    acc = win[:, :, :, a, :, b] if acc is None else acc + win[:, :, :, a, :, b]
+            return acc * (1.0 / (fh * fw))
+        up = x[:, :, :, None, :, None].expand(B, c, h, fh, w, fw).reshape(B, c, h * fh, w * fw)
+        return up if mode == "pinv" else up * (1.0 / (fh * fw))
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        if mode == "pinv":  # (fh fw A^T)^T
+            return _Apply.apply(g, self, "apply") * float(self.factor[0] * self.factor[1])
+        return super()._transposed(g, mode)
+
+    def pinv(self, y: Tensor) -> Tensor:
+        y = self._image(y, "pinv")
+        return self._run(y, "pinv")
+
+
+# ------------------------------------------------------------------------------------------------------------------ blur
+def gaussian_taps(sigma: float, size: int) -> Tensor:
+    r"""``size`` samples of a centred Gaussian of standard deviation ``sigma`` (in pixels), computed in fp64, normalised to sum 1
+    and then rounded to fp32."""
+    if size < 1 or sigma <= 0:
+        raise ValueError(f"gaussian_taps needs size >= 1 and sigma > 0, got size {size}, sigma {sigma}")
+    pos = torch.arange(size, dtype=torch.float64) - (size - 1) / 2
+    k = torch.exp(-0.5 * (pos / sigma) ** 2)
+    return (k / k.sum()).to(torch.float32)
+
+
+class BlurOperator(LinearOperator):
+    r"""Creates a separable blur of the input's size: the correlation
+    :math:`y_{ij} = \sum_a h_a \sum_b w_b \, \tilde x_{i + a - r_h, j + b - r_w}` with the radii :math:`r = \lfloor n / 2 \rfloor`.
+
+    Arguments:
+        taps_h: The vertical taps, an odd number of them, at most 65.  Any values: symmetry is not assumed.
+        taps_w: The horizontal taps (``taps_h`` when ``None``).
+        padding: ``"zeros"`` (:math:`\tilde x = 0` outside the image) or ``"circular"`` (wrapped; the radii are smaller than the
+            image).
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    The adjoint is the same correlation with both tap vectors reversed, for both paddings.  There is no ``pinv``.
+    """
+
+    def __init__(self, taps_h, taps_w=None, padding: str = "zeros", flatten: bool = False,
+                 in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        if padding not in ("zeros", "circular"):
+            raise ValueError(f"padding is 'zeros' or 'circular', got {padding!r}")
+        self.padding = padding
+        taps = []
+        for t in (taps_h, taps_h if taps_w is None else taps_w):
+            t = torch.as_tensor(t).detach().to(device="cpu", dtype=torch.float32).contiguous()
+            if t.ndim != 1 or t.numel() % 2 == 0 or t.numel() > MAX_TAPS:
+                raise ValueError(f"taps are 1-d vectors of an odd length of at most {MAX_TAPS}, got shape {tuple(t.shape)}")
+            taps.append(t)
+        self.taps_h, self.taps_w = taps
+        self._cache: dict = {}
+
+    @classmethod
+    def gaussian(cls, sigma: float, size: int, **kwargs) -> BlurOperator:
+        r"""A Gaussian blur: ``gaussian_taps(sigma, size)`` along both axes."""
+        return cls(gaussian_taps(sigma, size), **kwargs)
+
+    def _taps(self, x: Tensor, mode: str) -> tuple[Tensor, Tensor]:
+        key = (x.device, x.dtype, mode)
+        t = self._cache.get(key)
+        if t is None:
+            hw = (self.taps_h, self.taps_w) if mode == "apply" else (self.taps_h.flip(0), self.taps_w.flip(0))
+            t = self._cache[key] = tuple(v.to(device=x.device, dtype=x.dtype).contiguous() for v in hw)
+        return t
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        _, h, w = in_shape
+        rh, rw = self.taps_h.numel() // 2, self.taps_w.numel() // 2
+        if self.padding == "circular" and (rh >= h or rw >= w):
+            raise ValueError(f"circular padding needs radii ({rh}, {rw}) smaller than the image, got {h} x {w}")
+        return in_shape
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        B, c, h, w = x.shape
+        th, tw = self._taps(x, mode)
+        y = torch.empty_like(x)
+        if x.numel():
+            _launch("az_op_blur_f32", y.data_ptr(), x.data_ptr(), th.data_ptr(), th.numel(), tw.data_ptr(), tw.numel(), B * c, h, w,
+                    int(self.padding == "circular"))
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        h, w = x.shape[2:]
+        th, tw = self._taps(x, mode)
+        rh, rw = th.numel() // 2, tw.numel() // 2
+        xp = F.pad(x, (rw, rw, rh, rh), mode="circular") if self.padding == "circular" else F.pad(x, (rw, rw, rh, rh))
+        rows = None
+        for b in range(tw.numel()):  # (the kernel's two passes; torch rounds the product where the kernel fuses it)
+            term = tw[b] * xp[:, :, :, b:b + w]
+            rows = term if rows is None else rows + term
+        out = None
+        for a in range(th.numel()):
+            term = th[a] * rows[:, :, a:a + h, :]
+            out = term if out is None else out + term
+        return out
+
+
+def blur_tile(nh: int, nw: int) -> tuple[int, int]:
+    r"""The output tile (rows, columns) of one workgroup of ``az_op_blur_f32`` for these tap counts."""
+    th, tw = C.c_int32(0), C.c_int32(0)
+    _lib.call("az_op_blur_tile", nh, nw, C.byref(th), C.byref(tw))
+    return th.value, tw.value

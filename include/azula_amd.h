@@ -147,6 +147,37 @@ typedef struct AzRepaintArgs {
 } AzRepaintArgs; /* 72 bytes */
 int az_repaint_f32(const AzRepaintArgs* args, az_stream_t stream);
 
+/* ---- Measurement operators of the guidance methods (csrc/operators.hip, azula_amd/guidance/operators.py) -----------
+ * The linear maps A of inpainting, super-resolution and deblurring with their adjoints, on planar fp32 (B, C, H, W) tensors
+ * seen as planes = B * C contiguous images of H x W.  The project's own: the reference takes A as a Python callable.  No
+ * atomics and a fixed summation order (two launches give the same bits); any plane count (work items are a linear 64-bit
+ * range); tensors 16-byte aligned, tap vectors 4-byte aligned (else AZ_E_ALIGN).
+ *
+ * az_op_mul_f32: y[i] = x[i] * m[i mod m_n] -- a mask whose shape is a suffix of x's; m_n divides n (else AZ_E_SHAPE).  m is
+ * read 16 bytes at a time where m_n % 4 == 0.  y may be x.
+ *
+ * az_op_avgpool_f32: y[n, i, j] = (sum_{a < fh} sum_{b < fw} x[n, i fh + a, j fw + b]) * (1 / (fh fw)), summed in that order in
+ * fp32; y is (planes, H / fh, W / fw).  1 <= fh, fw <= 16, H % fh == 0 and W % fw == 0 (else AZ_E_SHAPE).
+ *
+ * az_op_avgpool_adj_f32: dx[n, Y, X] = scale * g[n, Y / fh, X / fw] on the (H, W) grid, g being (planes, H / fh, W / fw):
+ * scale = 1 / (fh fw) is the adjoint of az_op_avgpool_f32, scale = 1 its pseudo-inverse (nearest up-sampling).
+ *
+ * az_op_blur_f32: the separable correlation y[n, i, j] = sum_a taps_h[a] sum_b taps_w[b] x~[n, i + a - nh / 2, j + b - nw / 2] of
+ * x's size, x~ = 0 outside the image (circular = 0) or wrapped (circular = 1: nh / 2 < H and nw / 2 < W).  nh, nw odd, 1 .. 65
+ * (else AZ_E_SHAPE); taps are DEVICE pointers, arbitrary values.  y must not overlap x (AZ_E_SHAPE).  One launch: a workgroup
+ * stages its tile and halo in LDS, runs the row pass into LDS and the column pass to y; both sums are chains of fused
+ * multiply-adds from 0 with the taps ascending.  The adjoint is the same entry with both tap vectors reversed.
+ *
+ * az_op_blur_tile: the output tile (rows th, columns tw) of a launch with these tap counts (host arithmetic). */
+int az_op_mul_f32(float* y, const float* x, const float* m, int64_t n, int64_t m_n, az_stream_t stream);
+int az_op_avgpool_f32(float* y, const float* x, int64_t planes, int64_t H, int64_t W, int32_t fh, int32_t fw,
+                      az_stream_t stream);
+int az_op_avgpool_adj_f32(float* dx, const float* g, int64_t planes, int64_t H, int64_t W, int32_t fh, int32_t fw, float scale,
+                          az_stream_t stream);
+int az_op_blur_f32(float* y, const float* x, const float* taps_h, int32_t nh, const float* taps_w, int32_t nw, int64_t planes,
+                   int64_t H, int64_t W, int32_t circular, az_stream_t stream);
+int az_op_blur_tile(int32_t nh, int32_t nw, int32_t* th, int32_t* tw);
+
 /* ---- Twisted diffusion sampler: resample and proposal -------------------------------------------------------------
  * The non-network part of TDSSampler.step (azula/guidance/tds.py:70-102) for K particles of N elements each.
  *
