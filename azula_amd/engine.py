@@ -246,6 +246,61 @@ STEM_PLANAR = os.environ.get("AZ_STEM_PLANAR", "1") != "0"
 AFFINE_FUSED = os.environ.get("AZ_AFFINE_FUSED", "1") != "0"
 GN_FUSED_SPLITK = os.environ.get("AZ_GN_FUSED", "1") != "epilogue"  # ("epilogue": only the Winograd epilogue's moments -- A/B)
 
+# Every switch above that a plan bakes in at build time: what :func:`plan_mode` reads
+PLAN_SWITCHES = ("FP32_MFMA", "WINOGRAD", "WINO_X3", "F16X2_DYNAMIC", "F16X2_MOMENTS", "GN_FUSED", "GN_FUSED_SPLITK", "HALF_ACT", "QK_PREP",
+                 "STEM_PLANAR", "AFFINE_FUSED", "ATTN_H2", "ATTN_X3", "WINOGRAD4_MIN_TILES", "X3_MIN_CHANNELS")
+
+
+def plan_mode() -> tuple:
+    r"""The arithmetic mode a plan built now would bake in (read per call: tests and ``bench.py`` assign to these names)."""
+    g = globals()
+    return tuple(g[name] for name in PLAN_SWITCHES)
+
+
+class PlanCache(dict):
+    r"""The compiled plans of one module, ``key -> plan`` in build order (a plain dict to everything that reads it).  A plan is
+    valid for its *stamp*: the module's :func:`param_versions`, :func:`plan_mode` and whatever else its builder bakes in
+    (``extra``).  At most ``max_live`` plans are kept, oldest built dropped first (a hit does not reorder); a plan that a
+    captured loop or a pullback still holds lives on with its holder, and a later lookup builds it again."""
+
+    def __init__(self, max_live: int = 4) -> None:
+        super().__init__()
+        self.max_live = max_live
+        self.stamps: dict = {}
+
+    def get(self, key, make, module: torch.nn.Module, extra=()):
+        r"""The plan under ``key`` while its stamp is the current one, else ``make()`` -- after dropping every plan with
+        another stamp, none of which can become valid again."""
+        stamp = (param_versions(module), plan_mode(), extra)
+        if key in self and self.stamps.get(key) == stamp:
+            return self[key]
+        for k in [k for k in self if self.stamps.get(k) != stamp]:
+            del self[k]
+        self[key] = plan = make()
+        while len(self) > self.max_live:
+            del self[next(iter(self))]
+        self.stamps = dict.fromkeys(self, stamp)
+        return plan
+
+
+def content_key(module: torch.nn.Module, *tensors) -> tuple:
+    r"""Cache-key element for tensors that a plan bakes in by CONTENT (positions -> RoPE / embedding tables, mask bytes): per
+    tensor ``None`` or (shape, dtype, bytes).  Bytes compare by value, so no hash collision can hand out a plan built for other
+    values.  The last two argument sets are remembered on the module by identity -- same objects, storage, shape and version
+    counter, the tensors kept alive so that their storage cannot pass to others -- and recognised without another copy to the
+    host: a steady-state call does not synchronise the device."""
+    seen = module.__dict__.setdefault("_plan_seen", {})
+    ik = tuple(None if t is None else (t.data_ptr(), t._version, tuple(t.shape), str(t.dtype), str(t.device)) for t in tensors)
+    hit = seen.get(ik)
+    if hit is not None and all(a is b for a, b in zip(hit[1], tensors)):
+        return hit[0]
+    content = tuple(None if t is None else (tuple(t.shape), str(t.dtype), t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes())
+                    for t in tensors)
+    if len(seen) >= 2:
+        seen.clear()
+    seen[ik] = (content, tensors)
+    return content
+
 
 WINO_X3_NAMES = ("az_conv2d_winograd_x3_f32", "az_conv2d_winograd_f16x2_f32")  # wino_x3.hip: the piece forms of the Winograd kernel
 H2_NAMES = ("az_conv2d_winograd_f16x2_f32", "az_conv2d_f16x2_f32")

@@ -15,8 +15,7 @@ class _GradTapes:
     output, planar) -> ``dx`` (the cotangent of the input, planar).  The backward tape only writes temporaries of its own, so it
     runs any number of times after one forward-keep run.  Plain ``Tape.run`` on the current stream: no graph capture."""
 
-    def __init__(self, device, B: int, cin: int, cout: int, H: int, W: int, mod_rows: int, D: int, versions, tokens: bool = False) -> None:
-        self.versions = versions
+    def __init__(self, device, B: int, cin: int, cout: int, H: int, W: int, mod_rows: int, D: int, tokens: bool = False) -> None:
         self.bld = Builder(device)
         if tokens:  # (B, L, C) token plans: the four buffers are views of the plan's own activations (_TokenGradTapes)
             self.x_in = self.out = self.v_in = self.dx = None
@@ -74,8 +73,8 @@ class _TokenGradTapes(_GradTapes):
     r""":class:`_GradTapes` on (B, L, C) token tensors: ``x_in`` / ``out`` / ``v_in`` / ``dx`` are views of the plan's own
     (channel-padded) activations, so nothing is rearranged on the way in or out."""
 
-    def __init__(self, device, B: int, L: int, cin: int, mod_rows: int, D: int, versions) -> None:
-        super().__init__(device, B, cin, cin, L, 1, mod_rows, D, versions, tokens=True)
+    def __init__(self, device, B: int, L: int, cin: int, mod_rows: int, D: int) -> None:
+        super().__init__(device, B, cin, cin, L, 1, mod_rows, D, tokens=True)
         self.B, self.L = B, L
 
     def _pinned(self, channels: int) -> Act:

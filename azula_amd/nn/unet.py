@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from ..engine import Act, Builder, Tape, ada_zero_triple, mod_front_tape, mod_rows, pad4, param_versions
+from ..engine import Act, Builder, PlanCache, Tape, ada_zero_triple, mod_front_tape, mod_rows, pad4
 from ..gradplan import _GradTapes
 from .. import _lib, engine
 
@@ -100,7 +100,7 @@ class UNetBlock(nn.Module):
             _conv_holder(ffn_factor * channels, channels, kernel_size),
         )
 
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     def _emit(self, bld: Builder, x: Act, D: int, mod_rows: int, mod_jobs: list, keep_input: bool = False,
               saved: dict | None = None) -> Act:
@@ -179,8 +179,8 @@ class UNetBlock(nn.Module):
         B, Cc, H, W = x.shape
         D = self.mod_features
 
-        def make(rows: int, versions: tuple) -> _GradTapes:
-            plan = _GradTapes(x.device, B, Cc, Cc, H, W, rows, D, versions)
+        def make(rows: int) -> _GradTapes:
+            plan = _GradTapes(x.device, B, Cc, Cc, H, W, rows, D)
             bld = plan.bld
             xin = bld.new_act(B, H, W, Cc, pinned=True)
             plan.fwd.add("az_nchw_to_nhwc_f32", xin.ptr, plan.x_in.data_ptr(), None, B, Cc, H * W, xin.cs)
@@ -204,18 +204,11 @@ class UNetBlock(nn.Module):
         return out, pullback
 
     def _cached_plan(self, x: Tensor, mod: Tensor | None, make, vjp: bool = False):
-        r"""(plan, modulation rows) of this block for ``x`` (B, C, *dims) and ``mod``: the cached plan while the parameters are what
-        it was built for, else ``make(rows, versions)``.  A forward plan (a tuple that starts with its versions) replaces every
-        cached plan; a gradient plan lives beside them under a ``"vjp"`` key."""
+        r"""(plan, modulation rows) of this block for ``x`` (B, C, *dims) and ``mod``: the cached plan, else ``make(rows)``.  A
+        gradient plan lives beside the forward ones under a ``"vjp"`` key."""
         rows = mod_rows(mod, x.shape[0], self.mod_features, "block")
         key = (*(("vjp",) if vjp else ()), x.shape[0], *x.shape[2:], rows, str(x.device))
-        versions = param_versions(self)
-        plan = self._plans.get(key)
-        if plan is None or (plan.versions if vjp else plan[0]) != versions:
-            if not vjp:
-                self._plans.clear()
-            plan = self._plans[key] = make(rows, versions)
-        return plan, rows
+        return self._plans.get(key, lambda: make(rows), self), rows
 
     @torch.no_grad()
     @_lib.on_device
@@ -238,7 +231,7 @@ class UNetBlock(nn.Module):
         planes, (H, W) = (dims[0] if vol else 1), dims[-2:]
         D = self.mod_features
 
-        def make(rows: int, versions: tuple) -> tuple:
+        def make(rows: int) -> tuple:
             bld = Builder(x.device, half=next(self.parameters()).dtype)
             xin = bld.new_act(B * planes, H, W, Cc, pinned=True)
             mod_buf = torch.empty(max(rows, 1), max(D, 1), dtype=torch.float32, device=x.device)
@@ -256,9 +249,9 @@ class UNetBlock(nn.Module):
                 tape.extend(bld.tape)
             res = torch.empty(B, Cc, *dims, dtype=torch.float32, device=x.device)
             tape.add("az_nhwc_to_nchw_f32", res.data_ptr(), out.buf.data_ptr(), B, Cc, math.prod(dims), out.cs)
-            return (versions, xin, mod_buf, tape, res)
+            return (xin, mod_buf, tape, res)
 
-        (_, xin, mod_buf, tape, res), rows = self._cached_plan(x, mod, make)
+        (xin, mod_buf, tape, res), rows = self._cached_plan(x, mod, make)
         xs = x.to(torch.float32).contiguous()
         _lib.call("az_nchw_to_nhwc_f32", xin.ptr, xs.data_ptr(), None, B, Cc, math.prod(dims), xin.cs, _lib.stream_ptr())
         if rows:
@@ -300,7 +293,6 @@ class UNetPlan:
         self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
         self.mod_rows = mod_rows
         self.out = torch.empty(B, net.out_channels, H, W, dtype=torch.float32, device=device)
-        self.versions = net._param_versions()
         mod_jobs: list[tuple] = []  # queued modulation MLPs (ada_zero_triple), emitted together at the tape front
         _walk(net, bld, self.x_in, self.out, mod_rows, mod_jobs, planar=self.planar)
         bld.finish()
@@ -388,7 +380,7 @@ class UNetGradPlan(_GradTapes):
 
     def __init__(self, net: "UNet", B: int, H: int, W: int, mod_rows: int, device: torch.device) -> None:
         cin, D = net.in_channels, net.mod_features
-        super().__init__(device, B, cin, net.out_channels, H, W, mod_rows, D, net._param_versions())
+        super().__init__(device, B, cin, net.out_channels, H, W, mod_rows, D)
         bld = self.bld
         L = len(net.hid_blocks)
         sv = (net.stride, net.stride) if isinstance(net.stride, int) else tuple(net.stride)
@@ -496,38 +488,20 @@ class UNet(nn.Module):
                 up.insert(0, _conv_holder(hid_channels[i] + hid_channels[i + 1], hid_channels[i], ks, identity_init=identity_init))
             self.descent.append(do)
             self.ascent.insert(0, up)
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     # -- plan management -----------------------------------------------------------------------
-    def _param_versions(self) -> tuple:
-        return param_versions(self)
-
     def plan3d(self, B: int, D: int, H: int, W: int, mod_rows: int, device: torch.device):
         from .unet3d import UNet3DPlan
 
-        key = (B, D, H, W, mod_rows, str(device))
-        p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
-            p = UNet3DPlan(self, B, D, H, W, mod_rows, device)
-            self._plans[key] = p
-        return p
+        return self._plans.get((B, D, H, W, mod_rows, str(device)), lambda: UNet3DPlan(self, B, D, H, W, mod_rows, device), self)
 
     def plan(self, B: int, H: int, W: int, mod_rows: int, device: torch.device) -> UNetPlan:
-        key = (B, H, W, mod_rows, str(device))
-        p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
-            p = UNetPlan(self, B, H, W, mod_rows, device)
-            self._plans[key] = p
-        return p
+        return self._plans.get((B, H, W, mod_rows, str(device)), lambda: UNetPlan(self, B, H, W, mod_rows, device), self)
 
     # -- input gradient --------------------------------------------------------------------------------------------
     def grad_plan(self, B: int, H: int, W: int, mod_rows: int, device: torch.device) -> UNetGradPlan:
-        key = ("vjp", B, H, W, mod_rows, str(device))
-        p = self._plans.get(key)
-        if p is None or p.versions != self._param_versions():
-            p = UNetGradPlan(self, B, H, W, mod_rows, device)
-            self._plans[key] = p
-        return p
+        return self._plans.get(("vjp", B, H, W, mod_rows, str(device)), lambda: UNetGradPlan(self, B, H, W, mod_rows, device), self)
 
     @torch.no_grad()
     @_lib.on_device

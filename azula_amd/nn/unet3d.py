@@ -227,7 +227,6 @@ class UNet3DPlan:
         self.x_in = Vol(xa, B, D)
         self.mod = torch.empty(max(mod_rows, 1), max(Dm, 1), dtype=torch.float32, device=device)
         self.out = torch.empty(B, net.out_channels, D, H, W, dtype=torch.float32, device=device)
-        self.versions = net._param_versions()
         L = len(net.hid_blocks)
         stride, per = net.stride, net.periodic
         sv = (stride,) * 3 if isinstance(stride, int) else tuple(stride)

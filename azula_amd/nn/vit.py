@@ -29,7 +29,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _lib, engine
-from ..engine import Act, Builder, LinearView, SharedResidual, ada_zero_triple, mod_front_tape, mod_rows, pad4, param_versions
+from ..engine import Act, Builder, LinearView, PlanCache, SharedResidual, ada_zero_triple, content_key, mod_front_tape, mod_rows, pad4
 from ..gradplan import _TokenGradTapes
 
 __all__ = ["DiT", "DiTBlock", "MultiheadSelfAttention", "ViT"]
@@ -63,7 +63,7 @@ class MultiheadSelfAttention(nn.Module):
             self.theta_proj = None
         self.heads = attention_heads
         self.qk_norm = qk_norm
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     def _emit(self, bld: Builder, y: Act, pos_h: Tensor | None, mask: Tensor | None, res: Act | None = None,
               saved: dict | None = None) -> Act:
@@ -170,7 +170,6 @@ class _TokenPlan:
 
     def __init__(self, module: nn.Module, B: int, L: int, Cin: int, pos_h, mod_rows: int, D: int, emit, device) -> None:
         bld = self.bld = Builder(device, half=next(module.parameters()).dtype, half_act=_half_act_ok(module) and Cin % 8 == 0)
-        self.versions = param_versions(module)
         self.x_in = bld.new_act(B, L, 1, Cin, pinned=True)
         self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
         self.mod_jobs: list = []
@@ -198,47 +197,26 @@ class _TokenPlan:
         return o.buf.view(B, L, o.cs)[..., : o.C].reshape(*x.shape[:-1], o.C).clone()
 
 
+def _host_pos(pos: Tensor | None, L: int) -> Tensor | None:
+    r"""Positions as the emitters read them: (L, P) fp32 on the host."""
+    return None if pos is None else pos.detach().to("cpu", torch.float32).reshape(L, -1)
+
+
 def _cached_token_plan(module, x: Tensor, pos, mask, D: int, mod: Tensor | None, make, vjp: bool = False):
-    r"""Plan cache of a standalone token module, keyed on shapes, positions, mask content and parameter versions (gradient plans
-    under a ``"vjp"`` key beside the forward ones).  ``make(B, L, Cin, rows, pos_h, versions)`` builds a missing or stale plan."""
+    r"""The plan of a standalone token module for shapes, modulation rows and the CONTENT of positions and mask, both baked into
+    it (RoPE tables, mask bytes); gradient plans under a ``"vjp"`` key beside the forward ones.  ``make(B, L, Cin, rows, pos_h)``
+    builds a missing or stale plan."""
     assert x.ndim >= 2, "expected (*, L, C) tokens"
     L, Cin = x.shape[-2], x.shape[-1]
     B = x.numel() // (L * Cin)
     rows = mod_rows(mod, B, D, "block", tokens=True)
-    # Positions and mask are BAKED into the plan (RoPE tables, mask bytes).  The key holds their CONTENT (bytes compare by
-    # value: no hash-collision reuse); a tensor already seen -- same storage, shape and version counter -- is recognised
-    # without copying it to the host again, so a steady-state call does not synchronise the device.
-    def ident(t):
-        return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), str(t.dtype), str(t.device))
-
-    def host(t):
-        return None if t is None else t.detach().to("cpu", torch.float32).reshape(L, -1)
-
-    seen = module.__dict__.setdefault("_plan_seen", {})
-    ik = (ident(pos), ident(mask))
-    hit = seen.get(ik)  # (content, pos, mask): the tensors are kept alive, so their storage cannot be handed to others
-    content = hit[0] if hit is not None and hit[1] is pos and hit[2] is mask else None
-    pos_h = None
-    if content is None:
-        pos_h = host(pos)
-        content = (None if pos_h is None else pos_h.numpy().tobytes(),
-                   None if mask is None else (tuple(mask.shape), mask.detach().cpu().numpy().tobytes()))
-        if len(seen) >= 2:
-            seen.clear()
-        seen[ik] = (content, pos, mask)
-    key = (*(("vjp",) if vjp else ()), B, L, Cin, rows, str(x.device), content)
-    versions = param_versions(module)
-    plan = module._plans.get(key)
-    if plan is None or plan.versions != versions:
-        if not vjp and (plan is not None or len(module._plans) >= 4):
-            module._plans.clear()  # stale parameters, or more than a few live (positions, mask) variants
-        plan = module._plans[key] = make(B, L, Cin, rows, host(pos) if pos_h is None else pos_h, versions)
-    return plan
+    key = (*(("vjp",) if vjp else ()), B, L, Cin, rows, str(x.device), content_key(module, pos, mask))
+    return module._plans.get(key, lambda: make(B, L, Cin, rows, _host_pos(pos, L)), module)
 
 
 def _token_plan(module, x: Tensor, pos, mask, D: int, emit, mod: Tensor | None = None) -> _TokenPlan:
     return _cached_token_plan(module, x, pos, mask, D, mod,
-                              lambda B, L, Cin, rows, pos_h, versions: _TokenPlan(module, B, L, Cin, pos_h, rows, D, emit, x.device))
+                              lambda B, L, Cin, rows, pos_h: _TokenPlan(module, B, L, Cin, pos_h, rows, D, emit, x.device))
 
 
 def _vjp_scope(module: nn.Module, x: Tensor, name: str) -> None:
@@ -255,8 +233,8 @@ def _vjp_scope(module: nn.Module, x: Tensor, name: str) -> None:
 
 def _token_grad_plan(module, x: Tensor, pos, mask, D: int, mod: Tensor | None, build) -> _TokenGradTapes:
     r"""The gradient plan of a standalone token module from the same cache; ``build(plan, x_in, pos_h)`` emits both tapes."""
-    def make(B, L, Cin, rows, pos_h, versions):
-        plan = _TokenGradTapes(x.device, B, L, Cin, rows, D, versions)
+    def make(B, L, Cin, rows, pos_h):
+        plan = _TokenGradTapes(x.device, B, L, Cin, rows, D)
         build(plan, plan.token_input(Cin), pos_h)
         return plan
 
@@ -295,7 +273,7 @@ class DiTBlock(nn.Module):
             nn.Identity() if dropout is None else nn.Dropout(dropout),
             nn.Linear(ffn_factor * channels // (2 if ffn_activation == "swiglu" else 1), channels),
         )
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     _ACT_KIND = {"silu": 1, "relu": 2, "relu2": 3}
 
@@ -428,7 +406,6 @@ class DiTPlan:
         D, C_ = net.mod_features, net.hid_channels
         self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
         self.mod_rows = mod_rows
-        self.versions = param_versions(net)
         cin = net.in_proj.in_features
         cout = net.out_proj.out_features
         if patch is not None:
@@ -481,7 +458,7 @@ class DiTGradPlan(_TokenGradTapes):
     def __init__(self, net: "DiT", B: int, L: int, pos: Tensor, mod_rows: int, device) -> None:
         D, C_ = net.mod_features, net.hid_channels
         cin, cout = net.in_proj.in_features, net.out_proj.out_features
-        super().__init__(device, B, L, cin, mod_rows, D, param_versions(net))
+        super().__init__(device, B, L, cin, mod_rows, D)
         bld = self.bld
         tokens = self.token_input(cin)
         x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=SharedResidual(_pos_table(net, bld, pos, L)))
@@ -533,7 +510,7 @@ class DiT(nn.Module):
             DiTBlock(channels=hid_channels, pos_channels=pos_channels, mod_features=mod_features, **kwargs)
             for _ in range(hid_blocks)
         ])
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     def _check_device(self, x: Tensor) -> torch.dtype:
         from .utils import backbone_io_dtype
@@ -543,12 +520,11 @@ class DiT(nn.Module):
     def _mod_rows(self, mod, B: int) -> int:
         return mod_rows(mod, B, self.mod_features, "network")
 
-    def _get_plan(self, key, make):
-        p = self._plans.get(key)
-        if p is None or p.versions != param_versions(self):
-            p = make()
-            self._plans[key] = p
-        return p
+    def _pos(self, pos: Tensor | None, L: int) -> tuple:
+        r"""(key element, host loader) of the positions a plan bakes in: ``None`` stands for the sequence indices."""
+        if pos is None:
+            return None, lambda: torch.arange(L, dtype=torch.float32)[:, None]
+        return content_key(self, pos), lambda: _host_pos(pos, L)
 
     @torch.no_grad()
     @_lib.on_device
@@ -561,13 +537,8 @@ class DiT(nn.Module):
         x = x.to(torch.float32).contiguous()
         B, L, Cin = x.shape
         rows = self._mod_rows(mod, B)
-        if pos is None:
-            pos_h = torch.arange(L, dtype=torch.float32)[:, None]
-            pkey = None
-        else:
-            pos_h = pos.detach().to("cpu", torch.float32).reshape(L, -1)
-            pkey = hash(pos_h.numpy().tobytes())
-        plan = self._get_plan((B, L, rows, pkey, str(x.device)), lambda: DiTPlan(self, B, L, pos_h, rows, x.device))
+        pkey, pos_h = self._pos(pos, L)
+        plan = self._plans.get((B, L, rows, pkey, str(x.device)), lambda: DiTPlan(self, B, L, pos_h(), rows, x.device), self)
         t = plan.tokens
         if t.cs == Cin:
             t.buf.copy_(x.reshape(-1))
@@ -595,12 +566,8 @@ class DiT(nn.Module):
         assert x.ndim == 3, "DiT.vjp expects (B, L, C) tokens"
         B, L, _ = x.shape
         rows = self._mod_rows(mod, B)
-        if pos is None:
-            pos_h, pkey = torch.arange(L, dtype=torch.float32)[:, None], None
-        else:
-            pos_h = pos.detach().to("cpu", torch.float32).reshape(L, -1)
-            pkey = pos_h.numpy().tobytes()
-        plan = self._get_plan(("vjp", B, L, rows, pkey, str(x.device)), lambda: DiTGradPlan(self, B, L, pos_h, rows, x.device))
+        pkey, pos_h = self._pos(pos, L)
+        plan = self._plans.get(("vjp", B, L, rows, pkey, str(x.device)), lambda: DiTGradPlan(self, B, L, pos_h(), rows, x.device), self)
         return plan.run(x, mod)
 
 
@@ -672,9 +639,10 @@ class ViT(DiT):
         Hp, Wp = H // p, W // p
         pos = torch.cartesian_prod(torch.arange(Hp, dtype=torch.float32), torch.arange(Wp, dtype=torch.float32))
         pos = pos.reshape(-1, 2)
-        return self._get_plan(
+        return self._plans.get(
             ("vit", B, H, W, rows, str(device)),
             lambda: DiTPlan(self, B, Hp * Wp, pos, rows, device, patch=(self.image_in + self.image_cond, H, W, p, self.unpatch_size)),
+            self,
         )
 
     @torch.no_grad()

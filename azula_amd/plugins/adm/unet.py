@@ -30,7 +30,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder, pad8, param_versions
+from ...engine import Act, Builder, PlanCache, pad8
 from ...gradplan import _GradTapes
 
 __all__ = ["UNetModel"]
@@ -417,7 +417,6 @@ class ADMPlan:
         half_act = (net.dims != 3 and all(c % 128 == 0 for c in chans) and net.model_channels % 8 == 0
                     and (x_in is None or x_in.cs == pad8(net.in_channels)))  # (a shared input: the first program's, same stride)
         bld = self.bld = Builder(device, half=next(net.parameters()).dtype, half_act=half_act)
-        self.versions = param_versions(net)
         self.emb_rows = emb_rows
         cin, three_d = net.in_channels, net.dims == 3
         PB = B * D
@@ -444,7 +443,7 @@ class ADMGradPlan(_GradTapes):
     the pullback.  ``dims`` 1 and 2, fp32."""
 
     def __init__(self, net: "UNetModel", B: int, H: int, W: int, emb_rows: int, device, frac: bool = False) -> None:
-        super().__init__(device, B, net.in_channels, net.out_channels, H, W, 0, 0, param_versions(net))
+        super().__init__(device, B, net.in_channels, net.out_channels, H, W, 0, 0)
         bld = self.bld
         one_d = net.dims == 1
         assert net.dims in (1, 2) and (not one_d or H == 1)
@@ -660,25 +659,17 @@ class UNetModel(nn.Module):
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(nn.GroupNorm(32, ch), nn.SiLU(), _zero(conv(ch, out_channels, 3, padding=1)))
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     def plan(self, B, H, W, emb_rows, device, x_in: Act | None = None, coef_ptr: int | None = None, tag=None, frac=False,
              D: int = 1) -> ADMPlan:
         key = (B, D, H, W, emb_rows, str(device), x_in.ptr if x_in is not None else None, coef_ptr, tag, frac)
-        p = self._plans.get(key)
-        if p is None or p.versions != param_versions(self):
-            p = ADMPlan(self, B, H, W, emb_rows, device, x_in=x_in, coef_ptr=coef_ptr, frac=frac, D=D)
-            self._plans[key] = p
-        return p
+        return self._plans.get(key, lambda: ADMPlan(self, B, H, W, emb_rows, device, x_in=x_in, coef_ptr=coef_ptr, frac=frac, D=D), self)
 
     # -- input gradient --------------------------------------------------------------------------------------------
     def grad_plan(self, B, H, W, emb_rows, device, frac=False) -> ADMGradPlan:
         key = ("vjp", B, H, W, emb_rows, str(device), frac)
-        p = self._plans.get(key)
-        if p is None or p.versions != param_versions(self):
-            p = ADMGradPlan(self, B, H, W, emb_rows, device, frac=frac)
-            self._plans[key] = p
-        return p
+        return self._plans.get(key, lambda: ADMGradPlan(self, B, H, W, emb_rows, device, frac=frac), self)
 
     @torch.no_grad()
     @_lib.on_device

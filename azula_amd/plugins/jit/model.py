@@ -31,7 +31,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder, LinearView, SharedResidual, param_versions
+from ...engine import Act, Builder, LinearView, PlanCache, SharedResidual, param_versions
 from ...gradplan import _GradTapes
 
 __all__ = ["JiT", "JiTGradPlan", "JiT_models"]
@@ -291,7 +291,6 @@ class JiTPlan:
         half_act = net.hidden_size % 8 == 0 and all((blk.mlp.w12.weight.shape[0] // 2) % 8 == 0 for blk in net.blocks) and net.hidden_size <= 4096
         bld = self.bld = Builder(device, half=net.pos_embed.dtype, half_act=half_act)
         Z, S = net.in_channels, net.input_size
-        self.versions = param_versions(net)
         self.x_nchw = torch.empty(B, Z, S, S, dtype=torch.float32, device=device)
         self.out = torch.empty(B, Z, S, S, dtype=torch.float32, device=device)
         _emit_forward(self, net, B, t_shared, self.x_nchw, self.out)
@@ -313,7 +312,7 @@ class JiTGradPlan(_GradTapes):
     def __init__(self, net: "JiT", B: int, t_shared: bool, device) -> None:
         Hd, p, Z = net.hidden_size, net.patch_size, net.in_channels
         S = net.input_size
-        super().__init__(device, B, Z, Z, S, S, 0, 0, param_versions(net))
+        super().__init__(device, B, Z, Z, S, S, 0, 0)
         self._net = weakref.ref(net)
         bld = self.bld
         L, Lc = (S // p) ** 2, net.in_context_len
@@ -385,12 +384,13 @@ class JiTGradPlan(_GradTapes):
         self.labels.copy_(y.to(device=x.device, dtype=torch.int64).expand(self.labels.shape[0]))
         out, pull = self.run(x, None)
         net = self._net
+        versions = param_versions(net())
 
         def pullback(v: Tensor) -> Tensor:
             # the tapes read the norm gains, biases and tables where the module keeps them, the GEMM weights from packed copies:
             # after an in-place parameter change the saved tensors no longer belong to what the backward tape would read
             m = net()
-            if m is None or param_versions(m) != self.versions:
+            if m is None or param_versions(m) != versions:
                 raise RuntimeError("this pullback belongs to an earlier vjp call: the module's parameters have changed since, "
                                    "and its saved tensors belong to the old ones")
             return pull(v)
@@ -471,22 +471,14 @@ class JiT(nn.Module):
             for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.w12, blk.mlp.w3):
                 nn.init.xavier_uniform_(lin.weight)
                 nn.init.zeros_(lin.bias)
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     def plan(self, B: int, t_shared: bool, device) -> JiTPlan:
-        key = (B, t_shared, str(device))
-        p = self._plans.get(key)
-        if p is None or p.versions != param_versions(self):
-            p = self._plans[key] = JiTPlan(self, B, t_shared, device)
-        return p
+        return self._plans.get((B, t_shared, str(device)), lambda: JiTPlan(self, B, t_shared, device), self)
 
     # -- input gradient --------------------------------------------------------------------------------------------
     def grad_plan(self, B: int, t_shared: bool, device) -> JiTGradPlan:
-        key = ("vjp", B, t_shared, str(device))
-        p = self._plans.get(key)
-        if p is None or p.versions != param_versions(self):
-            p = self._plans[key] = JiTGradPlan(self, B, t_shared, device)
-        return p
+        return self._plans.get(("vjp", B, t_shared, str(device)), lambda: JiTGradPlan(self, B, t_shared, device), self)
 
     @torch.no_grad()
     @_lib.on_device

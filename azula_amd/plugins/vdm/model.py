@@ -27,7 +27,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder
+from ...engine import Act, Builder, PlanCache
 
 __all__ = ["ARCHITECTURES", "VDMModel", "VDMPlan", "ResConvBlock", "SelfAttention2d", "SkipBlock", "FourierFeatures"]
 
@@ -143,11 +143,6 @@ def _level_modules(a: dict, c: int) -> nn.Sequential:
 CONV_OVERRIDE: dict | None = None
 
 
-def _mode_key() -> tuple:
-    r"""What a plan bakes in besides shapes and weights: the arithmetic mode and the kernel override."""
-    return (engine.FP32_MFMA, engine.WINOGRAD, tuple(sorted(CONV_OVERRIDE.items())) if CONV_OVERRIDE else None)
-
-
 class VDMPlan:
     r"""Compiled forward of a ``nn.Sequential`` of ResConvBlock / SelfAttention2d / SkipBlock / AvgPool2d / Upsample modules for
     one (batch, H, W).  ``embed = (weight, mode)``: the input carries 3 image channels and the Fourier planes of the time in
@@ -156,7 +151,6 @@ class VDMPlan:
     def __init__(self, seq: nn.Sequential, B: int, H: int, W: int, cin: int, device, *, embed: tuple | None = None,
                  coef_ptr: int | None = None) -> None:
         bld = self.bld = Builder(device)
-        self.versions = _param_versions(seq) + (() if embed is None else _param_versions(embed[0]))
         cs = bld.pad(cin)
         self.x_in = Act(torch.zeros(B * H * W * cs, dtype=torch.float32, device=device), B, H, W, cin, cs, True)
         self.t = torch.zeros(B, dtype=torch.float32, device=device)
@@ -281,11 +275,6 @@ class VDMPlan:
         return self.out.clone()
 
 
-def _param_versions(m: nn.Module | Tensor) -> tuple:
-    ps = [m] if torch.is_tensor(m) else list(m.parameters())
-    return tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps)
-
-
 class VDMModel(nn.Module):
     r"""One of the six v-diffusion backbones (``model``: a key of :data:`ARCHITECTURES`).  ``base_channels`` (default: the
     model's own 128 / 256) is this project's one extension, for narrow test networks.  ``forward(x, t)``: x (B, 3, H, W) with
@@ -306,7 +295,7 @@ class VDMModel(nn.Module):
         self.out_channels = 3
         self.timestep_embed = FourierFeatures(1, 16, std=a["std"])
         self.net = _level_modules(a, c)
-        self._plans: dict = {}
+        self._plans = PlanCache()
 
     # -- half precision: out of scope ---------------------------------------------------------------------------------
     def half(self):
@@ -320,16 +309,12 @@ class VDMModel(nn.Module):
             raise ValueError(f"vdm {self.model}: H and W must be multiples of {1 << self.depth} ({self.depth} poolings), got {H} x {W}")
         if next(self.parameters()).dtype != torch.float32:
             raise NotImplementedError("azula_amd.plugins.vdm: half-precision VDM backbones are not implemented (fp32 parameters only)")
-        key = (B, H, W, str(device), coef_ptr, _mode_key())
-        p = self._plans.get(key)
-        versions = _param_versions(self)
-        if p is None or p.net_versions != versions:
-            mode = 1 if self.arch["embed"] == "log_snr" else 0
-            p = VDMPlan(self.net, B, H, W, 3 + 16, device, embed=(self.timestep_embed.weight, mode), coef_ptr=coef_ptr)
-            p.net_versions = versions
-            self._plans = {k: v for k, v in self._plans.items() if v.net_versions == versions}
-            self._plans[key] = p
-        return p
+        mode = 1 if self.arch["embed"] == "log_snr" else 0
+        return self._plans.get(
+            (B, H, W, str(device), coef_ptr),
+            lambda: VDMPlan(self.net, B, H, W, 3 + 16, device, embed=(self.timestep_embed.weight, mode), coef_ptr=coef_ptr),
+            self, extra=tuple(sorted(CONV_OVERRIDE.items())) if CONV_OVERRIDE else (),
+        )
 
     @torch.no_grad()
     @_lib.on_device

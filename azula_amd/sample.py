@@ -31,7 +31,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import COEF_FIELDS, COEF_WORDS
 from .denoise import Denoiser, axpby_wide, is_wide, require_f32_cuda
-from .engine import StepGraph, Tape, transition_args
+from .engine import StepGraph, Tape, plan_mode, transition_args
 
 SLICED_NOISE = os.environ.get("AZ_SLICED_NOISE", "1") != "0"  # sharded batches: draw only the rank's slice of the full-batch noise
 WIDE_FUSED = os.environ.get("AZ_WIDE_FUSED", "1") != "0"  # captured loop for Sampler(dtype=float64) ("0": the generic fp64 loop)
@@ -384,8 +384,8 @@ class Sampler(abc.ABC):
 
     def _call_fused(self, x: Tensor, kwargs: dict) -> Tensor | None:
         r"""The captured loop is cached per sampler, keyed on everything that is BAKED into it: the latent's shape and
-        device, the structure of the keyword arguments, the step count / noise use, and a fingerprint of the denoiser
-        (address, version counter and dtype of every parameter and buffer, train/eval flags).  The reference re-reads
+        device, the structure of the keyword arguments, the step count / noise use, the arithmetic mode (``engine.plan_mode``)
+        and a fingerprint of the denoiser (address, version counter and dtype of every parameter and buffer, train/eval flags).  The reference re-reads
         weights, guidance and hyper-parameters on every call (``azula/sample.py:139-161``); so does this: after
         ``load_state_dict`` / ``.half()`` / ``.train()`` the plan is rebuilt, and values that only live in the
         coefficient table (guidance, eta, temperature, start / stop, the schedule) are re-uploaded by ``run``."""
@@ -396,7 +396,7 @@ class Sampler(abc.ABC):
         wide = not (x.dtype == torch.float32 and self.dtype in (None, torch.float32))
         key = (
             tuple(x.shape), str(dev), _kwargs_signature(kwargs), self._fused_structure(), id(self.denoiser),
-            module_fingerprint(self.denoiser), str(x.dtype), wide, getattr(self.denoiser, "_az_fused_key", tuple)(),
+            module_fingerprint(self.denoiser), str(x.dtype), wide, getattr(self.denoiser, "_az_fused_key", tuple)(), plan_mode(),
         )
         ent = self._fused_cache.get(key)
         if ent is _NOT_WIDE:

@@ -46,7 +46,6 @@ def test_c2_channel_plan_against_the_oracle(c2_net, policy, monkeypatch):
     den, x1, ref_mean, ref_x0 = c2_net
     monkeypatch.setattr(engine, "WINOGRAD", policy)
     net = den.backbone.net
-    net._plans.clear()
     mean = den(x1.cuda(), torch.tensor(0.6, device="cuda")).mean
     ops = [n for _, _, n in next(iter(net._plans.values())).tape.ops]
     nw, nd = sum(ops.count(n) for n in WINO_OPS), sum(ops.count(n) for n in DIRECT_OPS)  # (whatever the AZ_FP32_MFMA mode)
@@ -101,7 +100,6 @@ def test_c2_channel_plan_under_the_f4_policy(c2_net, monkeypatch):
     monkeypatch.setattr(engine, "WINOGRAD", "4")
     monkeypatch.setattr(engine, "WINOGRAD4_MIN_TILES", 16)
     net = den.backbone.net
-    net._plans.clear()
     mean = den(x1.cuda(), torch.tensor(0.6, device="cuda")).mean
     ops = [n for _, _, n in next(iter(net._plans.values())).tape.ops]
     n4 = ops.count("az_conv2d_winograd4_f32")

@@ -251,10 +251,8 @@ def test_vit_half_activations_in_hbm(golden, half, monkeypatch):
     print("vit, half activations", half, "q99/scale", q99, "max/scale", mx)
     assert q99 < bq and mx < bm
     monkeypatch.setattr(engine, "HALF_ACT", False)
-    net._plans.clear()
     y32 = net(xin, mod)
     assert not next(iter(net._plans.values())).bld.half_act
-    net._plans.clear()
     q99b, mxb, _, _ = _bar(g["y_modB"].cuda(), y32, half)
     print("vit, fp32 activations ", half, "q99/scale", q99b, "max/scale", mxb)
     assert q99b < bq and mxb < bm
@@ -328,12 +326,10 @@ def test_unet_half_activations_in_hbm(half, norm):
     mp = _p.MonkeyPatch()
     try:
         mp.setattr(engine, "HALF_ACT", False)
-        net._plans.clear()
         y16b = net(x.to(half), mod.to(half))
         assert not next(iter(net._plans.values())).bld.half_act
     finally:
         mp.undo()
-        net._plans.clear()
     q99b, mxb, _, _ = _bar(y32, y16b, half)
     print("unet", norm, "fp32 activations ", half, "q99/scale", q99b, "max/scale", mxb)
     assert q99b < bq and mxb < bm

@@ -193,18 +193,23 @@ def test_invalidate_after_a_raw_weight_write_adm():
     assert torch.equal(b, fresh) and not torch.equal(a, b)
 
 
-def _small_cond_adm():
-    from azula_amd.guidance import CFGDenoiser
+def _small_adm(**kwargs):
     from azula_amd.plugins import adm
 
     torch.manual_seed(0)
-    den = adm.make_model(image_size=16, num_channels=32, channel_mult=(1, 2), attention_resolutions=(8,), num_classes=10,
-                         num_res_blocks=2, num_head_channels=32, resblock_updown=True, use_scale_shift_norm=True)
+    den = adm.make_model(image_size=16, num_channels=32, channel_mult=(1, 2), attention_resolutions=(8,),
+                         num_res_blocks=2, num_head_channels=32, resblock_updown=True, use_scale_shift_norm=True, **kwargs)
     g = torch.Generator().manual_seed(123)
     for _, v in sorted(den.backbone.state_dict().items()):
         if torch.is_floating_point(v) and v.ndim > 1 and not torch.any(v != 0):
             v.copy_(torch.randn(v.shape, generator=g) / math.sqrt(v[0].numel()))
-    den = den.cuda().eval()
+    return den.cuda().eval()
+
+
+def _small_cond_adm():
+    from azula_amd.guidance import CFGDenoiser
+
+    den = _small_adm(num_classes=10)
     return den, CFGDenoiser(den)
 
 
@@ -301,3 +306,161 @@ def test_tensor_valued_hyper_parameters_reach_the_table(golden):
     torch.manual_seed(3)
     fresh2 = DDIMSampler(den2, steps=6, eta=1.0, silent=True)(x1)
     assert max_err(c, fresh2) < 1e-6 * max(1.0, fresh2.abs().max().item()) and not torch.equal(c, b)
+
+
+# ------------------------------------------------------------------------------------------------ engine.PlanCache on every backbone
+# The smallest nets of every family whose tape differs between FP32_MFMA = "f16x2" and "native": 32 channels and more put their
+# convolutions / token GEMMs on the piece kernels in the first mode and on the fp32 kernels in the second (engine.choose_conv,
+# the rows of tests/test_host_choice.py), so a plan that survived the flip would show in the op names.
+def _gen_inputs(seed, *shapes):
+    g = torch.Generator().manual_seed(seed)
+    return tuple(torch.randn(s, generator=g).cuda() for s in shapes)
+
+
+def _unet():
+    from azula_amd.nn import UNet
+
+    torch.manual_seed(40)
+    net = UNet(3, 3, hid_channels=(32, 64), hid_blocks=(1, 1), norm="group", groups=4, mod_features=16)
+    return net.cuda().eval(), _gen_inputs(41, (2, 3, 16, 16), (2, 16))
+
+
+def _unet_block():
+    from azula_amd.nn import UNetBlock
+
+    torch.manual_seed(42)
+    return UNetBlock(32, mod_features=16, norm="group", groups=4).cuda().eval(), _gen_inputs(43, (2, 32, 16, 16), (2, 16))
+
+
+def _adm_backbone():
+    (x,) = _gen_inputs(44, (2, 3, 16, 16))
+    return _small_adm().backbone, (x, torch.tensor([5, 700]).cuda())
+
+
+def _pos44():
+    return torch.cartesian_prod(torch.arange(4.0), torch.arange(4.0)).cuda()
+
+
+def _dit():
+    from azula_amd.nn import DiT
+
+    torch.manual_seed(45)
+    net = DiT(16, 16, pos_channels=2, mod_features=16, hid_channels=64, hid_blocks=2, attention_heads=4, rope=True).cuda().eval()
+    return net, (*_gen_inputs(46, (2, 16, 16), (2, 16)), _pos44())
+
+
+def _dit_block():
+    from azula_amd.nn import DiTBlock
+
+    torch.manual_seed(47)
+    blk = DiTBlock(64, mod_features=16, pos_channels=2, attention_heads=4, rope=True).cuda().eval()
+    return blk, (*_gen_inputs(48, (2, 16, 64), (2, 16)), _pos44())
+
+
+def _jit(golden):
+    from azula_amd.plugins import jit
+
+    g = golden("g10_jit_ctx")
+    net = jit.JiT(**g.meta["cfg"])
+    net.load_state_dict(synth.synth_state_dict({k: tuple(v) for k, v in g.meta["shapes"].items()}, g.meta["weight_seed"]))
+    return net.cuda().eval(), (g["x"].cuda(), torch.linspace(0.3, 0.8, 3).cuda(), g["y"].long().cuda())
+
+
+def _vdm():
+    from azula_amd.plugins.vdm.model import VDMModel
+
+    torch.manual_seed(49)
+    net = VDMModel("danbooru_128", base_channels=32).cuda().eval()  # (5 poolings: 32 x 32 is its smallest image)
+    return net, (*_gen_inputs(50, (1, 3, 32, 32)), torch.tensor([0.3]).cuda())
+
+
+FAMILIES = {"unet": _unet, "unet_block": _unet_block, "adm": _adm_backbone, "dit": _dit, "dit_block": _dit_block, "jit": _jit, "vdm": _vdm}
+
+
+@pytest.fixture(params=list(FAMILIES))
+def family(request, golden):
+    make = FAMILIES[request.param]
+    return (lambda: make(golden)) if make is _jit else make
+
+
+def _op_names(module) -> list:
+    r"""Op names of the module's one cached plan (a standalone UNetBlock's forward plan is a tuple around its tape)."""
+    (plan,) = module._plans.values()
+    tape = plan[2] if isinstance(plan, tuple) else plan.tape
+    return [n for _, _, n in tape.ops]
+
+
+def test_mode_flip_rebuilds_without_a_clear(family, monkeypatch):
+    from azula_amd import engine
+
+    monkeypatch.setattr(engine, "FP32_MFMA", "f16x2")
+    net, args = family()
+    net(*args)
+    names_f16x2 = _op_names(net)
+    monkeypatch.setattr(engine, "FP32_MFMA", "native")
+    y = net(*args)
+    fresh, fresh_args = family()
+    y_fresh = fresh(*fresh_args)
+    assert names_f16x2 != _op_names(fresh), "the two modes choose the same kernels at this shape: the test would pass vacuously"
+    assert _op_names(net) == _op_names(fresh)
+    assert torch.equal(y, y_fresh)
+
+
+def test_weight_change_rebuilds_and_drops_the_old_plan(family):
+    def scaled(net):
+        next(p for p in net.parameters() if p.ndim > 1).mul_(1.25)
+
+    net, args = family()
+    before = net(*args)
+    (old,) = net._plans.values()
+    scaled(net)
+    y = net(*args)
+    fresh, fresh_args = family()
+    scaled(fresh)
+    assert torch.equal(y, fresh(*fresh_args)) and not torch.equal(y, before)
+    assert all(p is not old for p in net._plans.values()) and len(net._plans) == 1
+
+
+def test_plans_of_one_backbone_are_bounded():
+    r"""Every fused loop of another batch size builds another plan on the denoiser's backbone; at most ``max_live`` stay."""
+    from azula_amd.sample import DDIMSampler
+
+    den = _small_adm()
+    smp = DDIMSampler(den, steps=2, silent=True)
+    for B in range(1, 7):
+        (x1,) = _gen_inputs(60 + B, (B, 3, 16, 16))
+        x0 = smp(x1)
+        assert next(iter(smp._fused_cache.values())).graph is not None
+    assert den.backbone._plans.max_live == 4 and len(den.backbone._plans) <= 4
+    assert [k[0] for k in den.backbone._plans] == [3, 4, 5, 6]  # (the oldest went first)
+    assert torch.equal(x0, DDIMSampler(_small_adm(), steps=2, silent=True)(x1))
+
+
+def test_fused_loop_sees_the_arithmetic_mode(monkeypatch):
+    from azula_amd import engine
+    from azula_amd.sample import DDIMSampler
+
+    (x1,) = _gen_inputs(70, (2, 3, 16, 16))
+    monkeypatch.setattr(engine, "FP32_MFMA", "f16x2")
+    smp = DDIMSampler(_small_adm(), steps=2, silent=True)
+    a = smp(x1)
+    loop = next(iter(smp._fused_cache.values()))
+    monkeypatch.setattr(engine, "FP32_MFMA", "native")
+    b = smp(x1)
+    assert next(iter(smp._fused_cache.values())) is not loop and len(smp._fused_cache) == 1
+    assert torch.equal(b, DDIMSampler(_small_adm(), steps=2, silent=True)(x1)) and not torch.equal(a, b)
+
+
+def test_positions_are_keyed_by_content():
+    r"""Two position tensors that differ in one value are two plans (their bytes are the key, not a hash of them), and equal
+    values in another tensor are the same plan."""
+    net, (x, mod, pos_a) = _dit()
+    pos_b = pos_a.clone()
+    pos_b[5, 1] += 0.5
+    ya, yb = net(x, mod, pos_a), net(x, mod, pos_b)
+    assert len(net._plans) == 2 and not torch.equal(ya, yb)
+    net(x, mod, pos_a.clone())
+    assert len(net._plans) == 2
+    for pos, y in ((pos_a, ya), (pos_b, yb)):
+        fresh, _ = _dit()
+        assert torch.equal(fresh(x, mod, pos), y)

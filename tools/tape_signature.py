@@ -132,8 +132,8 @@ def tensors_of(*roots) -> list:
 def plan_record(plan, module=None) -> dict:
     r"""Signatures of one plan: a forward plan (``.tape``, or a standalone block's tuple), or a gradient plan (``.fwd``, ``.bwd``)."""
     tapes = {}
-    if isinstance(plan, tuple):  # UNetBlock's one-block plans: (versions, x_in, mod, tape, out)
-        tapes["tape"] = plan[3]
+    if isinstance(plan, tuple):  # UNetBlock's one-block plans: (x_in, mod, tape, out)
+        tapes["tape"] = plan[2]
     elif hasattr(plan, "fwd"):
         tapes["fwd"], tapes["bwd"] = plan.fwd, plan.bwd
     else:
@@ -253,10 +253,7 @@ def unet_cases(rec: Recorder) -> None:
     torch.manual_seed(13)
     blk = UNetBlock(16, mod_features=16, norm="group", groups=4).cuda().eval()
     x, mod = torch.randn(2, 16, 12, 12, generator=gen).cuda(), torch.randn(2, 16, generator=gen).cuda()
-    y = blk(x, mod)
-    fwd_plans = dict(blk._plans)  # (a one-block forward plan clears the cache when it is built)
-    out, pull = blk.vjp(x, mod)
-    rec.save("unet.block", blk, {"y": y, "vjp_out": out, "dx": pull(_cotangent(out))}, plans={**fwd_plans, **blk._plans})
+    _fwd_vjp(rec, "unet.block", blk, x, mod)
     torch.manual_seed(14)
     blk3 = UNetBlock(16, mod_features=16, norm="group", groups=4, spatial=3, kernel_size=(3, 3, 3)).cuda().eval()
     rec.save("unet.block3d", blk3, {"y": blk3(torch.randn(2, 16, 4, 8, 8, generator=gen).cuda(), mod)})
