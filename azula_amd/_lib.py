@@ -405,6 +405,11 @@ PROTOTYPES: dict[str, list] = {
     "az_op_avgpool_adj_f32": [vp, vp, i64, i64, i64, i32, i32, f32, c_stream],
     "az_op_blur_f32": [vp, vp, vp, i32, vp, i32, i64, i64, i64, i32, c_stream],
     "az_op_blur_tile": [i32, i32, C.POINTER(i32), C.POINTER(i32)],
+    "az_op_psf_f32": [vp, vp, vp, i32, i32, i64, i64, i64, i64, i64, i64, i32, c_stream],
+    "az_op_psf_tile": [i32, i32, C.POINTER(i32), C.POINTER(i32)],
+    "az_op_decimate_f32": [vp, vp, i64, i64, i64, i32, i32, i32, i32, c_stream],
+    "az_op_decimate_adj_f32": [vp, vp, i64, i64, i64, i32, i32, i32, i32, c_stream],
+    "az_op_chanmix_f32": [vp, vp, vp, i64, i32, i32, i64, c_stream],
     "az_tds_chunks": [i64, i64],
     "az_tds_resample_f32": [vp, vp, vp, vp, vp, i64, c_stream],
     "az_tds_propose_f32": [C.POINTER(AzTdsProposeArgs), c_stream],

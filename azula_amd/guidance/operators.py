@@ -1,5 +1,6 @@
-r"""Measurement operators for the guidance methods: pixel mask, average-pool downsampling and separable blur, with exact
-adjoints and (where one exists) the pseudo-inverse.
+r"""Measurement operators for the guidance methods: pixel mask, average-pool downsampling, separable blur, general 2-D PSF
+(motion blur), decimation (bicubic super-resolution) and per-pixel channel mix (colourisation), with exact adjoints and (where
+one exists) the pseudo-inverse.
 
 The guidance classes take the operator :math:`A` of :math:`y = A x + n` as a callable and differentiate it with
 ``torch.autograd.grad`` (DPS, TMPD, MMPS, JFPS, DiffPIR) and ``torch.func.jvp`` (MMPS, JFPS).  The operators below are such
@@ -9,6 +10,9 @@ same bits) and a fixed launch sequence.  The project's own extension: the refere
     A = DownsampleOperator(2, flatten=True) @ BlurOperator.gaussian(1.0, 5)
     DiffPIRDenoiser(denoiser, y, A, var_y)              # y: (B, D)
     PGDMSampler(denoiser, y, M, M.pinv)                 # M = MaskOperator(mask)
+    PSFOperator(motion_psf(31.0, 30.0, 61), flatten=True)                        # motion deblurring
+    DecimateOperator(4, 2, flatten=True) @ BlurOperator(bicubic_taps(4))         # bicubic super-resolution x4
+    ChannelMixOperator.grayscale(flatten=True)                                   # colourisation
 
 Two paths, as ``RePaintSampler`` has them:
 
@@ -33,9 +37,11 @@ from torch import Tensor
 from .. import _lib
 from .repaint import _aligned, _broadcasts_to
 
-__all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps"]
+__all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps", "PSFOperator", "motion_psf",
+           "DecimateOperator", "bicubic_taps", "ChannelMixOperator"]
 
-MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_blur_f32)
+MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_decimate_f32 and of az_op_blur_f32 / az_op_psf_f32)
+MAX_CHANNELS = 16  # (the limit of az_op_chanmix_f32)
 
 
 def _launch(name: str, *args) -> None:
@@ -423,3 +429,265 @@ def blur_tile(nh: int, nw: int) -> tuple[int, int]:
     th, tw = C.c_int32(0), C.c_int32(0)
     _lib.call("az_op_blur_tile", nh, nw, C.byref(th), C.byref(tw))
     return th.value, tw.value
+
+
+# ------------------------------------------------------------------------------------------------------------------- PSF
+def motion_psf(length: float, angle: float, size: int) -> Tensor:
+    r"""A ``size`` x ``size`` line PSF (linear motion blur): a centred segment that covers ``length`` pixels, at ``angle``
+    degrees counter-clockwise from the horizontal axis, rasterised bilinearly -- 8 samples per pixel of length, each shared
+    between its four neighbouring pixels -- in fp64, normalised to sum 1 and then rounded to fp32.  Deterministic: no random
+    numbers.  ``angle = 0`` gives one row."""
+    if size < 1 or size % 2 == 0 or not 1 <= length <= size:
+        raise ValueError(f"motion_psf needs an odd size >= 1 and 1 <= length <= size, got size {size}, length {length}")
+    n = 8 * math.ceil(length) + 1
+    s = torch.linspace(-0.5, 0.5, n, dtype=torch.float64) * (length - 1)
+    rad = math.radians(angle)
+    right = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}  # (cos(pi / 2) is 6e-17 in fp64)
+    cos, sin = right.get(angle % 360.0, (math.cos(rad), math.sin(rad)))
+    c = (size - 1) / 2
+    px, py = c + s * cos, c - s * sin
+    x0, y0 = px.floor(), py.floor()
+    fx, fy = px - x0, py - y0
+    k = torch.zeros(size * size, dtype=torch.float64)
+    for dy, wy in ((0, 1 - fy), (1, fy)):
+        for dx, wx in ((0, 1 - fx), (1, fx)):
+            xi, yi = (x0 + dx).long(), (y0 + dy).long()
+            keep = (xi >= 0) & (xi < size) & (yi >= 0) & (yi < size)  # (a weight-0 neighbour may lie outside)
+            k.index_add_(0, (yi * size + xi)[keep], (wy * wx)[keep])
+    return (k / k.sum()).reshape(size, size).to(torch.float32)
+
+
+class PSFOperator(LinearOperator):
+    r"""Creates the blur by a general two-dimensional point-spread function (motion deblurring): the correlation
+    :math:`y_{bcij} = \sum_a \sum_{b'} k_{bc, a b'} \, \tilde x_{bc, i + a - r_h, j + b' - r_w}` of the input's size, with
+    the radii :math:`r = \lfloor k / 2 \rfloor`.
+
+    Arguments:
+        psf: The PSF: :math:`(k_h, k_w)` (one for all planes), :math:`(C, k_h, k_w)` (one per channel),
+            :math:`(B, 1, k_h, k_w)` (one per sample) or :math:`(B, C, k_h, k_w)` (one per plane).  Odd sizes of at most 65,
+            any values.  See :func:`motion_psf`.
+        padding: ``"zeros"`` or ``"circular"``, as for :class:`BlurOperator`.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    Every output is one chain of :math:`k_h k_w` fused multiply-adds from 0, over :math:`a` and then :math:`b'`, ascending.  The
+    adjoint is the same correlation with the PSF flipped along both axes, for both paddings.  There is no ``pinv``.
+    """
+
+    def __init__(self, psf: Tensor, padding: str = "zeros", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        if padding not in ("zeros", "circular"):
+            raise ValueError(f"padding is 'zeros' or 'circular', got {padding!r}")
+        self.padding = padding
+        k = torch.as_tensor(psf).detach().to(device="cpu", dtype=torch.float32)
+        if k.ndim not in (2, 3, 4) or k.shape[-2] % 2 == 0 or k.shape[-1] % 2 == 0 or max(k.shape[-2:]) > MAX_TAPS or k.numel() == 0:
+            raise ValueError("psf is (kh, kw), (C, kh, kw), (B, 1, kh, kw) or (B, C, kh, kw) with odd kh, kw of at most "
+                             f"{MAX_TAPS}, got shape {tuple(k.shape)}")
+        self.psf = k.reshape((1,) * (4 - k.ndim) + tuple(k.shape)).contiguous()  # (Bp, Cp, kh, kw)
+        self._cache: dict = {}
+
+    def _taps(self, x: Tensor, mode: str) -> Tensor:
+        key = (x.device, x.dtype, mode)
+        k = self._cache.get(key)
+        if k is None:
+            k = self.psf if mode == "apply" else self.psf.flip(2, 3)
+            k = self._cache[key] = k.to(device=x.device, dtype=x.dtype).contiguous()
+        return k
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        c, h, w = in_shape
+        (_, cp, kh, kw) = self.psf.shape
+        if cp not in (1, c):
+            raise ValueError(f"a psf of shape {tuple(self.psf.shape)} is for {cp} channels, got {c}")
+        if self.padding == "circular" and (kh // 2 >= h or kw // 2 >= w):
+            raise ValueError(f"circular padding needs radii ({kh // 2}, {kw // 2}) smaller than the image, got {h} x {w}")
+        return in_shape
+
+    def _check_batch(self, x: Tensor) -> None:
+        if self.psf.shape[0] not in (1, x.shape[0]):
+            raise ValueError(f"a psf of shape {tuple(self.psf.shape)} is for a batch of {self.psf.shape[0]}, got {tuple(x.shape)}")
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        self._check_batch(x)
+        B, c, h, w = x.shape
+        k = self._taps(x, mode)
+        bp, cp, kh, kw = k.shape
+        y = torch.empty_like(x)
+        if x.numel():
+            _launch("az_op_psf_f32", y.data_ptr(), x.data_ptr(), k.data_ptr(), kh, kw, cp if bp > 1 else 0, int(cp > 1), B, c, h, w,
+                    int(self.padding == "circular"))
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        self._check_batch(x)
+        h, w = x.shape[2:]
+        k = self._taps(x, mode)
+        kh, kw = k.shape[2:]
+        rh, rw = kh // 2, kw // 2
+        xp = F.pad(x, (rw, rw, rh, rh), mode="circular") if self.padding == "circular" else F.pad(x, (rw, rw, rh, rh))
+        out = None
+        for a in range(kh):  # (the kernel's order; torch rounds the product where the kernel fuses it)
+            for b in range(kw):
+                term = k[:, :, a, b, None, None] * xp[:, :, a:a + h, b:b + w]
+                out = term if out is None else out + term
+        return out
+
+
+def psf_tile(kh: int, kw: int) -> tuple[int, int]:
+    r"""The output tile (rows, columns) of one workgroup of ``az_op_psf_f32`` for this PSF size."""
+    th, tw = C.c_int32(0), C.c_int32(0)
+    _lib.call("az_op_psf_tile", kh, kw, C.byref(th), C.byref(tw))
+    return th.value, tw.value
+
+
+# ------------------------------------------------------------------------------------------------------------- decimation
+def bicubic_taps(factor: int) -> Tensor:
+    r"""The ``4 factor + 1`` taps of the bicubic low-pass of a down-sampling by ``factor``: the Keys kernel (:math:`a = -0.5`)
+    stretched by ``factor`` and sampled at the integers :math:`-2 f .. 2 f` (the two end taps are 0: the count stays odd),
+    computed in fp64, normalised to sum 1 and then rounded to fp32."""
+    if not (isinstance(factor, int) and 1 <= factor <= MAX_FACTOR):
+        raise ValueError(f"bicubic_taps needs an int factor in 1 .. {MAX_FACTOR}, got {factor}")
+    t = (torch.arange(-2 * factor, 2 * factor + 1, dtype=torch.float64) / factor).abs()
+    a = -0.5
+    k = torch.where(t <= 1, ((a + 2) * t - (a + 3)) * t * t + 1, ((a * t - 5 * a) * t + 8 * a) * t - 4 * a)
+    k = torch.where(t < 2, k, torch.zeros_like(k))
+    return (k / k.sum()).to(torch.float32)
+
+
+def _pair(v, what: str) -> tuple:
+    pair = (v, v) if isinstance(v, int) else tuple(v) if isinstance(v, Sequence) else ()
+    if len(pair) != 2 or not all(isinstance(a, int) for a in pair):
+        raise ValueError(f"{what} is an int or a pair of ints, got {v}")
+    return pair
+
+
+class DecimateOperator(LinearOperator):
+    r"""Creates the decimation :math:`y_{ij} = x_{i f_h + o_h, j f_w + o_w}`: keep every ``factor``-th pixel, starting at
+    ``offset`` (where :class:`DownsampleOperator` averages each window).
+
+    Arguments:
+        factor: The factor, an int or ``(fh, fw)``, each in 1 .. 16.  The input's height and width are multiples of it.
+        offset: The first kept row and column, an int or ``(oh, ow)`` with ``0 <= oh < fh`` and ``0 <= ow < fw``.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    The adjoint stuffs zeros between the values.  :math:`A A^\top = I`, so ``pinv`` is the adjoint.
+
+    Bicubic super-resolution by ``f`` is ``DecimateOperator(f, f // 2) @ BlurOperator(bicubic_taps(f))``: the bicubic low-pass,
+    then every ``f``-th pixel.  The composition computes :math:`f^2` times more blur outputs than it keeps; a fused strided
+    blur is not provided.
+    """
+
+    def __init__(self, factor: int | Sequence[int], offset: int | Sequence[int] = 0, flatten: bool = False,
+                 in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        fh, fw = _pair(factor, "factor")
+        oh, ow = _pair(offset, "offset")
+        if not (1 <= fh <= MAX_FACTOR and 1 <= fw <= MAX_FACTOR):
+            raise ValueError(f"factor is an int or a pair of ints in 1 .. {MAX_FACTOR}, got {factor}")
+        if not (0 <= oh < fh and 0 <= ow < fw):
+            raise ValueError(f"offset is an int or a pair of ints with 0 <= offset < factor, got {offset} for factor {factor}")
+        self.factor, self.offset = (fh, fw), (oh, ow)
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        (c, h, w), (fh, fw) = in_shape, self.factor
+        if h % fh or w % fw:
+            raise ValueError(f"decimation by {self.factor} needs a height and width that are multiples of it, got {h} x {w}")
+        return (c, h // fh, w // fw)
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        return (out_shape[0], out_shape[1] * self.factor[0], out_shape[2] * self.factor[1])
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        (B, c, h, w), (fh, fw), (oh, ow) = x.shape, self.factor, self.offset
+        if mode == "apply":
+            y = x.new_empty(B, c, h // fh, w // fw)
+            if y.numel():
+                _launch("az_op_decimate_f32", y.data_ptr(), x.data_ptr(), B * c, h, w, fh, fw, oh, ow)
+            return y
+        y = x.new_empty(B, c, h * fh, w * fw)
+        if y.numel():
+            _launch("az_op_decimate_adj_f32", y.data_ptr(), x.data_ptr(), B * c, h * fh, w * fw, fh, fw, oh, ow)
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        (B, c, h, w), (fh, fw), (oh, ow) = x.shape, self.factor, self.offset
+        if mode == "apply":
+            return x[:, :, oh::fh, ow::fw]
+        win = F.pad(x[:, :, :, None, :, None], (ow, fw - 1 - ow, 0, 0, oh, fh - 1 - oh))  # (B, c, h, fh, w, fw)
+        return win.reshape(B, c, h * fh, w * fw)
+
+    def pinv(self, y: Tensor) -> Tensor:
+        return self.adjoint(y)
+
+
+# ------------------------------------------------------------------------------------------------------------ channel mix
+class ChannelMixOperator(LinearOperator):
+    r"""Creates the per-pixel channel mix :math:`y_{b o p} = \sum_c M_{o c} \, x_{b c p}` (colourisation: 3 channels to 1).
+
+    Arguments:
+        matrix: The matrix :math:`M`, of shape :math:`(C_{out}, C_{in})`, each at most 16.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    Every output is a chain of fused multiply-adds from 0 with :math:`c` ascending.  The adjoint mixes with :math:`M^\top`;
+    ``pinv`` mixes with :math:`M^+`, ``torch.linalg.pinv`` of the matrix in fp64, computed once on the host.
+    """
+
+    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv_t", "pinv_t": "pinv"}
+
+    def __init__(self, matrix, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        m = torch.as_tensor(matrix).detach().to(device="cpu", dtype=torch.float64)
+        if m.ndim != 2 or not (1 <= m.shape[0] <= MAX_CHANNELS and 1 <= m.shape[1] <= MAX_CHANNELS):
+            raise ValueError(f"matrix is (Cout, Cin) with 1 .. {MAX_CHANNELS} channels each, got shape {tuple(m.shape)}")
+        self.matrix = m.contiguous()
+        self._cache: dict = {}
+
+    @classmethod
+    def grayscale(cls, weights: Sequence[float] = (1 / 3, 1 / 3, 1 / 3), **kwargs) -> ChannelMixOperator:
+        r"""The colourisation operator: one channel, the weighted sum of the input's ``len(weights)`` channels."""
+        return cls(torch.tensor([list(weights)], dtype=torch.float64), **kwargs)
+
+    def _matrix(self, x: Tensor, mode: str) -> Tensor:
+        key = (x.device, x.dtype, mode)
+        m = self._cache.get(key)
+        if m is None:
+            m = self.matrix if mode in ("apply", "adjoint") else torch.linalg.pinv(self.matrix).T  # M or (M^+)^T: (Cout, Cin)
+            m = m.T if mode in ("adjoint", "pinv") else m
+            m = self._cache[key] = m.to(device=x.device, dtype=x.dtype).contiguous()
+        return m
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        if in_shape[0] != self.matrix.shape[1]:
+            raise ValueError(f"a matrix of shape {tuple(self.matrix.shape)} mixes {self.matrix.shape[1]} channels, got {in_shape[0]}")
+        return (self.matrix.shape[0], *in_shape[1:])
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        if out_shape[0] != self.matrix.shape[0]:
+            raise ValueError(f"a matrix of shape {tuple(self.matrix.shape)} gives {self.matrix.shape[0]} channels, got {out_shape[0]}")
+        return (self.matrix.shape[1], *out_shape[1:])
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        B, c, h, w = x.shape
+        m = self._matrix(x, mode)
+        y = x.new_empty(B, m.shape[0], h, w)
+        if y.numel():
+            _launch("az_op_chanmix_f32", y.data_ptr(), x.data_ptr(), m.data_ptr(), B, c, m.shape[0], h * w)
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        m = self._matrix(x, mode)
+        rows = []
+        for o in range(m.shape[0]):
+            acc = None
+            for c in range(m.shape[1]):  # (the kernel's order; torch rounds the product where the kernel fuses it)
+                term = m[o, c] * x[:, c]
+                acc = term if acc is None else acc + term
+            rows.append(acc)
+        return torch.stack(rows, dim=1)
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        return _Apply.apply(g, self, self._TRANSPOSE[mode])
+
+    def pinv(self, y: Tensor) -> Tensor:
+        y = self._image(y, "pinv")
+        self._in_shape_of(tuple(y.shape[1:]))
+        return self._run(y, "pinv")

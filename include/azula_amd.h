@@ -168,7 +168,32 @@ int az_repaint_f32(const AzRepaintArgs* args, az_stream_t stream);
  * stages its tile and halo in LDS, runs the row pass into LDS and the column pass to y; both sums are chains of fused
  * multiply-adds from 0 with the taps ascending.  The adjoint is the same entry with both tap vectors reversed.
  *
- * az_op_blur_tile: the output tile (rows th, columns tw) of a launch with these tap counts (host arithmetic). */
+ * az_op_blur_tile: the output tile (rows th, columns tw) of a launch with these tap counts (host arithmetic).
+ *
+ * az_op_psf_f32: the general (non-separable) correlation y[b, c, i, j] = sum_a sum_b' k[a, b'] x~[b, c, i + a - kh / 2,
+ * j + b' - kw / 2] on (B, C, H, W), k = psf + (b psf_bstride + c psf_cstride) kh kw: the strides count PSFs and 0 shares the PSF
+ * along that axis (one PSF for all planes, one per channel, one per sample, one per plane).  x~ as for az_op_blur_f32; kh, kw
+ * odd, 1 .. 65, strides >= 0 (else AZ_E_SHAPE); psf is a DEVICE pointer, 4-byte aligned, arbitrary values; y must not overlap x
+ * (AZ_E_SHAPE).  Replaces F.conv2d(groups = planes) on a padded copy (motion deblurring: one 61 x 61 kernel per image).  Each
+ * output is ONE chain of kh kw fused multiply-adds from 0, a ascending and then b' ascending.  A workgroup stages its tile and
+ * halo in LDS; a thread carries up to 4 output rows of a column, so one staged value feeds up to 4 chains.  The adjoint is the
+ * same entry on the PSF flipped along both axes, for both paddings.
+ *
+ * az_op_psf_tile: the output tile (rows th, columns tw) of an az_op_psf_f32 launch with this PSF size (host arithmetic).
+ *
+ * az_op_decimate_f32: y[n, i, j] = x[n, i fh + oh, j fw + ow], y being (planes, H / fh, W / fw) -- the slice x[..., oh::fh,
+ * ow::fw].  1 <= fh, fw <= 16, 0 <= oh < fh, 0 <= ow < fw, H % fh == 0 and W % fw == 0 (else AZ_E_SHAPE); y must not overlap x.
+ * A copy: no arithmetic.
+ *
+ * az_op_decimate_adj_f32: dx = g zero-stuffed back onto the (H, W) grid: dx[n, i fh + oh, j fw + ow] = g[n, i, j] and 0
+ * elsewhere; EVERY element of dx is written.  The adjoint of az_op_decimate_f32 and, as A A^T = I, its pseudo-inverse; replaces
+ * zeros() and a strided assignment.  The same constraints.
+ *
+ * az_op_chanmix_f32: y[b, o, p] = sum_c M[o Cin + c] x[b, c, p] on x (B, Cin, HW), y (B, Cout, HW) -- a per-pixel channel mix
+ * (colourisation: 3 -> 1), what einsum("oc,bcp->bop") computes.  M is a DEVICE pointer, 4-byte aligned; 1 <= Cin, Cout <= 16
+ * (else AZ_E_SHAPE); y must not overlap x.  Each output is a chain of fused multiply-adds from 0 with c ascending; 16 bytes
+ * along p at a time where HW % 4 == 0, one pixel per thread otherwise.  The adjoint is the same entry with M^T (Cin and Cout
+ * exchanged), the pseudo-inverse the same entry with M^+. */
 int az_op_mul_f32(float* y, const float* x, const float* m, int64_t n, int64_t m_n, az_stream_t stream);
 int az_op_avgpool_f32(float* y, const float* x, int64_t planes, int64_t H, int64_t W, int32_t fh, int32_t fw,
                       az_stream_t stream);
@@ -177,6 +202,15 @@ int az_op_avgpool_adj_f32(float* dx, const float* g, int64_t planes, int64_t H, 
 int az_op_blur_f32(float* y, const float* x, const float* taps_h, int32_t nh, const float* taps_w, int32_t nw, int64_t planes,
                    int64_t H, int64_t W, int32_t circular, az_stream_t stream);
 int az_op_blur_tile(int32_t nh, int32_t nw, int32_t* th, int32_t* tw);
+int az_op_psf_f32(float* y, const float* x, const float* psf, int32_t kh, int32_t kw, int64_t psf_bstride, int64_t psf_cstride,
+                  int64_t B, int64_t C, int64_t H, int64_t W, int32_t circular, az_stream_t stream);
+int az_op_psf_tile(int32_t kh, int32_t kw, int32_t* th, int32_t* tw);
+int az_op_decimate_f32(float* y, const float* x, int64_t planes, int64_t H, int64_t W, int32_t fh, int32_t fw, int32_t oh,
+                       int32_t ow, az_stream_t stream);
+int az_op_decimate_adj_f32(float* dx, const float* g, int64_t planes, int64_t H, int64_t W, int32_t fh, int32_t fw, int32_t oh,
+                           int32_t ow, az_stream_t stream);
+int az_op_chanmix_f32(float* y, const float* x, const float* M, int64_t B, int32_t Cin, int32_t Cout, int64_t HW,
+                      az_stream_t stream);
 
 /* ---- Twisted diffusion sampler: resample and proposal -------------------------------------------------------------
  * The non-network part of TDSSampler.step (azula/guidance/tds.py:70-102) for K particles of N elements each.

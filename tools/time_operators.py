@@ -1,8 +1,10 @@
-r"""Time ``az_op_blur_f32`` (through ``BlurOperator``) against torch-op forms of the same blur on the same device tensor.
+r"""Time ``az_op_blur_f32`` (through ``BlurOperator``) or ``az_op_psf_f32`` (through ``PSFOperator``) against torch-op forms of the
+same map on the same device tensor.
 
-    python tools/time_operators.py [taps] [B] [C] [H] [W]
+    python tools/time_operators.py [taps] [B] [C] [H] [W]          # blur
+    python tools/time_operators.py psf [size] [B] [C] [H] [W]      # general PSF
 
-Default: the 61-tap Gaussian of DPS's deblurring setup on 4 x 3 x 256 x 256.  HIP events around back-to-back calls after a
+Blur, default: the 61-tap Gaussian of DPS's deblurring setup on 4 x 3 x 256 x 256.  HIP events around back-to-back calls after a
 warm-up, the forms alternating over ``ROUNDS`` rounds; prints the median time per call of
 
 * the operator (one launch of the kernel),
@@ -10,7 +12,18 @@ warm-up, the forms alternating over ``ROUNDS`` rounds; prints the median time pe
 * the oracle of the tests (``tests/operator_oracle.py``: the two-dimensional shift-and-add, ``taps^2`` slices),
 
 the kernel's share of the HBM roofline (one fp32 read and one write per element over the measured copy bandwidth of the MI355X,
-6.29 TB/s) and one JSON line.  The figures in DESIGN.md section 9c come from this script.
+6.29 TB/s) and one JSON line.
+
+PSF, default: ``motion_psf(size / 2, 30, size)`` with size 61 on 4 x 3 x 256 x 256, once shared by all planes and once with one
+PSF per sample (angles 30 + 15 b).  The same method; the forms are
+
+* the operator (one launch),
+* ``F.conv2d(groups = planes)`` on the same device tensor -- what a user writes today, and
+* the package's torch path (``size^2`` slices; fewer repetitions: it takes tens of milliseconds),
+
+and the yardstick is the vector-fp32 FMA peak of the MI355X, 157.3 TFLOP/s: ``2 size^2 B C H W`` FLOP per call.
+
+The figures in DESIGN.md section 9c come from this script.
 """
 
 from __future__ import annotations
@@ -25,11 +38,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
 
 import operator_oracle as oo  # noqa: E402
-from azula_amd.guidance import BlurOperator, gaussian_taps  # noqa: E402
+from azula_amd.guidance import BlurOperator, PSFOperator, gaussian_taps, motion_psf  # noqa: E402
 
 HBM = 6.29e12
+FP32_PEAK = 157.3e12  # vector fp32, FLOP/s
 ROUNDS, WARMUP = 7, 3
 
 
@@ -43,19 +58,8 @@ def timed(fn, reps: int) -> float:
     return a.elapsed_time(b) * 1e-3 / reps
 
 
-def main() -> None:
-    n, B, Cc, H, W = (int(v) for v in (sys.argv[1:6] + ["61", "4", "3", "256", "256"][len(sys.argv) - 1:]))
-    if not torch.cuda.is_available():
-        raise SystemExit("time_operators.py measures on the GPU: no device visible")
-    torch.manual_seed(0)
-    x = torch.randn(B, Cc, H, W, device="cuda")
-    taps = gaussian_taps(n / 6.0, n)
-    A = BlurOperator(taps)
-    td = taps.cuda()
-    forms = {"kernel": (lambda: A(x), 200), "torch_path": (lambda: A._torch(x, "apply"), 5),
-             "oracle": (lambda: oo.blur(x, td, td, False), 2)}
-    ref = oo.blur(x.double(), td.double(), td.double(), False)
-    err = {k: float((fn().double() - ref).abs().max()) for k, (fn, _) in forms.items()}
+def measure(forms: dict) -> dict:
+    r"""name -> the per-call times of ``ROUNDS`` rounds, the forms alternating, after ``WARMUP`` calls of each."""
     for fn, _ in forms.values():
         for _ in range(WARMUP):
             fn()
@@ -64,14 +68,74 @@ def main() -> None:
     for _ in range(ROUNDS):
         for k, (fn, reps) in forms.items():
             times[k].append(timed(fn, reps))
+    return times
+
+
+def report(forms: dict, times: dict, err: dict) -> dict:
     med = {k: statistics.median(v) for k, v in times.items()}
-    floor = 2 * x.numel() * 4 / HBM
     for k in forms:
         print(f"{k}: {med[k] * 1e6:.1f} us per call (min {min(times[k]) * 1e6:.1f}, max {max(times[k]) * 1e6:.1f}), "
               f"max|d| to fp64 {err[k]:.2e}")
+    return med
+
+
+def blur(args: list[str]) -> None:
+    n, B, Cc, H, W = (int(v) for v in (args + ["61", "4", "3", "256", "256"][len(args):]))
+    x = torch.randn(B, Cc, H, W, device="cuda")
+    taps = gaussian_taps(n / 6.0, n)
+    A = BlurOperator(taps)
+    td = taps.cuda()
+    forms = {"kernel": (lambda: A(x), 200), "torch_path": (lambda: A._torch(x, "apply"), 5),
+             "oracle": (lambda: oo.blur(x, td, td, False), 2)}
+    ref = oo.blur(x.double(), td.double(), td.double(), False)
+    err = {k: float((fn().double() - ref).abs().max()) for k, (fn, _) in forms.items()}
+    times = measure(forms)
+    med = report(forms, times, err)
+    floor = 2 * x.numel() * 4 / HBM
     print(f"HBM floor {floor * 1e6:.2f} us -> the kernel runs at {floor / med['kernel']:.1%} of the HBM roofline")
     print(json.dumps({"taps": n, "shape": [B, Cc, H, W], **{f"{k}_us": med[k] * 1e6 for k in forms}, "hbm_floor_us": floor * 1e6,
                       "hbm_fraction": floor / med["kernel"]}))
+
+
+def psf(args: list[str]) -> None:
+    n, B, Cc, H, W = (int(v) for v in (args + ["61", "4", "3", "256", "256"][len(args):]))
+    x = torch.randn(B, Cc, H, W, device="cuda")
+    flop = 2.0 * n * n * x.numel()
+    for what in ("shared", "per_sample"):
+        k = motion_psf(n / 2, 30.0, n) if what == "shared" else \
+            torch.stack([motion_psf(n / 2, 30.0 + 15.0 * b, n) for b in range(B)])[:, None]
+        A = PSFOperator(k)
+        # conv2d correlates, as the operator does: one group per plane, the plane's PSF as its only filter
+        weight = k.expand(B, Cc, n, n).reshape(B * Cc, 1, n, n).contiguous().cuda()
+        conv = lambda: F.conv2d(x.reshape(1, B * Cc, H, W), weight, padding=n // 2, groups=B * Cc).reshape(B, Cc, H, W)  # noqa: E731, B023
+        forms = {"kernel": (lambda: A(x), 20), "conv2d_groups": (conv, 5), "torch_path": (lambda: A._torch(x, "apply"), 1)}  # noqa: B023
+        ref = A._torch(x.double(), "apply")
+        try:
+            conv()
+        except RuntimeError as e:  # (the convolution library may have no kernel for a filter this large)
+            print(f"conv2d_groups is not timed: {str(e).splitlines()[0]}")
+            del forms["conv2d_groups"]
+        err = {k_: float((fn().double() - ref).abs().max()) for k_, (fn, _) in forms.items()}
+        times = measure(forms)
+        print(f"-- {n} x {n} motion PSF, {what}, on {B} x {Cc} x {H} x {W}")
+        med = report(forms, times, err)
+        peak = flop / FP32_PEAK
+        print(f"{flop / 1e9:.2f} GFLOP: {peak * 1e6:.1f} us at the vector fp32 peak -> the kernel runs at "
+              f"{peak / med['kernel']:.1%} of it ({flop / med['kernel'] / 1e12:.1f} TFLOP/s)")
+        print(json.dumps({"psf": n, "form": what, "shape": [B, Cc, H, W], **{f"{k_}_us": med[k_] * 1e6 for k_ in forms},
+                          **{f"{k_}_min_us": min(times[k_]) * 1e6 for k_ in forms},
+                          **{f"{k_}_max_us": max(times[k_]) * 1e6 for k_ in forms}, "fp32_peak_us": peak * 1e6,
+                          "fp32_peak_fraction": peak / med["kernel"]}))
+
+
+def main() -> None:
+    if not torch.cuda.is_available():
+        raise SystemExit("time_operators.py measures on the GPU: no device visible")
+    torch.manual_seed(0)
+    if sys.argv[1:2] == ["psf"]:
+        psf(sys.argv[2:7])
+    else:
+        blur(sys.argv[1:6])
 
 
 if __name__ == "__main__":
