@@ -1,11 +1,11 @@
 r"""Measurement operators for the guidance methods: pixel mask, average-pool downsampling, separable blur, general 2-D PSF
-(motion blur), decimation (bicubic super-resolution) and per-pixel channel mix (colourisation), with exact adjoints and (where
-one exists) the pseudo-inverse.
+(motion blur), decimation (bicubic super-resolution), per-pixel channel mix (colourisation) and the 2-D Fourier transform
+(k-space undersampling: accelerated MRI), with exact adjoints and (where one exists) the pseudo-inverse.
 
 The guidance classes take the operator :math:`A` of :math:`y = A x + n` as a callable and differentiate it with
 ``torch.autograd.grad`` (DPS, TMPD, MMPS, JFPS, DiffPIR) and ``torch.func.jvp`` (MMPS, JFPS).  The operators below are such
-callables whose three maps are kernels of ``csrc/operators.hip``: no autograd graph of torch ops, no atomics (two runs give the
-same bits) and a fixed launch sequence.  The project's own extension: the reference has no operator library.
+callables whose three maps are kernels of ``csrc/operators.hip`` and ``csrc/fft.hip``: no autograd graph of torch ops, no atomics
+(two runs give the same bits) and a fixed launch sequence.  The project's own extension: the reference has no operator library.
 
     A = DownsampleOperator(2, flatten=True) @ BlurOperator.gaussian(1.0, 5)
     DiffPIRDenoiser(denoiser, y, A, var_y)              # y: (B, D)
@@ -13,6 +13,7 @@ same bits) and a fixed launch sequence.  The project's own extension: the refere
     PSFOperator(motion_psf(31.0, 30.0, 61), flatten=True)                        # motion deblurring
     DecimateOperator(4, 2, flatten=True) @ BlurOperator(bicubic_taps(4))         # bicubic super-resolution x4
     ChannelMixOperator.grayscale(flatten=True)                                   # colourisation
+    MRIOperator(cartesian_mask(256, 256, 4), flatten=True)                       # 4x accelerated single-coil MRI
 
 Two paths, as ``RePaintSampler`` has them:
 
@@ -38,10 +39,11 @@ from .. import _lib
 from .repaint import _aligned, _broadcasts_to
 
 __all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps", "PSFOperator", "motion_psf",
-           "DecimateOperator", "bicubic_taps", "ChannelMixOperator"]
+           "DecimateOperator", "bicubic_taps", "ChannelMixOperator", "FourierOperator", "MRIOperator", "cartesian_mask"]
 
 MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_decimate_f32 and of az_op_blur_f32 / az_op_psf_f32)
 MAX_CHANNELS = 16  # (the limit of az_op_chanmix_f32)
+MAX_FFT = 1024  # (AZ_OP_FFT2_MAX: the largest height or width of az_op_fft2_f32)
 
 
 def _launch(name: str, *args) -> None:
@@ -688,6 +690,214 @@ class ChannelMixOperator(LinearOperator):
         return _Apply.apply(g, self, self._TRANSPOSE[mode])
 
     def pinv(self, y: Tensor) -> Tensor:
+        y = self._image(y, "pinv")
+        self._in_shape_of(tuple(y.shape[1:]))
+        return self._run(y, "pinv")
+
+
+# --------------------------------------------------------------------------------------------------------------- Fourier
+def _fft_kernel_size(n: int) -> bool:
+    return 1 <= n <= MAX_FFT and n & (n - 1) == 0
+
+
+class FourierOperator(LinearOperator):
+    r"""Creates the 2-D discrete Fourier transform of a real image in split-complex form: a :math:`(B, C, H, W)` input gives a
+    :math:`(B, 2 C, H, W)` observation whose channels :math:`[0, C)` are :math:`\Re F x` and :math:`[C, 2 C)` are
+    :math:`\Im F x`, with :math:`(F x)_{kl} = s \sum_{mn} x_{mn} e^{-2 \pi i (k m / H + l n / W)}`.  The DC term is at
+    :math:`[0, 0]`: there is no shift.  Everything stays real and 4-D, so :class:`MaskOperator`, ``flatten`` and compositions
+    apply to the observation as to any other.
+
+    Arguments:
+        norm: As in ``torch.fft``: ``"ortho"`` (:math:`s = 1 / \sqrt{H W}`, :math:`A^\top A = I` and ``pinv`` is the
+            adjoint), ``"backward"`` (:math:`s = 1`, ``pinv`` is the adjoint divided by :math:`H W`) or ``"forward"``
+            (:math:`s = 1 / (H W)`, ``pinv`` is :math:`H W` times the adjoint).
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    The adjoint maps :math:`(B, 2 C, H, W)` to :math:`(B, C, H, W)` as :math:`s \, \Re F^H (z_{re} + i z_{im})`: one inverse
+    transform whose imaginary part is never written.
+
+    Every fp32 device tensor takes ``az_op_fft2_f32`` (made contiguous and aligned first), whose heights and widths are powers
+    of two up to 1024; any other size of such a tensor raises ``NotImplementedError`` -- there is no vendor-FFT fallback on that
+    path.  Host and fp64 tensors run ``torch.fft`` in their own dtype at any size; half precision is not provided.
+
+    Out of scope: non-power-of-two sizes on the device, multi-coil sensitivity maps, ``fftshift``-ed layouts, nonlinear phase
+    retrieval, 3-D transforms, and an FFT-based ``pinv`` for the circular :class:`BlurOperator`.
+    """
+
+    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv_t", "pinv_t": "pinv"}
+
+    def __init__(self, norm: str = "ortho", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        if norm not in ("ortho", "backward", "forward"):
+            raise ValueError(f"norm is 'ortho', 'backward' or 'forward', got {norm!r}")
+        self.norm = norm
+
+    def _scale(self, hw: int, mode: str) -> float:
+        r"""The factor of the map ``mode``; "pinv_t" is the transpose of "pinv": the apply map at the pinv's scale."""
+        if self.norm == "ortho":
+            return 1.0 / math.sqrt(hw)
+        if mode in ("apply", "adjoint"):
+            return 1.0 if self.norm == "backward" else 1.0 / hw
+        return 1.0 / hw if self.norm == "backward" else 1.0
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        return (2 * in_shape[0], *in_shape[1:])
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        if out_shape[0] % 2:
+            raise ValueError(f"a split-complex observation has an even channel count (re, then im), got {out_shape[0]}")
+        return (out_shape[0] // 2, *out_shape[1:])
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        B, c, h, w = x.shape
+        scale = self._scale(h * w, mode)
+        if mode in ("apply", "pinv_t"):  # real -> split complex
+            n = c * h * w
+            if n % 4 == 0:  # (both halves of y start 16-byte aligned)
+                y = _aligned(x.new_empty(B, 2 * c, h, w), 16)
+                if y.numel():
+                    _launch("az_op_fft2_f32", y.data_ptr(), y.data_ptr() + 4 * n, 2 * n, x.data_ptr(), None, n, None, B, c, h, w, 0,
+                            scale)
+                return y
+            re, im = _aligned(torch.empty_like(x), 16), _aligned(torch.empty_like(x), 16)
+            if x.numel():
+                _launch("az_op_fft2_f32", re.data_ptr(), im.data_ptr(), n, x.data_ptr(), None, n, None, B, c, h, w, 0, scale)
+            return torch.cat([re, im], dim=1)
+        c //= 2  # split complex -> real: the inverse transform's real part
+        n = c * h * w
+        y = _aligned(x.new_empty(B, c, h, w), 16)
+        if not y.numel():
+            return y
+        floats = C.c_int64(0)
+        _lib.call("az_op_fft2_work", B, c, h, w, C.byref(floats))
+        work = _aligned(x.new_empty(floats.value), 16) if floats.value else None
+        if n % 4 == 0:
+            re_ptr, im_ptr, stride = x.data_ptr(), x.data_ptr() + 4 * n, 2 * n
+        else:
+            re, im = _aligned(x[:, :c].contiguous(), 16), _aligned(x[:, c:].contiguous(), 16)
+            re_ptr, im_ptr, stride = re.data_ptr(), im.data_ptr(), n
+        _launch("az_op_fft2_f32", y.data_ptr(), None, n, re_ptr, im_ptr, stride, None if work is None else work.data_ptr(), B, c, h,
+                w, 1, scale)
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        if x.dtype not in (torch.float32, torch.float64):
+            raise NotImplementedError(f"FourierOperator runs in fp32 and fp64, got {x.dtype}")
+        h, w = x.shape[2:]
+        scale = self._scale(h * w, mode)
+        if mode in ("apply", "pinv_t"):
+            f = torch.fft.fft2(x)
+            return torch.cat([f.real, f.imag], dim=1) * scale
+        c = x.shape[1] // 2
+        return torch.fft.ifft2(torch.complex(x[:, :c], x[:, c:]), norm="forward").real * scale  # ("forward": unscaled inverse)
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        return _Apply.apply(g, self, self._TRANSPOSE[mode])
+
+    def _run(self, x: Tensor, mode: str) -> Tensor:
+        if _use_kernels(x) or (x.is_cuda and x.dtype == torch.float32):  # (a strided view too: the Function makes it contiguous)
+            h, w = x.shape[2:]
+            if not (_fft_kernel_size(h) and _fft_kernel_size(w)):
+                raise NotImplementedError(f"FourierOperator on an fp32 device tensor needs a height and width that are powers of "
+                                          f"two of at most {MAX_FFT}, got {h} x {w}; host and fp64 tensors take any size")
+            return _Apply.apply(x, self, mode)
+        return self._torch(x, mode)
+
+    def pinv(self, y: Tensor) -> Tensor:
+        y = self._image(y, "pinv")
+        self._in_shape_of(tuple(y.shape[1:]))
+        return self._run(y, "pinv")
+
+
+def cartesian_mask(H: int, W: int, acceleration: float, center_fraction: float = 0.08, seed: int = 0) -> Tensor:
+    r"""A :math:`(H, W)` 0/1 fp32 mask of whole columns in DFT order (column :math:`l` is the frequency :math:`l` for
+    :math:`l \le W / 2` and :math:`l - W` above): Cartesian undersampling of k-space by about ``acceleration``.
+
+    The band :math:`|f| \le c`, :math:`c = \lfloor n_c / 2 \rfloor` with :math:`n_c` = ``center_fraction * W`` rounded half
+    up, is always kept: :math:`\min(W, 2 c + 1)` columns that hold the :math:`n_c` lowest frequencies.  The others are drawn in
+    pairs :math:`\pm f`, :math:`c < f < W / 2` (the Nyquist column has no partner and is never drawn), without replacement by a
+    CPU ``torch.Generator`` seeded with ``seed``: the mask is symmetric under :math:`l \to -l \bmod W` and the same on every
+    machine.  With :math:`P = \max(0, \lfloor (W - 1) / 2 \rfloor - c)` such pairs and :math:`n` = ``W / acceleration`` rounded
+    half up, the number of kept columns is :math:`\min(W, 2 c + 1) + 2 \min(P, \max(0, \lfloor (n - (2 c + 1)) / 2 \rfloor))`
+    (:func:`cartesian_columns`)."""
+    cols = cartesian_columns(W, acceleration, center_fraction)  # (validates)
+    if H < 1:
+        raise ValueError(f"cartesian_mask needs H >= 1, got {H}")
+    c = int(math.floor(center_fraction * W + 0.5)) // 2
+    band = min(W, 2 * c + 1)
+    row = torch.zeros(W, dtype=torch.float32)
+    f = torch.arange(W)
+    row[torch.minimum(f, W - f) <= c] = 1.0
+    pairs = torch.arange(c + 1, max(c + 1, (W - 1) // 2 + 1))
+    order = torch.randperm(pairs.numel(), generator=torch.Generator().manual_seed(seed))
+    chosen = pairs[order[:(cols - band) // 2]]
+    row[chosen] = 1.0
+    row[W - chosen] = 1.0
+    return row.expand(H, W).contiguous()
+
+
+def cartesian_columns(W: int, acceleration: float, center_fraction: float = 0.08) -> int:
+    r"""The number of columns :func:`cartesian_mask` keeps."""
+    if W < 1 or acceleration < 1 or not 0 <= center_fraction <= 1:
+        raise ValueError(f"cartesian_mask needs W >= 1, acceleration >= 1 and 0 <= center_fraction <= 1, got W {W}, acceleration "
+                         f"{acceleration}, center_fraction {center_fraction}")
+    c = int(math.floor(center_fraction * W + 0.5)) // 2
+    n = int(math.floor(W / acceleration + 0.5))
+    pairs = max(0, (W - 1) // 2 - c)
+    return min(W, 2 * c + 1) + 2 * min(pairs, max(0, (n - (2 * c + 1)) // 2))
+
+
+class MRIOperator(LinearOperator):
+    r"""Creates single-coil Cartesian k-space undersampling :math:`A = M F`: ``MaskOperator(mask) @ FourierOperator(norm)`` as
+    one operator, so that it has a pseudo-inverse.  A :math:`(B, C, H, W)` input gives a :math:`(B, 2 C, H, W)` observation.
+
+    Arguments:
+        mask: The sampling mask :math:`M` in DFT order (DC at :math:`[0, 0]`): :math:`(H, W)`, :math:`(1, H, W)` or anything
+            that broadcasts to :math:`(B, 2 C, H, W)` with the same values on the real and the imaginary half.  Bool, 0/1 or
+            weights.  See :func:`cartesian_mask`.
+        norm: See :class:`FourierOperator`.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    The adjoint is :math:`F^\top M`.  ``pinv`` is :math:`F^+ M^+` (:math:`F^\top M^+` for ``"ortho"``), the zero-filled
+    reconstruction.  It is the Moore--Penrose inverse exactly when the mask is symmetric under :math:`k \to -k \bmod (H, W)`:
+    :math:`F F^+` projects onto the Hermitian-symmetric spectra and commutes with :math:`M` only then.  The symmetry is checked
+    once, at construction; ``pinv`` of an unsymmetric mask raises ``NotImplementedError``.
+
+    Out of scope: see :class:`FourierOperator`.
+    """
+
+    def __init__(self, mask: Tensor, norm: str = "ortho", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        self.fourier = FourierOperator(norm)
+        self.sampling = MaskOperator(mask)
+        if mask.ndim < 2:
+            raise ValueError(f"mask is (H, W) or broadcasts to (B, 2 C, H, W), got shape {tuple(mask.shape)}")
+        if mask.ndim >= 3 and mask.shape[-3] > 1:
+            half = mask.shape[-3] // 2
+            if mask.shape[-3] % 2 or not torch.equal(mask[..., :half, :, :], mask[..., half:, :, :]):
+                raise ValueError("a mask with a channel axis has the same values on the real and the imaginary half of the 2 C "
+                                 f"channels, got shape {tuple(mask.shape)}")
+        self.symmetric = bool(torch.equal(mask, mask.flip(-2, -1).roll((1, 1), (-2, -1))))
+
+    @property
+    def mask(self) -> Tensor:
+        return self.sampling.mask
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        return self.sampling._out_shape(self.fourier._out_shape(in_shape))
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        return self.fourier._in_shape_of(self.sampling._out_shape(out_shape))
+
+    def _run(self, x: Tensor, mode: str) -> Tensor:
+        if mode == "apply":
+            return self.sampling._run(self.fourier._run(x, "apply"), "apply")
+        return self.fourier._run(self.sampling._run(x, "pinv" if mode == "pinv" else "apply"), mode)
+
+    def pinv(self, y: Tensor) -> Tensor:
+        if not self.symmetric:
+            raise NotImplementedError("MRIOperator.pinv is the Moore-Penrose inverse only for a mask that is symmetric under "
+                                      "k -> -k mod (H, W): F F^+ does not commute with this one")
         y = self._image(y, "pinv")
         self._in_shape_of(tuple(y.shape[1:]))
         return self._run(y, "pinv")

@@ -212,6 +212,27 @@ int az_op_decimate_adj_f32(float* dx, const float* g, int64_t planes, int64_t H,
 int az_op_chanmix_f32(float* y, const float* x, const float* M, int64_t B, int32_t Cin, int32_t Cout, int64_t HW,
                       az_stream_t stream);
 
+/* ---- Batched 2-D DFT of the Fourier-domain operators (csrc/fft.hip; FourierOperator, MRIOperator) -------------------
+ * az_op_fft2_f32: dst[k, l] = scale * sum_{m, n} src[m, n] exp(-+ 2 pi i (k m / H + l n / W)) on every plane, "-" for inverse = 0
+ * and "+" for inverse = 1, the DC term at [0, 0].  SPLIT-complex fp32: the real and the imaginary parts are separate planes, and
+ * plane (b, c), b < B, c < C, of a tensor starts at base + b * bstride + c * H * W floats, so the two halves of a (B, 2 C, H, W)
+ * tensor are a destination or a source (bstride = 2 C H W).  src_im == NULL: real input (4 bytes read per element); dst_im ==
+ * NULL: only the real part is written.  H and W are powers of two in 1 .. AZ_OP_FFT2_MAX, inverse is 0 or 1, B, C > 0, and for
+ * B > 1 the strides are at least C H W (else AZ_E_SHAPE); dst_re and src_re are required, and `work` where az_op_fft2_work says
+ * so and dst_im is NULL (else AZ_E_NULL); every base is 16-byte aligned (else AZ_E_ALIGN); no destination, source or `work` plane
+ * may share a float with another (AZ_E_SHAPE): never in place.  Planes of at most 8192 points run whole in LDS in one launch
+ * (12 bytes per element real -> complex); larger ones in two, rows and then tiles of 8192 / H columns, with the row result in
+ * dst_re and in dst_im (or `work`): 28 bytes per element.  Stockham radix-4 stages (one radix-2 stage for an odd log2), twiddles
+ * from sincospif of the exact fraction: multiples of a quarter turn are exactly 0 / +-1, so H, W <= 4 are exact on integers.  No
+ * atomics, a fixed order of operations: a plane's result does not depend on the other planes of the launch.
+ *
+ * az_op_fft2_work: the floats of `work` such a call may need (0: none; else B C H W, dense).  Host arithmetic. */
+#define AZ_OP_FFT2_MAX 1024
+int az_op_fft2_f32(float* dst_re, float* dst_im, int64_t dst_bstride, const float* src_re, const float* src_im,
+                   int64_t src_bstride, float* work, int64_t B, int64_t C, int32_t H, int32_t W, int32_t inverse, float scale,
+                   az_stream_t stream);
+int az_op_fft2_work(int64_t B, int64_t C, int32_t H, int32_t W, int64_t* floats);
+
 /* ---- Twisted diffusion sampler: resample and proposal -------------------------------------------------------------
  * The non-network part of TDSSampler.step (azula/guidance/tds.py:70-102) for K particles of N elements each.
  *

@@ -1,8 +1,9 @@
-r"""Time ``az_op_blur_f32`` (through ``BlurOperator``) or ``az_op_psf_f32`` (through ``PSFOperator``) against torch-op forms of the
-same map on the same device tensor.
+r"""Time ``az_op_blur_f32`` (through ``BlurOperator``), ``az_op_psf_f32`` (through ``PSFOperator``) or ``az_op_fft2_f32`` (through
+``FourierOperator``) against torch-op forms of the same map on the same device tensor.
 
     python tools/time_operators.py [taps] [B] [C] [H] [W]          # blur
     python tools/time_operators.py psf [size] [B] [C] [H] [W]      # general PSF
+    python tools/time_operators.py fft [B] [C] [H] [W]             # 2-D Fourier transform
 
 Blur, default: the 61-tap Gaussian of DPS's deblurring setup on 4 x 3 x 256 x 256.  HIP events around back-to-back calls after a
 warm-up, the forms alternating over ``ROUNDS`` rounds; prints the median time per call of
@@ -23,11 +24,18 @@ PSF per sample (angles 30 + 15 b).  The same method; the forms are
 
 and the yardstick is the vector-fp32 FMA peak of the MI355X, 157.3 TFLOP/s: ``2 size^2 B C H W`` FLOP per call.
 
-The figures in DESIGN.md section 9c come from this script.
+FFT, default: ``FourierOperator()`` apply (real -> split complex) and adjoint (split complex -> real) on 4 x 3 x 256 x 256; run it
+on 16 4 64 64 for the whole-plane form.  The same method; the forms are the operator, the C entry alone on buffers made once (the
+difference is what the operator adds: the autograd Function and the allocations) and the ``torch.fft`` lambda a user writes today
+(the vendor library, with the rearrangement to the split layout).  The yardstick is the bytes model of ``csrc/fft.hip`` at the
+same 6.29 TB/s: 12 bytes per element where a plane runs whole in LDS (at most 8192 points), else 28.
+
+The figures in DESIGN.md sections 9c and 9d come from this script.
 """
 
 from __future__ import annotations
 
+import ctypes as C
 import json
 import os
 import statistics
@@ -41,7 +49,8 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 import operator_oracle as oo  # noqa: E402
-from azula_amd.guidance import BlurOperator, PSFOperator, gaussian_taps, motion_psf  # noqa: E402
+from azula_amd import _lib  # noqa: E402
+from azula_amd.guidance import BlurOperator, FourierOperator, PSFOperator, gaussian_taps, motion_psf  # noqa: E402
 
 HBM = 6.29e12
 FP32_PEAK = 157.3e12  # vector fp32, FLOP/s
@@ -128,12 +137,55 @@ def psf(args: list[str]) -> None:
                           "fp32_peak_fraction": peak / med["kernel"]}))
 
 
+def fft(args: list[str]) -> None:
+    B, Cc, H, W = (int(v) for v in (args + ["4", "3", "256", "256"][len(args):]))
+    x, z = torch.randn(B, Cc, H, W, device="cuda"), torch.randn(B, 2 * Cc, H, W, device="cuda")
+    A = FourierOperator()
+
+    def lam(v):
+        f = torch.fft.fft2(v, norm="ortho")
+        return torch.cat([f.real, f.imag], dim=1)
+
+    def lam_t(v):
+        return torch.fft.ifft2(torch.complex(v[:, :Cc], v[:, Cc:]), norm="ortho").real
+
+    # the C entry alone on buffers made once: what the operator adds (the autograd Function, the allocation of the output and of
+    # `work`) is the difference
+    n, y, xo = Cc * H * W, torch.empty_like(z), torch.empty_like(x)
+    floats = C.c_int64(0)
+    _lib.call("az_op_fft2_work", B, Cc, H, W, C.byref(floats))
+    work = torch.empty(max(floats.value, 4), device="cuda")
+    scale, stream = 1.0 / (H * W) ** 0.5, _lib.stream_ptr()
+    entry = lambda: _lib.call("az_op_fft2_f32", y.data_ptr(), y.data_ptr() + 4 * n, 2 * n, x.data_ptr(), None, n, None, B, Cc, H,  # noqa: E731
+                              W, 0, scale, stream)
+    entry_t = lambda: _lib.call("az_op_fft2_f32", xo.data_ptr(), None, n, z.data_ptr(), z.data_ptr() + 4 * n, 2 * n,  # noqa: E731
+                                work.data_ptr(), B, Cc, H, W, 1, scale, stream)
+    forms = {"apply": (lambda: A(x), 200), "adjoint": (lambda: A.adjoint(z), 200), "entry_apply": (lambda: (entry(), y)[1], 200),
+             "entry_adjoint": (lambda: (entry_t(), xo)[1], 200), "torch_fft_apply": (lambda: lam(x), 200),
+             "torch_fft_adjoint": (lambda: lam_t(z), 200)}
+    ref, ref_t = lam(x.double()), lam_t(z.double())
+    err = {k: float((fn().double() - (ref_t if "adjoint" in k else ref)).abs().max()) for k, (fn, _) in forms.items()}
+    times = measure(forms)
+    med = report(forms, times, err)
+    per_element = 12 if H * W <= 8192 else 28
+    floor = per_element * x.numel() / HBM
+    print(f"{per_element} B per element: {floor * 1e6:.2f} us at {HBM / 1e12:.2f} TB/s -> apply runs at {floor / med['apply']:.1%} "
+          f"of the model, adjoint at {floor / med['adjoint']:.1%}; the entry alone at {floor / med['entry_apply']:.1%} and "
+          f"{floor / med['entry_adjoint']:.1%}")
+    print(json.dumps({"fft": [B, Cc, H, W], **{f"{k}_us": med[k] * 1e6 for k in forms},
+                      **{f"{k}_min_us": min(times[k]) * 1e6 for k in forms}, "bytes_per_element": per_element,
+                      "model_us": floor * 1e6, "model_fraction_apply": floor / med["apply"],
+                      "model_fraction_adjoint": floor / med["adjoint"]}))
+
+
 def main() -> None:
     if not torch.cuda.is_available():
         raise SystemExit("time_operators.py measures on the GPU: no device visible")
     torch.manual_seed(0)
     if sys.argv[1:2] == ["psf"]:
         psf(sys.argv[2:7])
+    elif sys.argv[1:2] == ["fft"]:
+        fft(sys.argv[2:6])
     else:
         blur(sys.argv[1:6])
 
