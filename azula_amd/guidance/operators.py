@@ -1,10 +1,11 @@
 r"""Measurement operators for the guidance methods: pixel mask, average-pool downsampling, separable blur, general 2-D PSF
-(motion blur), decimation (bicubic super-resolution), per-pixel channel mix (colourisation) and the 2-D Fourier transform
-(k-space undersampling: accelerated MRI), with exact adjoints and (where one exists) the pseudo-inverse.
+(motion blur), decimation (bicubic super-resolution), per-pixel channel mix (colourisation), the 2-D Fourier transform (k-space
+undersampling: accelerated MRI) and the parallel-beam Radon transform (sparse-view and limited-angle CT), with exact adjoints and
+(where one exists) the pseudo-inverse.
 
 The guidance classes take the operator :math:`A` of :math:`y = A x + n` as a callable and differentiate it with
 ``torch.autograd.grad`` (DPS, TMPD, MMPS, JFPS, DiffPIR) and ``torch.func.jvp`` (MMPS, JFPS).  The operators below are such
-callables whose three maps are kernels of ``csrc/operators.hip`` and ``csrc/fft.hip``: no autograd graph of torch ops, no atomics
+callables whose maps are kernels of ``csrc/operators.hip``, ``csrc/fft.hip`` and ``csrc/radon.hip``: no autograd graph of torch ops, no atomics
 (two runs give the same bits) and a fixed launch sequence.  The project's own extension: the reference has no operator library.
 
     A = DownsampleOperator(2, flatten=True) @ BlurOperator.gaussian(1.0, 5)
@@ -14,6 +15,7 @@ callables whose three maps are kernels of ``csrc/operators.hip`` and ``csrc/fft.
     DecimateOperator(4, 2, flatten=True) @ BlurOperator(bicubic_taps(4))         # bicubic super-resolution x4
     ChannelMixOperator.grayscale(flatten=True)                                   # colourisation
     MRIOperator(cartesian_mask(256, 256, 4), flatten=True)                       # 4x accelerated single-coil MRI
+    RadonOperator(radon_angles(30), (256, 256), flatten=True)                    # sparse-view CT, 30 views
 
 Two paths, as ``RePaintSampler`` has them:
 
@@ -39,11 +41,13 @@ from .. import _lib
 from .repaint import _aligned, _broadcasts_to
 
 __all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps", "PSFOperator", "motion_psf",
-           "DecimateOperator", "bicubic_taps", "ChannelMixOperator", "FourierOperator", "MRIOperator", "cartesian_mask"]
+           "DecimateOperator", "bicubic_taps", "ChannelMixOperator", "FourierOperator", "MRIOperator", "cartesian_mask", "RadonOperator",
+           "radon_angles"]
 
 MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_decimate_f32 and of az_op_blur_f32 / az_op_psf_f32)
 MAX_CHANNELS = 16  # (the limit of az_op_chanmix_f32)
 MAX_FFT = 1024  # (AZ_OP_FFT2_MAX: the largest height or width of az_op_fft2_f32)
+MAX_RADON_SIZE, MAX_RADON_DET, MAX_RADON_ANGLES = 1024, 2048, 4096  # (AZ_OP_RADON_MAX_SIZE / _DET / _ANGLES)
 
 
 def _launch(name: str, *args) -> None:
@@ -901,3 +905,264 @@ class MRIOperator(LinearOperator):
         y = self._image(y, "pinv")
         self._in_shape_of(tuple(y.shape[1:]))
         return self._run(y, "pinv")
+
+
+# ----------------------------------------------------------------------------------------------------------------- Radon
+def radon_angles(n: int, span: float = 180.0) -> Tensor:
+    r"""``n`` evenly spaced angles in :math:`[0, \text{span})`, in degrees (fp64): ``span = 180`` with a small ``n`` is sparse-view
+    CT, a smaller ``span`` limited-angle CT."""
+    if n < 1 or not span > 0:
+        raise ValueError(f"radon_angles needs n >= 1 and span > 0, got n {n}, span {span}")
+    return torch.arange(n, dtype=torch.float64) * (float(span) / n)
+
+
+def _cos_sin_degrees(deg: float) -> tuple[float, float]:
+    r"""(cos, sin) of an angle in degrees, fp64: reduced modulo 360, evaluated within the octant and rotated by quadrants, so
+    that multiples of 90 give exactly 0 / +-1 and 45 gives two equal numbers."""
+    r = math.fmod(deg, 360.0)
+    if r < 0:
+        r += 360.0
+    q, r = divmod(r, 90.0)
+    if r == 45.0:
+        c = s = math.sqrt(0.5)
+    elif r < 45.0:
+        c, s = math.cos(math.radians(r)), math.sin(math.radians(r))
+    else:
+        c, s = math.sin(math.radians(90.0 - r)), math.cos(math.radians(90.0 - r))
+    for _ in range(int(q) % 4):
+        c, s = -s, c
+    return c + 0.0, s + 0.0  # (+ 0.0: no negative zero)
+
+
+class _ApplyMatrix(torch.autograd.Function):
+    r"""``op``'s map ``mode`` as products with its sparse matrix, for the tensors the kernels do not take.  ``torch.sparse.mm``
+    has a backward but no forward-mode rule, and ``MMPSDenoiser`` calls ``torch.func.jvp``; the map is linear, so -- as for
+    :class:`_Apply` -- ``backward`` and ``jvp`` are applications of this Function."""
+
+    @staticmethod
+    def forward(x: Tensor, op: RadonOperator, mode: str) -> Tensor:
+        return op._product(x, mode)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output) -> None:
+        _, ctx.op, ctx.mode = inputs
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return _ApplyMatrix.apply(g, ctx.op, ctx.op._TRANSPOSE[ctx.mode]), None, None
+
+    @staticmethod
+    def jvp(ctx, tx: Tensor, *_):
+        return _ApplyMatrix.apply(tx, ctx.op, ctx.mode)
+
+
+class RadonOperator(LinearOperator):
+    r"""Creates the parallel-beam Radon transform (computed tomography): a :math:`(B, C, H, W)` input gives the sinogram
+    :math:`(B, C, A, D)` of :math:`A` angles and :math:`D` detector bins, :math:`(A x)_{ak} = \sum_{ij} w_{akij} x_{ij}`.
+
+    Arguments:
+        theta: The :math:`A` projection angles in degrees (the convention of ``skimage.transform.radon``), a sequence or a
+            tensor; any finite values, at most 4096 of them.  See :func:`radon_angles`.
+        size: The image size :math:`(H, W)`, each at most 1024.  Required: the sinogram's shape does not determine it.
+        det_count: :math:`D`, at most 2048.  The default, :math:`2 \lceil \sqrt{H^2 + W^2} / (2 d) \rceil + 1`, covers the image
+            at every angle; a smaller count truncates the projections.
+        det_spacing: The bin spacing :math:`d` in pixels, :math:`1 \le d \le 8`.  Below 1 the pixel-driven model leaves combs of
+            empty bins, and filtered back-projection of it is useless.
+        flatten: See :class:`LinearOperator`.  A flat :math:`(B, C A D)` observation is un-flattened without a recorded input
+            shape: :math:`A D` is known.
+
+    The model is pixel driven with linear interpolation on the detector, and its weights are fp32 by definition.  Per angle the
+    host reduces :math:`\theta` modulo 360 in fp64, takes cosine and sine within the octant, rotates by quadrants and rounds to
+    fp32: multiples of 90 degrees give exactly 0 / :math:`\pm 1`, 45 degrees two equal numbers.  With
+    :math:`x = j - (W - 1) / 2`, :math:`y = i - (H - 1) / 2`, the position on the detector is
+    :math:`p = ((x c + y s) \cdot (1 / d)) + (D - 1) / 2`, every operation rounded to fp32 on its own, and the weight of bin
+    :math:`k` is :math:`w = \max(0, 1 - |p - k|)`.  Projector and back-projector (``csrc/radon.hip``) evaluate :math:`w` with
+    one device function, so ``adjoint`` is the exact transpose of the call -- what ``cg`` in ``DiffPIRDenoiser`` and
+    ``MMPSDenoiser`` assumes -- and the kernels add only the rounding of their sums.  No atomics: two runs give the same bits.
+
+    ``fbp(y)`` is filtered back-projection, :math:`(\pi / A) A^\top (h * y)` with the Ram-Lak taps :math:`h_0 = 1 / (4 d^2)`,
+    :math:`h_n = -1 / (\pi n d)^2` for odd :math:`n` and 0 for even :math:`n`, applied along the detector over its full length
+    with zero padding: an APPROXIMATE inverse for angles that evenly cover 180 degrees, and what ``PGDMSampler(denoiser, y, A,
+    A.fbp)`` takes.  There is no Moore--Penrose ``pinv``.
+
+    Every fp32 device tensor takes the kernels (made contiguous and aligned first).  Host and fp64 tensors take products with the
+    sparse matrix of the same fp32 weights, cast to the tensor's dtype and built once per device and dtype; half tensors take
+    the fp32 product and round its result (``torch.sparse.mm`` has no half-precision form on the device).  ``torch.sparse.mm``
+    has no forward-mode rule either, so that path is an ``autograd.Function`` of its own whose ``backward`` and ``jvp`` are
+    products with the same matrices.
+
+    Out of scope: fan-beam and cone-beam geometry, ray-driven (Siddon, Joseph) weights, :math:`d < 1`, other filters, a
+    pseudo-inverse, half-precision kernels, 3-D.
+    """
+
+    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "fbp": "fbp_t", "fbp_t": "fbp"}
+
+    def __init__(self, theta, size: Sequence[int], det_count: int | None = None, det_spacing: float = 1.0,
+                 flatten: bool = False) -> None:
+        super().__init__(flatten)
+        theta = torch.as_tensor(theta, dtype=torch.float64).detach().to(device="cpu").reshape(-1)  # (a list of floats stays fp64)
+        if not 1 <= theta.numel() <= MAX_RADON_ANGLES or not torch.isfinite(theta).all():
+            raise ValueError(f"theta is 1 .. {MAX_RADON_ANGLES} finite angles in degrees, got {theta.numel()}")
+        size = tuple(size) if isinstance(size, Sequence) else ()
+        if len(size) != 2 or not all(isinstance(n, int) and 1 <= n <= MAX_RADON_SIZE for n in size):
+            raise ValueError(f"size is (H, W), two ints in 1 .. {MAX_RADON_SIZE}, got {size}")
+        d = float(det_spacing)
+        if not 1.0 <= d <= 8.0:
+            raise ValueError("det_spacing is between 1 and 8 pixels (below 1 the pixel-driven model leaves empty bins), got "
+                             f"{det_spacing}")
+        D = 2 * math.ceil(math.hypot(*size) / d / 2) + 1 if det_count is None else det_count
+        if not (isinstance(D, int) and 1 <= D <= MAX_RADON_DET):
+            raise ValueError(f"det_count is an int in 1 .. {MAX_RADON_DET}, got {D}")
+        self.theta, self.size, self.det_count, self.det_spacing = theta, size, D, d
+        self.table = torch.tensor([_cos_sin_degrees(float(t)) for t in theta], dtype=torch.float64).to(torch.float32)  # (A, 2)
+        n = torch.arange(D, dtype=torch.float64)
+        taps = torch.zeros(D, dtype=torch.float64)
+        taps[0] = 1.0 / (4.0 * d * d)
+        taps[1::2] = -1.0 / (math.pi * n[1::2] * d) ** 2
+        self.taps = taps.to(torch.float32)
+        self.fbp_scale = float(torch.tensor(math.pi / theta.numel(), dtype=torch.float32))  # (pi / A as the kernel receives it)
+        self._cache: dict = {}
+
+    @property
+    def angles(self) -> int:
+        return self.theta.numel()
+
+    # -- shapes ---------------------------------------------------------------------------------------------------------
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        if tuple(in_shape[1:]) != self.size:
+            raise ValueError(f"this RadonOperator projects {self.size[0]} x {self.size[1]} images, got {in_shape[1]} x {in_shape[2]}")
+        return (in_shape[0], self.angles, self.det_count)
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        if tuple(out_shape[1:]) != (self.angles, self.det_count):
+            raise ValueError(f"a sinogram of this RadonOperator is {self.angles} x {self.det_count} (angles x bins), got "
+                             f"{out_shape[1]} x {out_shape[2]}")
+        return (out_shape[0], *self.size)
+
+    def _image(self, v: Tensor, what: str) -> Tensor:
+        if v.ndim == 2:  # (the channel count follows from A D: no recorded input shape is needed)
+            n = self.angles * self.det_count
+            if v.shape[1] == 0 or v.shape[1] % n:
+                raise ValueError(f"{what}: {tuple(v.shape)} is not a flattened (B, C, {self.angles}, {self.det_count}) sinogram")
+            return v.unflatten(1, (v.shape[1] // n, self.angles, self.det_count))
+        return super()._image(v, what)
+
+    # -- the kernels ----------------------------------------------------------------------------------------------------
+    def _on(self, x: Tensor, what: str) -> Tensor:
+        r"""The angle table or the filter taps on ``x``'s device, uploaded once."""
+        key = (what, x.device)
+        t = self._cache.get(key)
+        if t is None:
+            t = self._cache[key] = (self.table if what == "table" else self.taps).to(x.device).contiguous()
+        return t
+
+    def _project(self, x: Tensor) -> Tensor:
+        (B, c, H, W), A, D = x.shape, self.angles, self.det_count
+        y = _aligned(x.new_empty(B, c, A, D), 16)
+        if y.numel():
+            floats = C.c_int64(0)
+            _lib.call("az_op_radon_work", B * c, H, W, C.byref(floats))
+            work = _aligned(x.new_empty(max(floats.value, 4)), 16)  # (the transposed planes of the column-major angles)
+            _launch("az_op_radon_f32", y.data_ptr(), x.data_ptr(), self._on(x, "table").data_ptr(), work.data_ptr(), B * c, H, W, A, D,
+                    1.0 / self.det_spacing)
+        return y
+
+    def _backproject(self, v: Tensor, scale: float) -> Tensor:
+        (B, c, A, D), (H, W) = v.shape, self.size
+        x = _aligned(v.new_empty(B, c, H, W), 16)
+        if x.numel():
+            _launch("az_op_radon_adj_f32", x.data_ptr(), v.data_ptr(), self._on(v, "table").data_ptr(), B * c, H, W, A, D,
+                    1.0 / self.det_spacing, scale)
+        return x
+
+    def _filter(self, v: Tensor, scale: float) -> Tensor:
+        B, c, A, D = v.shape
+        y = _aligned(torch.empty_like(v), 16)
+        if y.numel():
+            _launch("az_op_radon_filter_f32", y.data_ptr(), v.data_ptr(), self._on(v, "taps").data_ptr(), B * c * A, D, scale)
+        return y
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        if mode == "apply":
+            return self._project(x)
+        if mode == "adjoint":
+            return self._backproject(x, 1.0)
+        scale = self.fbp_scale
+        if mode == "fbp":
+            return self._backproject(self._filter(x, 1.0), scale)
+        return self._filter(self._project(x), scale)  # "fbp_t": the filter is symmetric Toeplitz, so (A^T F)^T = F A
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        return _Apply.apply(g, self, self._TRANSPOSE[mode])
+
+    # -- the torch path -------------------------------------------------------------------------------------------------
+    def _weights(self) -> tuple[Tensor, Tensor, Tensor]:
+        r"""The nonzero weights as (row a D + k, column i W + j, fp32 value): the kernels' arithmetic, one rounded operation at
+        a time, on the bins floor(p) and floor(p) + 1 -- all that can have a weight."""
+        w = self._cache.get("weights")
+        if w is None:
+            (H, W), D, f = self.size, self.det_count, torch.float32
+            x = (torch.arange(W, dtype=f) - (W - 1) / 2)[None, :]
+            y = (torch.arange(H, dtype=f) - (H - 1) / 2)[:, None]
+            inv, off = torch.tensor(1.0 / self.det_spacing, dtype=f), torch.tensor((D - 1) / 2, dtype=f)
+            rows, cols, vals = [], [], []
+            for a in range(self.angles):
+                p = ((x * self.table[a, 0] + y * self.table[a, 1]) * inv + off).reshape(-1)  # (eager fp32 ops: nothing is fused)
+                k0 = p.floor()
+                for k in (k0, k0 + 1):
+                    wk = (1 - (p - k).abs()).clamp_min(0)
+                    keep = ((k >= 0) & (k < D) & (wk > 0)).nonzero()[:, 0]
+                    rows.append(a * D + k[keep].long())
+                    cols.append(keep)
+                    vals.append(wk[keep])
+            w = self._cache["weights"] = (torch.cat(rows), torch.cat(cols), torch.cat(vals))
+        return w
+
+    def _matrices(self, x: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+        r"""(M, M^T, the Toeplitz matrix of the taps) in ``x``'s dtype on its device, built once per device and dtype."""
+        key = ("matrix", x.device, x.dtype)
+        m = self._cache.get(key)
+        if m is None:
+            rows, cols, vals = self._weights()
+            (H, W), A, D = self.size, self.angles, self.det_count
+            vals = vals.to(device=x.device, dtype=x.dtype)
+            rows, cols = rows.to(x.device), cols.to(x.device)
+            M = torch.sparse_coo_tensor(torch.stack([rows, cols]), vals, (A * D, H * W)).coalesce()
+            Mt = torch.sparse_coo_tensor(torch.stack([cols, rows]), vals, (H * W, A * D)).coalesce()
+            idx = (torch.arange(D)[:, None] - torch.arange(D)[None, :]).abs()
+            m = self._cache[key] = (M, Mt, self.taps[idx].to(device=x.device, dtype=x.dtype))
+        return m
+
+    def _product(self, x: Tensor, mode: str) -> Tensor:
+        if x.dtype not in (torch.float32, torch.float64):  # (torch has no half-precision sparse product on the device)
+            return self._product(x.float(), mode).to(x.dtype)
+        M, Mt, T = self._matrices(x)
+        (H, W), A, D = self.size, self.angles, self.det_count
+        B, c = x.shape[:2]
+        scale = self.fbp_scale
+        if mode == "fbp":
+            x = x @ T
+        if mode in ("apply", "fbp_t"):
+            y = torch.sparse.mm(M, x.reshape(B * c, H * W).T).T.reshape(B, c, A, D)
+            return (y @ T) * scale if mode == "fbp_t" else y
+        y = torch.sparse.mm(Mt, x.reshape(B * c, A * D).T).T.reshape(B, c, H, W)
+        return y * scale if mode == "fbp" else y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        return _ApplyMatrix.apply(x, self, mode)
+
+    def _run(self, x: Tensor, mode: str) -> Tensor:
+        if _use_kernels(x) or (x.is_cuda and x.dtype == torch.float32):  # (a strided view too: the Function makes it contiguous)
+            return _Apply.apply(x, self, mode)
+        return self._torch(x, mode)
+
+    # -- the public maps ------------------------------------------------------------------------------------------------
+    def pinv(self, y: Tensor) -> Tensor:
+        raise NotImplementedError("RadonOperator has no pseudo-inverse; fbp is filtered back-projection, an approximate inverse for "
+                                  "angles that evenly cover 180 degrees")
+
+    def fbp(self, y: Tensor) -> Tensor:
+        r"""Filtered back-projection of a :math:`(B, C, A, D)` or flat sinogram: :math:`(\pi / A) A^\top (h * y)`."""
+        y = self._image(y, "fbp")
+        self._in_shape_of(tuple(y.shape[1:]))
+        return self._run(y, "fbp")

@@ -233,6 +233,45 @@ int az_op_fft2_f32(float* dst_re, float* dst_im, int64_t dst_bstride, const floa
                    az_stream_t stream);
 int az_op_fft2_work(int64_t B, int64_t C, int32_t H, int32_t W, int64_t* floats);
 
+/* ---- Parallel-beam Radon transform of the computed-tomography operator (csrc/radon.hip; RadonOperator) ---------------
+ * Planes of H x W fp32 (`planes` contiguous images) and sinograms of A x D fp32 (A angles, D detector bins, `planes` contiguous
+ * sinograms).  The model is pixel driven with linear interpolation on the detector and its weights are fp32 by definition: with
+ * (c, s) = table[2 a], table[2 a + 1], x = j - (W - 1) / 2, y = i - (H - 1) / 2,
+ *   p = fadd(fmul(fadd(fmul(x, c), fmul(y, s)), inv_spacing), (D - 1) / 2),   w(a, k, i, j) = max(0, fsub(1, |fsub(p, float(k))|)),
+ * every operation rounded on its own.  Both maps evaluate w with one device function, so the back-projector's matrix is exactly
+ * the transpose of the projector's; sums are chains of fused multiply-adds from 0 in a fixed order, no atomics, and a plane's
+ * result does not depend on the other planes of the launch.
+ * PRECONDITION: every table row is (cos, sin) of an angle, rounded to fp32 -- max(|c|, |s|) >= sqrt(1/2) is what bounds the
+ * projector's window; rows that are not are memory safe (every read is bounds checked) but lose weights.
+ *
+ * az_op_radon_f32: dst[n, a, k] = sum_{i, j} w(a, k, i, j) src[n, i, j].  One output per thread; the sum walks the major axis
+ * (rows where |c| >= |s|, else columns) ascending and, on each line, floor(2 h) + 3 candidates ascending from floor(n0 - h), n0
+ * the solution of p = k on that line and h = 1 / (inv_spacing max(|c|, |s|)).  Column-major angles read a transposed copy of the
+ * planes that the call makes in `work` (required: az_op_radon_work floats), so that their reads coalesce as the row-major ones do.
+ *
+ * az_op_radon_adj_f32: dst[n, i, j] = scale * sum_{a, k} w(a, k, i, j) src[n, a, k].  One pixel per thread; angles ascending,
+ * bins floor(p) and floor(p) + 1 (all that can have a weight), guarded by 0 <= k < D.
+ *
+ * az_op_radon_filter_f32: dst[r, s] = scale * sum_k taps[|s - k|] src[r, k] on `rows` rows of D, k ascending, for taps whose
+ * even offsets other than 0 are ZERO (the Ram-Lak ramp filter): only taps[0] and the odd taps (D of them in all) are read.
+ *
+ * Limits: planes, H, W, A, D > 0, H, W <= AZ_OP_RADON_MAX_SIZE, D <= AZ_OP_RADON_MAX_DET, A <= AZ_OP_RADON_MAX_ANGLES, planes <=
+ * 2^31, 1/8 <= inv_spacing <= 1 (else AZ_E_SHAPE).  Every pointer is required (AZ_E_NULL); images, sinograms and `work` are
+ * 16-byte aligned, the table and the taps 4-byte aligned (AZ_E_ALIGN); a destination overlaps no source and not `work`, and
+ * `work` no source (AZ_E_SHAPE).  table and taps are DEVICE pointers.
+ *
+ * az_op_radon_work: the floats of `work` of an az_op_radon_f32 call (planes H W).  Host arithmetic. */
+#define AZ_OP_RADON_MAX_SIZE 1024
+#define AZ_OP_RADON_MAX_DET 2048
+#define AZ_OP_RADON_MAX_ANGLES 4096
+int az_op_radon_f32(float* dst, const float* src, const float* table, float* work, int64_t planes, int32_t H, int32_t W, int32_t A,
+                    int32_t D, float inv_spacing, az_stream_t stream);
+int az_op_radon_adj_f32(float* dst, const float* src, const float* table, int64_t planes, int32_t H, int32_t W, int32_t A,
+                        int32_t D, float inv_spacing, float scale, az_stream_t stream);
+int az_op_radon_filter_f32(float* dst, const float* src, const float* taps, int64_t rows, int32_t D, float scale,
+                           az_stream_t stream);
+int az_op_radon_work(int64_t planes, int32_t H, int32_t W, int64_t* floats);
+
 /* ---- Twisted diffusion sampler: resample and proposal -------------------------------------------------------------
  * The non-network part of TDSSampler.step (azula/guidance/tds.py:70-102) for K particles of N elements each.
  *

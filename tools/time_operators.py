@@ -4,6 +4,7 @@ r"""Time ``az_op_blur_f32`` (through ``BlurOperator``), ``az_op_psf_f32`` (throu
     python tools/time_operators.py [taps] [B] [C] [H] [W]          # blur
     python tools/time_operators.py psf [size] [B] [C] [H] [W]      # general PSF
     python tools/time_operators.py fft [B] [C] [H] [W]             # 2-D Fourier transform
+    python tools/time_operators.py radon [B] [C] [H] [W] [angles]  # parallel-beam Radon transform
 
 Blur, default: the 61-tap Gaussian of DPS's deblurring setup on 4 x 3 x 256 x 256.  HIP events around back-to-back calls after a
 warm-up, the forms alternating over ``ROUNDS`` rounds; prints the median time per call of
@@ -30,7 +31,12 @@ difference is what the operator adds: the autograd Function and the allocations)
 (the vendor library, with the rearrangement to the split layout).  The yardstick is the bytes model of ``csrc/fft.hip`` at the
 same 6.29 TB/s: 12 bytes per element where a plane runs whole in LDS (at most 8192 points), else 28.
 
-The figures in DESIGN.md sections 9c and 9d come from this script.
+Radon, default: ``RadonOperator(radon_angles(180), (256, 256))`` apply, adjoint and ``fbp`` on 4 x 3 x 256 x 256 (``radon B C H W
+angles``).  The same method; the comparison is what a user can write today on the same device tensor, ``torch.sparse.mm`` with
+the same matrix (the operator's own path for fp64 and half tensors), and the yardstick the vector-fp32 peak over the operation
+counts ``A D max(H, W) window`` (apply, window 5 at spacing 1) and ``2 A H W`` (adjoint) fused multiply-adds per plane.
+
+The figures in DESIGN.md sections 9c, 9d and 9e come from this script.
 """
 
 from __future__ import annotations
@@ -51,6 +57,7 @@ import torch.nn.functional as F  # noqa: E402
 import operator_oracle as oo  # noqa: E402
 from azula_amd import _lib  # noqa: E402
 from azula_amd.guidance import BlurOperator, FourierOperator, PSFOperator, gaussian_taps, motion_psf  # noqa: E402
+from azula_amd.guidance import RadonOperator, radon_angles  # noqa: E402
 
 HBM = 6.29e12
 FP32_PEAK = 157.3e12  # vector fp32, FLOP/s
@@ -178,11 +185,36 @@ def fft(args: list[str]) -> None:
                       "model_fraction_adjoint": floor / med["adjoint"]}))
 
 
+def radon(args: list[str]) -> None:
+    B, Cc, H, W, n = (int(v) for v in (args + ["4", "3", "256", "256", "180"][len(args):]))
+    A = RadonOperator(radon_angles(n), (H, W))
+    D = A.det_count
+    x, v = torch.randn(B, Cc, H, W, device="cuda"), torch.randn(B, Cc, n, D, device="cuda")
+    # what a user can write today on the same device tensor: torch.sparse.mm with the same matrix (the operator's torch path)
+    forms = {"apply": (lambda: A(x), 20), "adjoint": (lambda: A.adjoint(v), 20), "fbp": (lambda: A.fbp(v), 20),
+             "sparse_mm_apply": (lambda: A._torch(x, "apply"), 5), "sparse_mm_adjoint": (lambda: A._torch(v, "adjoint"), 5)}
+    ref, ref_t, ref_f = (A._torch(t.double(), m) for t, m in ((x, "apply"), (v, "adjoint"), (v, "fbp")))
+    refs = {"apply": ref, "sparse_mm_apply": ref, "adjoint": ref_t, "sparse_mm_adjoint": ref_t, "fbp": ref_f}
+    err = {k: float((fn().double() - refs[k]).abs().max()) for k, (fn, _) in forms.items()}
+    times = measure(forms)
+    med = report(forms, times, err)
+    planes, window = B * Cc, 5  # (the candidates per line at spacing 1)
+    flop = {"apply": 2.0 * planes * n * D * max(H, W) * window, "adjoint": 2.0 * planes * 2 * n * H * W}
+    for k in ("apply", "adjoint"):
+        print(f"{k}: {flop[k] / 2e6:.1f} M fused multiply-adds: {flop[k] / FP32_PEAK * 1e6:.1f} us at the vector fp32 peak -> "
+              f"{flop[k] / FP32_PEAK / med[k]:.1%} of it; {med['sparse_mm_' + k] / med[k]:.1f} x faster than torch.sparse.mm")
+    print(json.dumps({"radon": [B, Cc, H, W, n, D], **{f"{k}_us": med[k] * 1e6 for k in forms},
+                      **{f"{k}_min_us": min(times[k]) * 1e6 for k in forms},
+                      **{f"fp32_peak_fraction_{k}": flop[k] / FP32_PEAK / med[k] for k in flop}}))
+
+
 def main() -> None:
     if not torch.cuda.is_available():
         raise SystemExit("time_operators.py measures on the GPU: no device visible")
     torch.manual_seed(0)
-    if sys.argv[1:2] == ["psf"]:
+    if sys.argv[1:2] == ["radon"]:
+        radon(sys.argv[2:7])
+    elif sys.argv[1:2] == ["psf"]:
         psf(sys.argv[2:7])
     elif sys.argv[1:2] == ["fft"]:
         fft(sys.argv[2:6])
