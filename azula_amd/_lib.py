@@ -412,6 +412,8 @@ PROTOTYPES: dict[str, list] = {
     "az_op_chanmix_f32": [vp, vp, vp, i64, i32, i32, i64, c_stream],
     "az_op_fft2_f32": [vp, vp, i64, vp, vp, i64, vp, i64, i64, i32, i32, i32, f32, c_stream],
     "az_op_fft2_work": [i64, i64, i32, i32, C.POINTER(i64)],
+    "az_op_coil_expand_f32": [vp, vp, i64, vp, vp, i64, vp, vp, i64, i64, i32, i64, c_stream],
+    "az_op_coil_combine_f32": [vp, vp, i64, vp, vp, i64, vp, vp, i64, i64, i32, i64, i32, c_stream],
     "az_op_radon_f32": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, c_stream],
     "az_op_radon_adj_f32": [vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, c_stream],
     "az_op_radon_filter_f32": [vp, vp, vp, i64, i32, f32, c_stream],

@@ -5,8 +5,9 @@ undersampling: accelerated MRI) and the parallel-beam Radon transform (sparse-vi
 
 The guidance classes take the operator :math:`A` of :math:`y = A x + n` as a callable and differentiate it with
 ``torch.autograd.grad`` (DPS, TMPD, MMPS, JFPS, DiffPIR) and ``torch.func.jvp`` (MMPS, JFPS).  The operators below are such
-callables whose maps are kernels of ``csrc/operators.hip``, ``csrc/fft.hip`` and ``csrc/radon.hip``: no autograd graph of torch ops, no atomics
-(two runs give the same bits) and a fixed launch sequence.  The project's own extension: the reference has no operator library.
+callables whose maps are kernels of ``csrc/operators.hip``, ``csrc/fft.hip``, ``csrc/coil.hip`` and ``csrc/radon.hip``: no autograd
+graph of torch ops, no atomics (two runs give the same bits) and a fixed launch sequence.  The project's own extension: the
+reference has no operator library.
 
     A = DownsampleOperator(2, flatten=True) @ BlurOperator.gaussian(1.0, 5)
     DiffPIRDenoiser(denoiser, y, A, var_y)              # y: (B, D)
@@ -15,6 +16,7 @@ callables whose maps are kernels of ``csrc/operators.hip``, ``csrc/fft.hip`` and
     DecimateOperator(4, 2, flatten=True) @ BlurOperator(bicubic_taps(4))         # bicubic super-resolution x4
     ChannelMixOperator.grayscale(flatten=True)                                   # colourisation
     MRIOperator(cartesian_mask(256, 256, 4), flatten=True)                       # 4x accelerated single-coil MRI
+    MultiCoilMRIOperator(cartesian_mask(256, 256, 4), birdcage_maps(8, 256, 256), flatten=True)   # 8-coil SENSE MRI
     RadonOperator(radon_angles(30), (256, 256), flatten=True)                    # sparse-view CT, 30 views
 
 Two paths, as ``RePaintSampler`` has them:
@@ -41,8 +43,8 @@ from .. import _lib
 from .repaint import _aligned, _broadcasts_to
 
 __all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps", "PSFOperator", "motion_psf",
-           "DecimateOperator", "bicubic_taps", "ChannelMixOperator", "FourierOperator", "MRIOperator", "cartesian_mask", "RadonOperator",
-           "radon_angles"]
+           "DecimateOperator", "bicubic_taps", "ChannelMixOperator", "FourierOperator", "MRIOperator", "cartesian_mask",
+           "MultiCoilMRIOperator", "birdcage_maps", "RadonOperator", "radon_angles"]
 
 MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_decimate_f32 and of az_op_blur_f32 / az_op_psf_f32)
 MAX_CHANNELS = 16  # (the limit of az_op_chanmix_f32)
@@ -724,8 +726,8 @@ class FourierOperator(LinearOperator):
     of two up to 1024; any other size of such a tensor raises ``NotImplementedError`` -- there is no vendor-FFT fallback on that
     path.  Host and fp64 tensors run ``torch.fft`` in their own dtype at any size; half precision is not provided.
 
-    Out of scope: non-power-of-two sizes on the device, multi-coil sensitivity maps, ``fftshift``-ed layouts, nonlinear phase
-    retrieval, 3-D transforms, and an FFT-based ``pinv`` for the circular :class:`BlurOperator`.
+    Out of scope: non-power-of-two sizes on the device, ``fftshift``-ed layouts, nonlinear phase retrieval, 3-D transforms, and
+    an FFT-based ``pinv`` for the circular :class:`BlurOperator`.  Coil sensitivity maps: :class:`MultiCoilMRIOperator`.
     """
 
     _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv_t", "pinv_t": "pinv"}
@@ -851,6 +853,17 @@ def cartesian_columns(W: int, acceleration: float, center_fraction: float = 0.08
     return min(W, 2 * c + 1) + 2 * min(pairs, max(0, (n - (2 * c + 1)) // 2))
 
 
+def _check_kspace_mask(mask: Tensor) -> None:
+    r"""The rules of a sampling mask on a split-complex observation (:class:`MRIOperator`, :class:`MultiCoilMRIOperator`)."""
+    if mask.ndim < 2:
+        raise ValueError(f"mask is (H, W) or broadcasts to (B, 2 C, H, W), got shape {tuple(mask.shape)}")
+    if mask.ndim >= 3 and mask.shape[-3] > 1:
+        half = mask.shape[-3] // 2
+        if mask.shape[-3] % 2 or not torch.equal(mask[..., :half, :, :], mask[..., half:, :, :]):
+            raise ValueError("a mask with a channel axis has the same values on the real and the imaginary half of the 2 C "
+                             f"channels, got shape {tuple(mask.shape)}")
+
+
 class MRIOperator(LinearOperator):
     r"""Creates single-coil Cartesian k-space undersampling :math:`A = M F`: ``MaskOperator(mask) @ FourierOperator(norm)`` as
     one operator, so that it has a pseudo-inverse.  A :math:`(B, C, H, W)` input gives a :math:`(B, 2 C, H, W)` observation.
@@ -867,20 +880,14 @@ class MRIOperator(LinearOperator):
     :math:`F F^+` projects onto the Hermitian-symmetric spectra and commutes with :math:`M` only then.  The symmetry is checked
     once, at construction; ``pinv`` of an unsymmetric mask raises ``NotImplementedError``.
 
-    Out of scope: see :class:`FourierOperator`.
+    Out of scope: see :class:`FourierOperator`.  Complex images and coil sensitivity maps: :class:`MultiCoilMRIOperator`.
     """
 
     def __init__(self, mask: Tensor, norm: str = "ortho", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
         self.fourier = FourierOperator(norm)
         self.sampling = MaskOperator(mask)
-        if mask.ndim < 2:
-            raise ValueError(f"mask is (H, W) or broadcasts to (B, 2 C, H, W), got shape {tuple(mask.shape)}")
-        if mask.ndim >= 3 and mask.shape[-3] > 1:
-            half = mask.shape[-3] // 2
-            if mask.shape[-3] % 2 or not torch.equal(mask[..., :half, :, :], mask[..., half:, :, :]):
-                raise ValueError("a mask with a channel axis has the same values on the real and the imaginary half of the 2 C "
-                                 f"channels, got shape {tuple(mask.shape)}")
+        _check_kspace_mask(mask)
         self.symmetric = bool(torch.equal(mask, mask.flip(-2, -1).roll((1, 1), (-2, -1))))
 
     @property
@@ -905,6 +912,239 @@ class MRIOperator(LinearOperator):
         y = self._image(y, "pinv")
         self._in_shape_of(tuple(y.shape[1:]))
         return self._run(y, "pinv")
+
+
+# ------------------------------------------------------------------------------------------------------------ multi-coil
+def birdcage_maps(coils: int, H: int, W: int, radius: float = 1.5) -> Tensor:
+    r"""``coils`` synthetic sensitivity maps of a birdcage array, a ``complex128`` tensor :math:`(K, H, W)` for tests and demos,
+    computed on the CPU in fp64 without random numbers.  Pixel centres span :math:`(-1, 1)^2` (units of the half field of view);
+    coil :math:`k` sits at the angle :math:`2 \pi k / K` on a circle of ``radius``.  A map's magnitude is 1 / distance to its
+    coil and its phase the angle of the vector from the pixel to the coil; the set is normalised so that
+    :math:`\sum_k |S_k|^2 = 1` at every pixel.  ``radius`` exceeds :math:`\sqrt 2`, so no coil lies inside the image."""
+    if not (isinstance(coils, int) and coils >= 1 and H >= 1 and W >= 1 and radius > math.sqrt(2.0)):
+        raise ValueError(f"birdcage_maps needs coils, H, W >= 1 and radius > sqrt(2), got coils {coils}, {H} x {W}, radius {radius}")
+    y = ((torch.arange(H, dtype=torch.float64) - (H - 1) / 2) / (H / 2))[None, :, None]
+    x = ((torch.arange(W, dtype=torch.float64) - (W - 1) / 2) / (W / 2))[None, None, :]
+    ang = (2 * math.pi / coils) * torch.arange(coils, dtype=torch.float64)[:, None, None]
+    dx, dy = radius * torch.cos(ang) - x, radius * torch.sin(ang) - y
+    dist = torch.hypot(dx, dy)
+    s = torch.complex(dx, dy) / (dist * dist)  # exp(i phase) / distance
+    return s / (s.real**2 + s.imag**2).sum(0, keepdim=True).sqrt()
+
+
+class MultiCoilMRIOperator(LinearOperator):
+    r"""Creates multi-coil Cartesian k-space undersampling (SENSE parallel imaging):
+    :math:`y_k = M F (S_k \odot x)`, :math:`k = 0 .. K - 1`, with complex coil sensitivity maps :math:`S_k`.
+
+    Arguments:
+        mask: The sampling mask :math:`M` in DFT order, by the rules of :class:`MRIOperator`: :math:`(H, W)` or anything that
+            broadcasts to :math:`(B, 2 K, H, W)` with equal real and imaginary halves.  See :func:`cartesian_mask`.
+        maps: The sensitivity maps, a ``complex64`` or ``complex128`` tensor :math:`(K, H, W)` (one set for every sample) or
+            :math:`(B, K, H, W)` (one per sample), finite.  Kept as split planes and moved to an input's device and dtype on first
+            use: build a new operator for new maps rather than editing them in place.  See :func:`birdcage_maps`.
+        norm: See :class:`FourierOperator`.
+        complex_image: The input is :math:`(B, 2, H, W)` = :math:`\Re x \,|\, \Im x` (``True``) or a real image
+            :math:`(B, 1, H, W)` (``False``).
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    The observation is :math:`(B, 2 K, H, W)`: channel :math:`k` is :math:`\Re y_k` and channel :math:`K + k` is
+    :math:`\Im y_k`, :class:`FourierOperator`'s convention with :math:`C = K`, so :class:`MaskOperator`, ``flatten`` and
+    ``A2 @ A1`` apply unchanged.  The adjoint is :math:`\sum_k \bar S_k \odot F^H M y_k` (its real part for a real image): as a
+    real-linear map on split-complex vectors, multiplication by :math:`\bar S` is the transpose of multiplication by :math:`S`,
+    so this is the exact transpose.
+
+    ``zero_filled(y)`` is the coil-combined zero-filled reconstruction
+    :math:`\sum_k \bar S_k \odot F^+ M^+ y_k \,/\, \sum_k |S_k|^2` (0 where the maps vanish), with :math:`F^+` at the scale of
+    :class:`FourierOperator`'s ``pinv``: what ``PGDMSampler(denoiser, y, A, A.zero_filled)`` takes.  It is the Moore--Penrose
+    inverse exactly under full sampling with :math:`\sum_k |S_k|^2 > 0` everywhere, for both image kinds; under undersampling it
+    is the standard APPROXIMATION, not the pseudo-inverse.
+    ``pinv`` raises ``NotImplementedError``: solve the normal equations with ``linalg.cg`` where the exact one is needed.
+
+    Every fp32 device tensor takes the kernels -- ``az_op_coil_expand_f32``, ``az_op_fft2_f32``, ``az_op_mul_f32`` and, on the
+    way back, ``az_op_coil_combine_f32`` -- with two :math:`(B, 2 K, H, W)` intermediate buffers per call (the FFT entry is not
+    in place); heights and widths are powers of two up to 1024 there.  Host and fp64 tensors run ``torch.complex`` /
+    ``torch.fft`` in their own dtype at any size; half precision is not provided.
+
+    Out of scope: fusing the coil product into the FFT's row loads, ESPIRiT calibration of the maps, ``fftshift``-ed layouts,
+    non-Cartesian trajectories, more than one complex image per sample, and non-power-of-two sizes on the device.
+    """
+
+    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "zero_filled": "zero_filled_t", "zero_filled_t": "zero_filled"}
+
+    def __init__(self, mask: Tensor, maps: Tensor, norm: str = "ortho", complex_image: bool = True, flatten: bool = False,
+                 in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        self.fourier = FourierOperator(norm)
+        self.sampling = MaskOperator(mask)
+        _check_kspace_mask(mask)
+        if not torch.is_tensor(maps) or maps.dtype not in (torch.complex64, torch.complex128):
+            raise ValueError("maps is a complex64 or complex128 tensor, got "
+                             f"{maps.dtype if torch.is_tensor(maps) else type(maps).__name__}")
+        if maps.ndim not in (3, 4) or maps.shape[-3] < 1 or 0 in maps.shape:
+            raise ValueError(f"maps is (K, H, W) or (B, K, H, W) with K >= 1, got shape {tuple(maps.shape)}")
+        maps = maps.detach().to(device="cpu", dtype=torch.complex128)
+        if not (torch.isfinite(maps.real).all() and torch.isfinite(maps.imag).all()):
+            raise ValueError("maps has a non-finite value")
+        self.maps_re, self.maps_im = maps.real.contiguous(), maps.imag.contiguous()  # fp64 split planes
+        self.complex_image = bool(complex_image)
+        self._cache: dict = {}
+
+    @property
+    def mask(self) -> Tensor:
+        return self.sampling.mask
+
+    @property
+    def coils(self) -> int:
+        return self.maps_re.shape[-3]
+
+    # -- shapes ---------------------------------------------------------------------------------------------------------
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        out = self._cache.get(("out", in_shape))  # (a shape is checked once: broadcast_shapes costs more than a launch)
+        if out is None:
+            out = self._cache[("out", in_shape)] = self._checked_out_shape(in_shape)
+        return out
+
+    def _checked_out_shape(self, in_shape: tuple) -> tuple:
+        c = 2 if self.complex_image else 1
+        if in_shape[0] != c:
+            raise ValueError(f"MultiCoilMRIOperator(complex_image={self.complex_image}) takes {c} channel{'s' * (c - 1)} "
+                             f"({'re, then im' if c == 2 else 'a real image'}), got {in_shape[0]}")
+        if tuple(in_shape[1:]) != tuple(self.maps_re.shape[-2:]):
+            raise ValueError(f"the maps are {self.maps_re.shape[-2]} x {self.maps_re.shape[-1]}, got an image of {in_shape[1]} x "
+                             f"{in_shape[2]}")
+        return self.sampling._out_shape((2 * self.coils, *in_shape[1:]))
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        if out_shape[0] != 2 * self.coils:
+            raise ValueError(f"an observation of {self.coils} coils has {2 * self.coils} channels (re, then im), got {out_shape[0]}")
+        if ("in", out_shape) not in self._cache:
+            self.sampling._out_shape(out_shape)
+            self._cache[("in", out_shape)] = True
+        return (2 if self.complex_image else 1, *out_shape[1:])
+
+    def _check_batch(self, x: Tensor) -> None:
+        if self.maps_re.ndim == 4 and self.maps_re.shape[0] != x.shape[0]:
+            raise ValueError(f"maps of shape {tuple(self.maps_re.shape)} are for a batch of {self.maps_re.shape[0]}, got "
+                             f"{tuple(x.shape)}")
+
+    def _check_mask_batch(self, y: Tensor) -> None:
+        r"""``MaskOperator._check_batch`` of an observation, once per shape."""
+        key = ("mask", tuple(y.shape))
+        if key not in self._cache:
+            self.sampling._check_batch(y)
+            self._cache[key] = True
+
+    def _maps(self, x: Tensor, normalized: bool) -> tuple[Tensor, Tensor]:
+        r"""(re, im) of :math:`S`, or of :math:`S / \sum_k |S_k|^2` (0 where that is 0), in ``x``'s dtype on its device."""
+        key = (x.device, x.dtype, normalized)
+        m = self._cache.get(key)
+        if m is None:
+            re, im = self.maps_re, self.maps_im
+            if normalized:
+                D = (re * re + im * im).sum(-3, keepdim=True)
+                inv = torch.where(D != 0, 1 / torch.where(D != 0, D, torch.ones_like(D)), torch.zeros_like(D))
+                re, im = re * inv, im * inv
+            m = self._cache[key] = tuple(_aligned(v.to(device=x.device, dtype=x.dtype).contiguous(), 16) for v in (re, im))
+        return m
+
+    # -- the kernels ----------------------------------------------------------------------------------------------------
+    def _coil_buffers(self, x: Tensor, B: int, K: int, h: int, w: int) -> tuple[Tensor | None, Tensor, Tensor, int]:
+        r"""A split-complex (B, 2 K, h, w) buffer as (whole, re, im, sample stride): the halves of one tensor where both start
+        16-byte aligned (K h w % 4 == 0), else two tensors."""
+        n = K * h * w
+        if n % 4 == 0:
+            whole = _aligned(x.new_empty(B, 2 * K, h, w), 16)
+            return whole, whole[:, :K], whole[:, K:], 2 * n
+        return None, _aligned(x.new_empty(B, K, h, w), 16), _aligned(x.new_empty(B, K, h, w), 16), n
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        self._check_batch(x)
+        B, _, h, w = x.shape
+        K, hw = self.coils, h * w
+        n = K * hw
+        s_re, s_im = self._maps(x, mode == "zero_filled_t")
+        s_bs = n if s_re.ndim == 4 else 0
+        c = 2 if self.complex_image else 1
+        if mode in ("apply", "zero_filled_t"):  # image -> coil images -> k-space -> mask
+            if not x.numel():
+                return x.new_empty(B, 2 * K, h, w)
+            _, c_re, c_im, c_bs = self._coil_buffers(x, B, K, h, w)
+            _launch("az_op_coil_expand_f32", c_re.data_ptr(), c_im.data_ptr(), c_bs, x.data_ptr(),
+                    x.data_ptr() + 4 * hw if c == 2 else None, c * hw, s_re.data_ptr(), s_im.data_ptr(), s_bs, B, K, hw)
+            y, y_re, y_im, y_bs = self._coil_buffers(x, B, K, h, w)
+            _launch("az_op_fft2_f32", y_re.data_ptr(), y_im.data_ptr(), y_bs, c_re.data_ptr(), c_im.data_ptr(), c_bs, None, B, K, h,
+                    w, 0, self.fourier._scale(hw, "apply" if mode == "apply" else "pinv_t"))
+            if y is None:
+                y = _aligned(torch.cat([y_re, y_im], dim=1), 16)
+            self._check_mask_batch(y)
+            m = self.sampling._factor(y, mode == "zero_filled_t")
+            _launch("az_op_mul_f32", y.data_ptr(), y.data_ptr(), m.data_ptr(), y.numel(), m.numel())  # (in place: y is ours)
+            return y
+        # k-space -> mask -> coil images -> image
+        out = _aligned(x.new_empty(B, c, h, w), 16)
+        if not out.numel():
+            return out
+        self._check_mask_batch(x)
+        m = self.sampling._factor(x, mode == "zero_filled")
+        v = _aligned(torch.empty_like(x), 16)
+        _launch("az_op_mul_f32", v.data_ptr(), x.data_ptr(), m.data_ptr(), x.numel(), m.numel())
+        if n % 4 == 0:
+            v_re, v_im, v_bs = v.data_ptr(), v.data_ptr() + 4 * n, 2 * n
+        else:
+            halves = _aligned(v[:, :K].contiguous(), 16), _aligned(v[:, K:].contiguous(), 16)
+            v_re, v_im, v_bs = halves[0].data_ptr(), halves[1].data_ptr(), n
+        _, c_re, c_im, c_bs = self._coil_buffers(x, B, K, h, w)
+        _launch("az_op_fft2_f32", c_re.data_ptr(), c_im.data_ptr(), c_bs, v_re, v_im, v_bs, None, B, K, h, w, 1,
+                self.fourier._scale(hw, "adjoint" if mode == "adjoint" else "pinv"))
+        _launch("az_op_coil_combine_f32", out.data_ptr(), out.data_ptr() + 4 * hw if c == 2 else None, c * hw, c_re.data_ptr(),
+                c_im.data_ptr(), c_bs, s_re.data_ptr(), s_im.data_ptr(), s_bs, B, K, hw, int(mode == "zero_filled"))
+        return out
+
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        return _Apply.apply(g, self, self._TRANSPOSE[mode])
+
+    # -- the torch path -------------------------------------------------------------------------------------------------
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        if x.dtype not in (torch.float32, torch.float64):
+            raise NotImplementedError(f"MultiCoilMRIOperator runs in fp32 and fp64, got {x.dtype}")
+        self._check_batch(x)
+        h, w = x.shape[2:]
+        K = self.coils
+        s = torch.complex(*self._maps(x, mode == "zero_filled_t"))
+        if mode in ("apply", "zero_filled_t"):
+            img = torch.complex(x[:, 0], x[:, 1]) if self.complex_image else x[:, 0]
+            f = torch.fft.fft2(s * img[:, None]) * self.fourier._scale(h * w, "apply" if mode == "apply" else "pinv_t")
+            return self.sampling._torch(torch.cat([f.real, f.imag], dim=1), "pinv" if mode == "zero_filled_t" else "apply")
+        v = self.sampling._torch(x, "pinv" if mode == "zero_filled" else "apply")
+        z = torch.fft.ifft2(torch.complex(v[:, :K], v[:, K:]), norm="forward")  # ("forward": unscaled inverse)
+        z = z * self.fourier._scale(h * w, "adjoint" if mode == "adjoint" else "pinv")
+        img = (s.conj() * z).sum(1, keepdim=True)
+        if mode == "zero_filled":
+            D = (s.real * s.real + s.imag * s.imag).sum(-3, keepdim=True)
+            img = torch.where(D != 0, img / torch.where(D != 0, D, torch.ones_like(D)), torch.zeros_like(img))
+        return torch.cat([img.real, img.imag], dim=1) if self.complex_image else img.real
+
+    def _run(self, x: Tensor, mode: str) -> Tensor:
+        if _use_kernels(x) or (x.is_cuda and x.dtype == torch.float32):  # (a strided view too: the Function makes it contiguous)
+            h, w = x.shape[2:]
+            if not (_fft_kernel_size(h) and _fft_kernel_size(w)):
+                raise NotImplementedError(f"MultiCoilMRIOperator on an fp32 device tensor needs a height and width that are powers "
+                                          f"of two of at most {MAX_FFT}, got {h} x {w}; host and fp64 tensors take any size")
+            return _Apply.apply(x, self, mode)
+        return self._torch(x, mode)
+
+    # -- the public maps ------------------------------------------------------------------------------------------------
+    def pinv(self, y: Tensor) -> Tensor:
+        raise NotImplementedError("MultiCoilMRIOperator has no closed-form pseudo-inverse under undersampling; zero_filled is the "
+                                  "coil-combined zero-filled reconstruction (exact under full sampling), and linalg.cg solves the "
+                                  "normal equations")
+
+    def zero_filled(self, y: Tensor) -> Tensor:
+        r"""The coil-combined zero-filled reconstruction of a :math:`(B, 2 K, H, W)` or flat observation:
+        :math:`\sum_k \bar S_k \odot F^+ M^+ y_k \,/\, \sum_k |S_k|^2`."""
+        y = self._image(y, "zero_filled")
+        self._out_shape(self._in_shape_of(tuple(y.shape[1:])))
+        return self._run(y, "zero_filled")
 
 
 # ----------------------------------------------------------------------------------------------------------------- Radon

@@ -233,6 +233,35 @@ int az_op_fft2_f32(float* dst_re, float* dst_im, int64_t dst_bstride, const floa
                    az_stream_t stream);
 int az_op_fft2_work(int64_t B, int64_t C, int32_t H, int32_t W, int64_t* floats);
 
+/* ---- Coil maps of multi-coil (SENSE) MRI (csrc/coil.hip; MultiCoilMRIOperator) -----------------------------------------
+ * y_k = M F (S_k . x), k < K, with complex sensitivity maps S_k.  SPLIT-complex fp32 in az_op_fft2_f32's plane convention: plane
+ * (b, k) of a tensor starts at base + b * bstride + k * HW floats and the real and imaginary parts have separate bases, so the two
+ * halves of a (B, 2 K, H, W) tensor are a destination or a source.  HW is any plane size (not only a power of two).
+ *
+ * az_op_coil_expand_f32: dst[b, k] = S[b, k] . x[b].  Replaces the torch sequence torch.complex(x_re, x_im)[:, None] * maps
+ * followed by the split into .real / .imag that torch.fft-based SENSE code writes (four elementwise launches and a (B, K, H, W)
+ * complex temporary).  x_im == NULL: a real image.  With x = a + i b and S = c + i d: re = fma(a, c, -(b d)), im = fma(a, d, b c);
+ * real image: re = a c, im = a d (single roundings).  (4 or 8) + 16 K bytes per pixel.
+ *
+ * az_op_coil_combine_f32: dst[b] = sum_k conj(S[b, k]) . z[b, k], the transpose of expand as a real-linear map.  Replaces
+ * (maps.conj() * z).sum(1) and, with normalize = 1, the division by (maps.abs() ** 2).sum(1) of the coil-combined zero-filled
+ * reconstruction.  dst_im == NULL: the real part only.  With z = p + i q, from 0 with k ascending: re = fma(c, p, re), re =
+ * fma(d, q, re); im = fma(c, q, im), im = fma(-d, p, im).  normalize = 1 accumulates D = sum_k (c^2 + d^2) with fmas in the same
+ * loop and writes acc / D (IEEE division), or 0 where D == 0.  16 K + (4 or 8) bytes per pixel.  No atomics: a fixed order.
+ *
+ * s_bstride = 0: one set of maps for the whole batch; >= K HW: per-sample maps.  Bases and strides that are multiples of 4 floats
+ * with HW % 4 == 0 take 16-byte loads and stores, anything else a scalar form.  K >= 1, B, HW >= 0 (an empty tensor launches
+ * nothing and returns AZ_OK), strides >= 0 and, for B > 1, at least the tensor's K HW or HW floats, normalize 0 or 1 (else
+ * AZ_E_SHAPE); every pointer but x_im (expand) and dst_im (combine) is required -- the product with a complex map is complex, and
+ * coil data is complex (AZ_E_NULL); pointers are 4-byte aligned (AZ_E_ALIGN); no destination plane shares a float with the other
+ * destination or with a source (AZ_E_SHAPE). */
+int az_op_coil_expand_f32(float* dst_re, float* dst_im, int64_t dst_bstride, const float* x_re, const float* x_im,
+                          int64_t x_bstride, const float* s_re, const float* s_im, int64_t s_bstride, int64_t B, int32_t K,
+                          int64_t HW, az_stream_t stream);
+int az_op_coil_combine_f32(float* dst_re, float* dst_im, int64_t dst_bstride, const float* z_re, const float* z_im,
+                           int64_t z_bstride, const float* s_re, const float* s_im, int64_t s_bstride, int64_t B, int32_t K,
+                           int64_t HW, int32_t normalize, az_stream_t stream);
+
 /* ---- Parallel-beam Radon transform of the computed-tomography operator (csrc/radon.hip; RadonOperator) ---------------
  * Planes of H x W fp32 (`planes` contiguous images) and sinograms of A x D fp32 (A angles, D detector bins, `planes` contiguous
  * sinograms).  The model is pixel driven with linear interpolation on the detector and its weights are fp32 by definition: with

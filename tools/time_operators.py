@@ -5,6 +5,7 @@ r"""Time ``az_op_blur_f32`` (through ``BlurOperator``), ``az_op_psf_f32`` (throu
     python tools/time_operators.py psf [size] [B] [C] [H] [W]      # general PSF
     python tools/time_operators.py fft [B] [C] [H] [W]             # 2-D Fourier transform
     python tools/time_operators.py radon [B] [C] [H] [W] [angles]  # parallel-beam Radon transform
+    python tools/time_operators.py sense [B] [K] [H] [W]           # multi-coil (SENSE) MRI
 
 Blur, default: the 61-tap Gaussian of DPS's deblurring setup on 4 x 3 x 256 x 256.  HIP events around back-to-back calls after a
 warm-up, the forms alternating over ``ROUNDS`` rounds; prints the median time per call of
@@ -36,7 +37,14 @@ angles``).  The same method; the comparison is what a user can write today on th
 the same matrix (the operator's own path for fp64 and half tensors), and the yardstick the vector-fp32 peak over the operation
 counts ``A D max(H, W) window`` (apply, window 5 at spacing 1) and ``2 A H W`` (adjoint) fused multiply-adds per plane.
 
-The figures in DESIGN.md sections 9c, 9d and 9e come from this script.
+SENSE, default: ``MultiCoilMRIOperator(cartesian_mask(H, W, 4), birdcage_maps(K, H, W))`` apply and adjoint on a complex image,
+4 x 8 x 256 x 256 (``sense B K H W``; run it on 16 4 64 64 for the whole-plane FFT form).  The same method; the forms are the
+operator, the two coil entries alone on buffers made once, and the torch lambda a user writes today (complex multiply,
+``torch.fft``, mask, with the rearrangement to the split layout).  The yardsticks are the byte models of ``csrc/coil.hip`` at the
+same 6.29 TB/s: ``8 + 16 K`` bytes per pixel for either entry, and for the operator the sum over its three launches (the entry,
+the FFT's 24 or 56 bytes per coil pixel complex to complex, the mask's 16 bytes per coil pixel).
+
+The figures in DESIGN.md sections 9c, 9d, 9e and 9f come from this script.
 """
 
 from __future__ import annotations
@@ -57,6 +65,7 @@ import torch.nn.functional as F  # noqa: E402
 import operator_oracle as oo  # noqa: E402
 from azula_amd import _lib  # noqa: E402
 from azula_amd.guidance import BlurOperator, FourierOperator, PSFOperator, gaussian_taps, motion_psf  # noqa: E402
+from azula_amd.guidance import MultiCoilMRIOperator, birdcage_maps, cartesian_mask  # noqa: E402
 from azula_amd.guidance import RadonOperator, radon_angles  # noqa: E402
 
 HBM = 6.29e12
@@ -208,12 +217,66 @@ def radon(args: list[str]) -> None:
                       **{f"fp32_peak_fraction_{k}": flop[k] / FP32_PEAK / med[k] for k in flop}}))
 
 
+def sense(args: list[str]) -> None:
+    B, K, H, W = (int(v) for v in (args + ["4", "8", "256", "256"][len(args):]))
+    hw, n = H * W, K * H * W
+    maps, m = birdcage_maps(K, H, W), cartesian_mask(H, W, 4)
+    A = MultiCoilMRIOperator(m, maps)
+    x, z = torch.randn(B, 2, H, W, device="cuda"), torch.randn(B, 2 * K, H, W, device="cuda")
+    sd, md = maps.to(torch.complex64).cuda(), m.cuda()
+
+    def lam(v):  # what a user writes today
+        f = torch.fft.fft2(sd * torch.complex(v[:, 0], v[:, 1])[:, None], norm="ortho")
+        return torch.cat([f.real, f.imag], dim=1) * md
+
+    def lam_t(v):
+        v = v * md
+        img = (sd.conj() * torch.fft.ifft2(torch.complex(v[:, :K], v[:, K:]), norm="ortho")).sum(1)
+        return torch.stack([img.real, img.imag], dim=1)
+
+    # the two entries alone on buffers made once
+    s_re, s_im = sd.real.contiguous(), sd.imag.contiguous()
+    coil, img, stream = torch.empty_like(z), torch.empty_like(x), _lib.stream_ptr()
+    entry = lambda: _lib.call("az_op_coil_expand_f32", coil.data_ptr(), coil.data_ptr() + 4 * n, 2 * n, x.data_ptr(),  # noqa: E731
+                              x.data_ptr() + 4 * hw, 2 * hw, s_re.data_ptr(), s_im.data_ptr(), 0, B, K, hw, stream)
+    entry_t = lambda: _lib.call("az_op_coil_combine_f32", img.data_ptr(), img.data_ptr() + 4 * hw, 2 * hw, z.data_ptr(),  # noqa: E731
+                                z.data_ptr() + 4 * n, 2 * n, s_re.data_ptr(), s_im.data_ptr(), 0, B, K, hw, 0, stream)
+    forms = {"apply": (lambda: A(x), 200), "adjoint": (lambda: A.adjoint(z), 200), "entry_expand": (lambda: (entry(), coil)[1], 200),
+             "entry_combine": (lambda: (entry_t(), img)[1], 200), "torch_apply": (lambda: lam(x), 200),
+             "torch_adjoint": (lambda: lam_t(z), 200)}
+    s64 = maps.cuda()
+    c64 = s64 * torch.complex(x[:, 0].double(), x[:, 1].double())[:, None]
+    g64 = (s64.conj() * torch.complex(z[:, :K].double(), z[:, K:].double())).sum(1)
+    f64 = torch.fft.fft2(c64, norm="ortho")
+    zm = z.double() * md
+    a64 = (s64.conj() * torch.fft.ifft2(torch.complex(zm[:, :K], zm[:, K:]), norm="ortho")).sum(1)
+    refs = {"apply": torch.cat([f64.real, f64.imag], dim=1) * md, "adjoint": torch.stack([a64.real, a64.imag], dim=1),
+            "entry_expand": torch.cat([c64.real, c64.imag], dim=1), "entry_combine": torch.stack([g64.real, g64.imag], dim=1)}
+    refs["torch_apply"], refs["torch_adjoint"] = refs["apply"], refs["adjoint"]
+    err = {k: float((fn().double() - refs[k]).abs().max()) for k, (fn, _) in forms.items()}
+    times = measure(forms)
+    med = report(forms, times, err)
+    entry_floor = (8 + 16 * K) * B * hw / HBM
+    op_floor = entry_floor + ((24 if hw <= 8192 else 56) + 16) * B * n / HBM
+    print(f"{8 + 16 * K} B per pixel: {entry_floor * 1e6:.2f} us at {HBM / 1e12:.2f} TB/s -> expand runs at "
+          f"{entry_floor / med['entry_expand']:.1%} of the model, combine at {entry_floor / med['entry_combine']:.1%}")
+    print(f"operator (entry + FFT + mask): {op_floor * 1e6:.2f} us -> apply runs at {op_floor / med['apply']:.1%} of the model, adjoint "
+          f"at {op_floor / med['adjoint']:.1%}; {med['torch_apply'] / med['apply']:.2f} x and {med['torch_adjoint'] / med['adjoint']:.2f} "
+          "x the speed of the torch lambda")
+    print(json.dumps({"sense": [B, K, H, W], **{f"{k}_us": med[k] * 1e6 for k in forms},
+                      **{f"{k}_min_us": min(times[k]) * 1e6 for k in forms}, "entry_model_us": entry_floor * 1e6,
+                      "operator_model_us": op_floor * 1e6, "model_fraction_expand": entry_floor / med["entry_expand"],
+                      "model_fraction_combine": entry_floor / med["entry_combine"]}))
+
+
 def main() -> None:
     if not torch.cuda.is_available():
         raise SystemExit("time_operators.py measures on the GPU: no device visible")
     torch.manual_seed(0)
     if sys.argv[1:2] == ["radon"]:
         radon(sys.argv[2:7])
+    elif sys.argv[1:2] == ["sense"]:
+        sense(sys.argv[2:6])
     elif sys.argv[1:2] == ["psf"]:
         psf(sys.argv[2:7])
     elif sys.argv[1:2] == ["fft"]:
