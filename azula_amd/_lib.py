@@ -7,6 +7,7 @@ path of :mod:`azula_amd` goes through :func:`lib`, which raises if the shared ob
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -580,6 +581,16 @@ def stream_ptr(device: torch.device | None = None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+_NO_CONTEXT = contextlib.nullcontext()  # (stateless, so one serves every call)
+
+
+def device_context(x):
+    r"""The context that makes ``x``'s GPU the current device; nothing to do for a host tensor or on the current device."""
+    if torch.is_tensor(x) and x.is_cuda and x.device.index != torch.cuda.current_device():
+        return torch.cuda.device(x.device)
+    return _NO_CONTEXT
+
+
 def on_device(fn):
     r"""Method decorator: runs ``fn(self, x, ...)`` with ``x``'s GPU as the current device.  Kernels and graphs are
     launched on ``torch.cuda.current_stream()``, i.e. on the CURRENT device's stream; with the latent on ``cuda:1``
@@ -588,10 +599,8 @@ def on_device(fn):
 
     @functools.wraps(fn)
     def wrapped(self, x, *args, **kwargs):
-        if torch.is_tensor(x) and x.is_cuda and x.device.index != torch.cuda.current_device():
-            with torch.cuda.device(x.device):
-                return fn(self, x, *args, **kwargs)
-        return fn(self, x, *args, **kwargs)
+        with device_context(x):
+            return fn(self, x, *args, **kwargs)
 
     return wrapped
 

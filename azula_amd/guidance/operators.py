@@ -26,12 +26,20 @@ Two paths, as ``RePaintSampler`` has them:
   end in the same launches;
 * everything else (host tensors, fp64 and half tensors): a plain torch op sequence in the tensor's own dtype -- padding, slices,
   reshapes and elementwise ops -- which torch differentiates itself.
+
+How to add an operator: subclass :class:`LinearOperator` and state facts; the base class dispatches, differentiates, checks
+shapes and caches.  ``_out_shape`` / ``_in_shape_of`` give the observation's shape and back, and raise for what the operator
+cannot take.  ``_kernel(x, mode)`` is the map as launches through :func:`_launch`, ``_torch(x, mode)`` the same map as torch
+ops.  ``_TRANSPOSE`` lists every mode the two implement with the mode that is its transpose: ``backward`` looks it up.
+``_STRIDED = True`` sends strided fp32 device tensors to the kernels too (made contiguous first) where the torch path has no
+use for them, and ``_check_kernel_input`` refuses what the kernels cannot take.  Device constants come from ``_constant``; a
+public map of an observation (``pinv``, ``fbp``) is one call of ``_from_observation``.
 """
 
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
+import functools
 import math
 from collections.abc import Sequence
 
@@ -40,6 +48,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from .. import _lib
+from .._lib import device_context
 from .repaint import _aligned, _broadcasts_to
 
 __all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps", "PSFOperator", "motion_psf",
@@ -61,24 +70,35 @@ def _use_kernels(x: Tensor) -> bool:
     return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
 
 
-def _device_of(x: Tensor):
-    r"""The context ``_lib.on_device`` gives a method: launches go to the current device's stream, so ``x``'s is made current."""
-    if x.is_cuda and x.device.index != torch.cuda.current_device():
-        return torch.cuda.device(x.device)
-    return contextlib.nullcontext()
+def _to_kernels(x: Tensor, strided: bool) -> bool:
+    r"""Whether ``x`` goes to the kernels: a contiguous fp32 device tensor does, a strided one where the caller makes it
+    contiguous first."""
+    return _use_kernels(x) or (strided and x.is_cuda and x.dtype == torch.float32)
+
+
+_WITH_PINV = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv_t", "pinv_t": "pinv"}  # the _TRANSPOSE of a map with a pinv
+
+
+def _reciprocal_or_zero(t: Tensor) -> Tensor:
+    r"""``1 / t`` where ``t`` is nonzero, 0 elsewhere."""
+    return torch.where(t != 0, 1 / torch.where(t != 0, t, torch.ones_like(t)), torch.zeros_like(t))
 
 
 class _Apply(torch.autograd.Function):
-    r"""``op``'s map ``mode`` ("apply", "adjoint" or "pinv") on the kernels.
+    r"""``op``'s map ``mode``, a key of ``op._TRANSPOSE``: on the kernels for the tensors they take (made contiguous and aligned,
+    with ``x``'s device current), else as ``op._product``.
 
-    ``forward`` always receives plain tensors.  ``backward`` and ``jvp`` do NOT: under ``torch.func.jvp`` / ``vjp`` theirs are
-    functorch wrappers without storage, so neither may launch on what it receives.  Both are applications of this Function --
-    the tangent map of a linear map is the map, its pullback the transposed map -- which unwraps level by level down to
-    ``forward``."""
+    Two reasons for one shape.  ``forward`` always receives plain tensors; ``backward`` and ``jvp`` do NOT: under
+    ``torch.func.jvp`` / ``vjp`` theirs are functorch wrappers without storage, so neither may launch on what it receives.
+    And ``torch.sparse.mm``, of which :class:`RadonOperator`'s ``_product`` is made, has a backward but no forward-mode rule,
+    while ``MMPSDenoiser`` calls ``torch.func.jvp``.  So both are applications of this Function -- the tangent map of a linear
+    map is the map, its pullback the transposed map -- which unwraps level by level down to ``forward``."""
 
     @staticmethod
     def forward(x: Tensor, op: LinearOperator, mode: str) -> Tensor:
-        with _device_of(x):
+        if op._product is not None and not _to_kernels(x, True):  # (without a _product only the kernels' tensors come here)
+            return op._product(x, mode)
+        with device_context(x):
             return op._kernel(_aligned(x.contiguous(), 16), mode)
 
     @staticmethod
@@ -112,8 +132,12 @@ class LinearOperator:
         self.in_shape = None if in_shape is None else tuple(int(s) for s in in_shape)
         if self.in_shape is not None and len(self.in_shape) != 3:
             raise ValueError(f"in_shape is (C, H, W), got {self.in_shape}")
+        self._cache: dict = {}
 
     # -- what a subclass defines ----------------------------------------------------------------------------------------
+    _TRANSPOSE: dict[str, str] = {"apply": "adjoint", "adjoint": "apply"}  # every mode of _kernel / _torch -> its transpose
+    _STRIDED = False  # whether strided fp32 device tensors go to the kernels (else the torch path takes them without a copy)
+
     def _out_shape(self, in_shape: tuple) -> tuple:
         r"""(C', H', W') of the observation of a (C, H, W) input; raises ``ValueError`` for an input the operator cannot take."""
         return in_shape
@@ -130,15 +154,46 @@ class LinearOperator:
         r"""The same map as torch ops in ``x``'s dtype."""
         raise NotImplementedError
 
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        r"""The transpose of the map ``mode`` applied to ``g``, as applications of :class:`_Apply`."""
-        if mode == "pinv":
-            raise NotImplementedError(f"{type(self).__name__} has no pseudo-inverse")
-        return _Apply.apply(g, self, "adjoint" if mode == "apply" else "apply")
+    # ``_product(x, mode)``: the map for a tensor that enters :class:`_Apply` and is not the kernels'.  Only an operator whose
+    # ``_torch`` is an application of the Function has one.
+    _product = None
 
-    # -- the public maps ------------------------------------------------------------------------------------------------
+    def _check_kernel_input(self, x: Tensor) -> None:
+        r"""Raises for a tensor that is bound for the kernels and that they cannot take."""
+
+    # -- what the base class does with it -------------------------------------------------------------------------------
+    def _transposed(self, g: Tensor, mode: str) -> Tensor:
+        r"""The transpose of the map ``mode`` applied to ``g``, as an application of :class:`_Apply`."""
+        if mode not in self._TRANSPOSE:
+            raise NotImplementedError(f"{type(self).__name__} has no pseudo-inverse")
+        return _Apply.apply(g, self, self._TRANSPOSE[mode])
+
     def _run(self, x: Tensor, mode: str) -> Tensor:
-        return _Apply.apply(x, self, mode) if _use_kernels(x) else self._torch(x, mode)
+        r"""THE choice between the kernels and the torch path."""
+        if _to_kernels(x, self._STRIDED):
+            self._check_kernel_input(x)
+            return _Apply.apply(x, self, mode)
+        return self._torch(x, mode)
+
+    def _constant(self, x: Tensor, tag, make) -> Tensor | tuple:
+        r"""The constant ``make()``, a tensor or a tuple of tensors, in ``x``'s dtype on its device, contiguous and 16-byte
+        aligned: made and moved once per ``tag``, device and dtype."""
+        key = (tag, x.device, x.dtype)
+        c = self._cache.get(key)
+        if c is None:
+            def moved(t: Tensor) -> Tensor:
+                t = t.to(device=x.device, dtype=x.dtype)
+                return t if t.is_sparse else _aligned(t.contiguous(), 16)
+
+            c = make()
+            c = self._cache[key] = moved(c) if torch.is_tensor(c) else tuple(moved(t) for t in c)
+        return c
+
+    def _from_observation(self, y: Tensor, mode: str) -> Tensor:
+        r"""The map ``mode`` of an observation, flat or in its image shape: the body of the public method of that name."""
+        y = self._image(y, mode)
+        self._out_shape(self._in_shape_of(tuple(y.shape[1:])))
+        return self._run(y, mode)
 
     def _image(self, v: Tensor, what: str) -> Tensor:
         r"""An observation in its image shape: (B, C', H', W') as it is, (B, D) un-flattened with the recorded input shape."""
@@ -154,18 +209,18 @@ class LinearOperator:
             raise ValueError(f"{what}: {tuple(v.shape)} is not a flattened (B, {', '.join(map(str, out))}) observation")
         return v.unflatten(1, out)
 
+    # -- the public maps ------------------------------------------------------------------------------------------------
     def __call__(self, x: Tensor) -> Tensor:
         if x.ndim != 4:
             raise ValueError(f"{type(self).__name__} takes a (B, C, H, W) tensor, got {tuple(x.shape)}")
-        self._out_shape(tuple(x.shape[1:]))
-        self.in_shape = tuple(x.shape[1:])
+        in_shape = tuple(x.shape[1:])
+        self._out_shape(in_shape)
+        self.in_shape = in_shape
         y = self._run(x, "apply")
         return y.flatten(1) if self.flatten else y
 
     def adjoint(self, v: Tensor) -> Tensor:
-        v = self._image(v, "adjoint")
-        self._out_shape(self._in_shape_of(tuple(v.shape[1:])))
-        return self._run(v, "adjoint")
+        return self._from_observation(v, "adjoint")
 
     def pinv(self, y: Tensor) -> Tensor:
         raise NotImplementedError(f"{type(self).__name__} has no pseudo-inverse")
@@ -224,31 +279,29 @@ class MaskOperator(LinearOperator):
     and (where it has to be expanded) input shape: build a new operator for a new mask rather than editing ``mask`` in place.
     """
 
+    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv"}  # (diagonal maps: "adjoint" is "apply")
+
     def __init__(self, mask: Tensor, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
         if not torch.is_tensor(mask) or mask.ndim > 4:
             raise ValueError("mask is a tensor of at most 4 dimensions")
         self.mask = mask
-        self._cache: dict = {}
 
-    def _factor(self, x: Tensor, inverse: bool) -> Tensor:
-        r"""The factor in ``x``'s dtype, on ``x``'s device.  fp32 device tensors: contiguous and either a suffix of ``x``'s shape
-        (the kernel indexes it modulo its size) or expanded to ``x``'s shape; made once per device and shape."""
+    def _factor(self, x: Tensor, inverse: bool, kernels: bool) -> Tensor:
+        r"""The factor in ``x``'s dtype, on ``x``'s device.  For the kernels: either a suffix of ``x``'s shape (the kernel indexes
+        it modulo its size) or expanded to ``x``'s shape, then made once per shape as well."""
         core = tuple(self.mask.shape)
         while core and core[0] == 1:
             core = core[1:]
-        kernels = _use_kernels(x)
         suffix = core == tuple(x.shape[x.ndim - len(core):])
-        key = (x.device, x.dtype, inverse, kernels, tuple(x.shape) if kernels and not suffix else None)
-        m = self._cache.get(key)
-        if m is None:
-            m = self.mask.to(device=x.device, dtype=x.dtype)
+
+        def make() -> Tensor:
+            m = self.mask.to(device=x.device, dtype=x.dtype)  # (first: the reciprocal is taken in x's dtype)
             if inverse:
-                m = torch.where(m != 0, 1 / torch.where(m != 0, m, torch.ones_like(m)), torch.zeros_like(m))
-            if kernels:
-                m = _aligned((m.reshape(core) if suffix else m.expand(x.shape)).contiguous(), 16)
-            self._cache[key] = m
-        return m
+                m = _reciprocal_or_zero(m)
+            return (m.reshape(core) if suffix else m.expand(x.shape)) if kernels else m
+
+        return self._constant(x, ("factor", inverse, kernels, tuple(x.shape) if kernels and not suffix else None), make)
 
     def _out_shape(self, in_shape: tuple) -> tuple:
         if not _broadcasts_to(self.mask.shape[-3:], in_shape):  # (the batch dimension: _check_batch)
@@ -261,7 +314,7 @@ class MaskOperator(LinearOperator):
 
     def _kernel(self, x: Tensor, mode: str) -> Tensor:
         self._check_batch(x)
-        m = self._factor(x, mode == "pinv")
+        m = self._factor(x, mode == "pinv", True)
         y = torch.empty_like(x)
         if x.numel():
             _launch("az_op_mul_f32", y.data_ptr(), x.data_ptr(), m.data_ptr(), x.numel(), m.numel())
@@ -269,24 +322,43 @@ class MaskOperator(LinearOperator):
 
     def _torch(self, x: Tensor, mode: str) -> Tensor:
         self._check_batch(x)
-        return x * self._factor(x, mode == "pinv")
-
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        return _Apply.apply(g, self, mode if mode == "pinv" else "apply")  # (diagonal maps: each is its own transpose)
-
-    def adjoint(self, v: Tensor) -> Tensor:
-        v = self._image(v, "adjoint")
-        self._out_shape(tuple(v.shape[1:]))
-        return self._run(v, "apply")
+        return x * self._factor(x, mode == "pinv", False)
 
     def pinv(self, y: Tensor) -> Tensor:
-        y = self._image(y, "pinv")
-        self._out_shape(tuple(y.shape[1:]))
-        return self._run(y, "pinv")
+        return self._from_observation(y, "pinv")
 
 
 # ------------------------------------------------------------------------------------------------------------ downsample
-class DownsampleOperator(LinearOperator):
+def _pair(v, what: str) -> tuple:
+    pair = (v, v) if isinstance(v, int) else tuple(v) if isinstance(v, Sequence) else ()
+    if len(pair) != 2 or not all(isinstance(a, int) for a in pair):
+        raise ValueError(f"{what} is an int or a pair of ints, got {v}")
+    return pair
+
+
+class _SubsampleOperator(LinearOperator):
+    r"""What :class:`DownsampleOperator` and :class:`DecimateOperator` share: the factor and the two shapes."""
+
+    _NAME = ""  # (the operator's own word in the "multiples" message)
+
+    def __init__(self, factor: int | Sequence[int], flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        fh, fw = _pair(factor, "factor")
+        if not (1 <= fh <= MAX_FACTOR and 1 <= fw <= MAX_FACTOR):
+            raise ValueError(f"factor is an int or a pair of ints in 1 .. {MAX_FACTOR}, got {factor}")
+        self.factor = (fh, fw)
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        (c, h, w), (fh, fw) = in_shape, self.factor
+        if h % fh or w % fw:
+            raise ValueError(f"{self._NAME} by {self.factor} needs a height and width that are multiples of it, got {h} x {w}")
+        return (c, h // fh, w // fw)
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        return (out_shape[0], out_shape[1] * self.factor[0], out_shape[2] * self.factor[1])
+
+
+class DownsampleOperator(_SubsampleOperator):
     r"""Creates the average-pool downsampling by ``factor`` (super-resolution).
 
     Arguments:
@@ -296,29 +368,18 @@ class DownsampleOperator(LinearOperator):
     ``pinv`` is nearest up-sampling, :math:`f_h f_w` times the adjoint.
     """
 
-    def __init__(self, factor: int | Sequence[int], flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
-        super().__init__(flatten, in_shape)
-        fh, fw = (factor, factor) if isinstance(factor, int) else factor
-        if not (isinstance(fh, int) and isinstance(fw, int) and 1 <= fh <= MAX_FACTOR and 1 <= fw <= MAX_FACTOR):
-            raise ValueError(f"factor is an int or a pair of ints in 1 .. {MAX_FACTOR}, got {factor}")
-        self.factor = (fh, fw)
-
-    def _out_shape(self, in_shape: tuple) -> tuple:
-        (c, h, w), (fh, fw) = in_shape, self.factor
-        if h % fh or w % fw:
-            raise ValueError(f"downsampling by {self.factor} needs a height and width that are multiples of it, got {h} x {w}")
-        return (c, h // fh, w // fw)
-
-    def _in_shape_of(self, out_shape: tuple) -> tuple:
-        return (out_shape[0], out_shape[1] * self.factor[0], out_shape[2] * self.factor[1])
+    _NAME = "downsampling"
+    _TRANSPOSE = _WITH_PINV
 
     def _kernel(self, x: Tensor, mode: str) -> Tensor:
         (B, c, h, w), (fh, fw) = x.shape, self.factor
-        if mode == "apply":
+        if mode in ("apply", "pinv_t"):
             y = x.new_empty(B, c, h // fh, w // fw)
             if y.numel():
                 _launch("az_op_avgpool_f32", y.data_ptr(), x.data_ptr(), B * c, h, w, fh, fw)
-            return y
+            # "pinv_t" is (fh fw A^T)^T = fh fw A.  The entry has no scale argument, so the factor is a torch multiply and the
+            # launch sequence stays az_op_avgpool_f32 alone.
+            return y * float(fh * fw) if mode == "pinv_t" else y
         y = x.new_empty(B, c, h * fh, w * fw)
         if y.numel():
             scale = 1.0 if mode == "pinv" else 1.0 / (fh * fw)
@@ -327,24 +388,19 @@ class DownsampleOperator(LinearOperator):
 
     def _torch(self, x: Tensor, mode: str) -> Tensor:
         (B, c, h, w), (fh, fw) = x.shape, self.factor
-        if mode == "apply":
+        if mode in ("apply", "pinv_t"):
             win = x.reshape(B, c, h // fh, fh, w // fw, fw)
             acc = None
             for a in range(fh):  # (the kernel's order of summation)
                 for b in range(fw):
                     acc = win[:, :, :, a, :, b] if acc is None else acc + win[:, :, :, a, :, b]
-            return acc * (1.0 / (fh * fw))
+            y = acc * (1.0 / (fh * fw))
+            return y * float(fh * fw) if mode == "pinv_t" else y  # (as the kernel path: the apply map, then the factor)
         up = x[:, :, :, None, :, None].expand(B, c, h, fh, w, fw).reshape(B, c, h * fh, w * fw)
         return up if mode == "pinv" else up * (1.0 / (fh * fw))
 
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        if mode == "pinv":  # (fh fw A^T)^T
-            return _Apply.apply(g, self, "apply") * float(self.factor[0] * self.factor[1])
-        return super()._transposed(g, mode)
-
     def pinv(self, y: Tensor) -> Tensor:
-        y = self._image(y, "pinv")
-        return self._run(y, "pinv")
+        return self._from_observation(y, "pinv")
 
 
 # ------------------------------------------------------------------------------------------------------------------ blur
@@ -356,6 +412,23 @@ def gaussian_taps(sigma: float, size: int) -> Tensor:
     pos = torch.arange(size, dtype=torch.float64) - (size - 1) / 2
     k = torch.exp(-0.5 * (pos / sigma) ** 2)
     return (k / k.sum()).to(torch.float32)
+
+
+def _padding(padding: str) -> str:
+    if padding not in ("zeros", "circular"):
+        raise ValueError(f"padding is 'zeros' or 'circular', got {padding!r}")
+    return padding
+
+
+def _pad(x: Tensor, rh: int, rw: int, padding: str) -> Tensor:
+    r"""``x`` with ``rh`` rows and ``rw`` columns of ``padding`` on every side, for the torch paths."""
+    return F.pad(x, (rw, rw, rh, rh), mode="circular") if padding == "circular" else F.pad(x, (rw, rw, rh, rh))
+
+
+def _tile(entry: str, nh: int, nw: int) -> tuple[int, int]:
+    th, tw = C.c_int32(0), C.c_int32(0)
+    _lib.call(entry, nh, nw, C.byref(th), C.byref(tw))
+    return th.value, tw.value
 
 
 class BlurOperator(LinearOperator):
@@ -375,9 +448,7 @@ class BlurOperator(LinearOperator):
     def __init__(self, taps_h, taps_w=None, padding: str = "zeros", flatten: bool = False,
                  in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
-        if padding not in ("zeros", "circular"):
-            raise ValueError(f"padding is 'zeros' or 'circular', got {padding!r}")
-        self.padding = padding
+        self.padding = _padding(padding)
         taps = []
         for t in (taps_h, taps_h if taps_w is None else taps_w):
             t = torch.as_tensor(t).detach().to(device="cpu", dtype=torch.float32).contiguous()
@@ -385,7 +456,6 @@ class BlurOperator(LinearOperator):
                 raise ValueError(f"taps are 1-d vectors of an odd length of at most {MAX_TAPS}, got shape {tuple(t.shape)}")
             taps.append(t)
         self.taps_h, self.taps_w = taps
-        self._cache: dict = {}
 
     @classmethod
     def gaussian(cls, sigma: float, size: int, **kwargs) -> BlurOperator:
@@ -393,12 +463,8 @@ class BlurOperator(LinearOperator):
         return cls(gaussian_taps(sigma, size), **kwargs)
 
     def _taps(self, x: Tensor, mode: str) -> tuple[Tensor, Tensor]:
-        key = (x.device, x.dtype, mode)
-        t = self._cache.get(key)
-        if t is None:
-            hw = (self.taps_h, self.taps_w) if mode == "apply" else (self.taps_h.flip(0), self.taps_w.flip(0))
-            t = self._cache[key] = tuple(v.to(device=x.device, dtype=x.dtype).contiguous() for v in hw)
-        return t
+        hw = self.taps_h, self.taps_w
+        return self._constant(x, ("taps", mode), lambda: hw if mode == "apply" else tuple(t.flip(0) for t in hw))
 
     def _out_shape(self, in_shape: tuple) -> tuple:
         _, h, w = in_shape
@@ -419,8 +485,7 @@ class BlurOperator(LinearOperator):
     def _torch(self, x: Tensor, mode: str) -> Tensor:
         h, w = x.shape[2:]
         th, tw = self._taps(x, mode)
-        rh, rw = th.numel() // 2, tw.numel() // 2
-        xp = F.pad(x, (rw, rw, rh, rh), mode="circular") if self.padding == "circular" else F.pad(x, (rw, rw, rh, rh))
+        xp = _pad(x, th.numel() // 2, tw.numel() // 2, self.padding)
         rows = None
         for b in range(tw.numel()):  # (the kernel's two passes; torch rounds the product where the kernel fuses it)
             term = tw[b] * xp[:, :, :, b:b + w]
@@ -434,9 +499,7 @@ class BlurOperator(LinearOperator):
 
 def blur_tile(nh: int, nw: int) -> tuple[int, int]:
     r"""The output tile (rows, columns) of one workgroup of ``az_op_blur_f32`` for these tap counts."""
-    th, tw = C.c_int32(0), C.c_int32(0)
-    _lib.call("az_op_blur_tile", nh, nw, C.byref(th), C.byref(tw))
-    return th.value, tw.value
+    return _tile("az_op_blur_tile", nh, nw)
 
 
 # ------------------------------------------------------------------------------------------------------------------- PSF
@@ -483,23 +546,15 @@ class PSFOperator(LinearOperator):
 
     def __init__(self, psf: Tensor, padding: str = "zeros", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
-        if padding not in ("zeros", "circular"):
-            raise ValueError(f"padding is 'zeros' or 'circular', got {padding!r}")
-        self.padding = padding
+        self.padding = _padding(padding)
         k = torch.as_tensor(psf).detach().to(device="cpu", dtype=torch.float32)
         if k.ndim not in (2, 3, 4) or k.shape[-2] % 2 == 0 or k.shape[-1] % 2 == 0 or max(k.shape[-2:]) > MAX_TAPS or k.numel() == 0:
             raise ValueError("psf is (kh, kw), (C, kh, kw), (B, 1, kh, kw) or (B, C, kh, kw) with odd kh, kw of at most "
                              f"{MAX_TAPS}, got shape {tuple(k.shape)}")
         self.psf = k.reshape((1,) * (4 - k.ndim) + tuple(k.shape)).contiguous()  # (Bp, Cp, kh, kw)
-        self._cache: dict = {}
 
     def _taps(self, x: Tensor, mode: str) -> Tensor:
-        key = (x.device, x.dtype, mode)
-        k = self._cache.get(key)
-        if k is None:
-            k = self.psf if mode == "apply" else self.psf.flip(2, 3)
-            k = self._cache[key] = k.to(device=x.device, dtype=x.dtype).contiguous()
-        return k
+        return self._constant(x, ("taps", mode), lambda: self.psf if mode == "apply" else self.psf.flip(2, 3))
 
     def _out_shape(self, in_shape: tuple) -> tuple:
         c, h, w = in_shape
@@ -530,8 +585,7 @@ class PSFOperator(LinearOperator):
         h, w = x.shape[2:]
         k = self._taps(x, mode)
         kh, kw = k.shape[2:]
-        rh, rw = kh // 2, kw // 2
-        xp = F.pad(x, (rw, rw, rh, rh), mode="circular") if self.padding == "circular" else F.pad(x, (rw, rw, rh, rh))
+        xp = _pad(x, kh // 2, kw // 2, self.padding)
         out = None
         for a in range(kh):  # (the kernel's order; torch rounds the product where the kernel fuses it)
             for b in range(kw):
@@ -542,9 +596,7 @@ class PSFOperator(LinearOperator):
 
 def psf_tile(kh: int, kw: int) -> tuple[int, int]:
     r"""The output tile (rows, columns) of one workgroup of ``az_op_psf_f32`` for this PSF size."""
-    th, tw = C.c_int32(0), C.c_int32(0)
-    _lib.call("az_op_psf_tile", kh, kw, C.byref(th), C.byref(tw))
-    return th.value, tw.value
+    return _tile("az_op_psf_tile", kh, kw)
 
 
 # ------------------------------------------------------------------------------------------------------------- decimation
@@ -561,14 +613,7 @@ def bicubic_taps(factor: int) -> Tensor:
     return (k / k.sum()).to(torch.float32)
 
 
-def _pair(v, what: str) -> tuple:
-    pair = (v, v) if isinstance(v, int) else tuple(v) if isinstance(v, Sequence) else ()
-    if len(pair) != 2 or not all(isinstance(a, int) for a in pair):
-        raise ValueError(f"{what} is an int or a pair of ints, got {v}")
-    return pair
-
-
-class DecimateOperator(LinearOperator):
+class DecimateOperator(_SubsampleOperator):
     r"""Creates the decimation :math:`y_{ij} = x_{i f_h + o_h, j f_w + o_w}`: keep every ``factor``-th pixel, starting at
     ``offset`` (where :class:`DownsampleOperator` averages each window).
 
@@ -584,25 +629,15 @@ class DecimateOperator(LinearOperator):
     blur is not provided.
     """
 
+    _NAME = "decimation"
+
     def __init__(self, factor: int | Sequence[int], offset: int | Sequence[int] = 0, flatten: bool = False,
                  in_shape: Sequence[int] | None = None) -> None:
-        super().__init__(flatten, in_shape)
-        fh, fw = _pair(factor, "factor")
+        super().__init__(factor, flatten, in_shape)
         oh, ow = _pair(offset, "offset")
-        if not (1 <= fh <= MAX_FACTOR and 1 <= fw <= MAX_FACTOR):
-            raise ValueError(f"factor is an int or a pair of ints in 1 .. {MAX_FACTOR}, got {factor}")
-        if not (0 <= oh < fh and 0 <= ow < fw):
+        if not (0 <= oh < self.factor[0] and 0 <= ow < self.factor[1]):
             raise ValueError(f"offset is an int or a pair of ints with 0 <= offset < factor, got {offset} for factor {factor}")
-        self.factor, self.offset = (fh, fw), (oh, ow)
-
-    def _out_shape(self, in_shape: tuple) -> tuple:
-        (c, h, w), (fh, fw) = in_shape, self.factor
-        if h % fh or w % fw:
-            raise ValueError(f"decimation by {self.factor} needs a height and width that are multiples of it, got {h} x {w}")
-        return (c, h // fh, w // fw)
-
-    def _in_shape_of(self, out_shape: tuple) -> tuple:
-        return (out_shape[0], out_shape[1] * self.factor[0], out_shape[2] * self.factor[1])
+        self.offset = (oh, ow)
 
     def _kernel(self, x: Tensor, mode: str) -> Tensor:
         (B, c, h, w), (fh, fw), (oh, ow) = x.shape, self.factor, self.offset
@@ -639,7 +674,7 @@ class ChannelMixOperator(LinearOperator):
     ``pinv`` mixes with :math:`M^+`, ``torch.linalg.pinv`` of the matrix in fp64, computed once on the host.
     """
 
-    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv_t", "pinv_t": "pinv"}
+    _TRANSPOSE = _WITH_PINV
 
     def __init__(self, matrix, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
@@ -647,7 +682,6 @@ class ChannelMixOperator(LinearOperator):
         if m.ndim != 2 or not (1 <= m.shape[0] <= MAX_CHANNELS and 1 <= m.shape[1] <= MAX_CHANNELS):
             raise ValueError(f"matrix is (Cout, Cin) with 1 .. {MAX_CHANNELS} channels each, got shape {tuple(m.shape)}")
         self.matrix = m.contiguous()
-        self._cache: dict = {}
 
     @classmethod
     def grayscale(cls, weights: Sequence[float] = (1 / 3, 1 / 3, 1 / 3), **kwargs) -> ChannelMixOperator:
@@ -655,13 +689,11 @@ class ChannelMixOperator(LinearOperator):
         return cls(torch.tensor([list(weights)], dtype=torch.float64), **kwargs)
 
     def _matrix(self, x: Tensor, mode: str) -> Tensor:
-        key = (x.device, x.dtype, mode)
-        m = self._cache.get(key)
-        if m is None:
+        def make() -> Tensor:
             m = self.matrix if mode in ("apply", "adjoint") else torch.linalg.pinv(self.matrix).T  # M or (M^+)^T: (Cout, Cin)
-            m = m.T if mode in ("adjoint", "pinv") else m
-            m = self._cache[key] = m.to(device=x.device, dtype=x.dtype).contiguous()
-        return m
+            return m.T if mode in ("adjoint", "pinv") else m
+
+        return self._constant(x, ("matrix", mode), make)
 
     def _out_shape(self, in_shape: tuple) -> tuple:
         if in_shape[0] != self.matrix.shape[1]:
@@ -692,18 +724,64 @@ class ChannelMixOperator(LinearOperator):
             rows.append(acc)
         return torch.stack(rows, dim=1)
 
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        return _Apply.apply(g, self, self._TRANSPOSE[mode])
-
     def pinv(self, y: Tensor) -> Tensor:
-        y = self._image(y, "pinv")
-        self._in_shape_of(tuple(y.shape[1:]))
-        return self._run(y, "pinv")
+        return self._from_observation(y, "pinv")
 
 
 # --------------------------------------------------------------------------------------------------------------- Fourier
 def _fft_kernel_size(n: int) -> bool:
     return 1 <= n <= MAX_FFT and n & (n - 1) == 0
+
+
+def _check_fft_input(op: LinearOperator, x: Tensor) -> None:
+    r"""``_check_kernel_input`` of the operators on ``az_op_fft2_f32``."""
+    h, w = x.shape[2:]
+    if not (_fft_kernel_size(h) and _fft_kernel_size(w)):
+        raise NotImplementedError(f"{type(op).__name__} on an fp32 device tensor needs a height and width that are powers of two "
+                                  f"of at most {MAX_FFT}, got {h} x {w}; host and fp64 tensors take any size")
+
+
+# Planes as ``az_op_fft2_f32`` and the coil entries receive them are a triple (re pointer, im pointer, floats from one sample to the
+# next); real planes have the im pointer ``None``.  A split-complex (B, 2 C, H, W) buffer is (tensors, planes): the two halves of
+# ONE tensor where both start 16-byte aligned, else two tensors of (B, C, H, W).  Plain tuples, unpacked into names where they are
+# made: the host side of a call costs as much time as its launch, and a class instance per buffer adds a tenth to it.
+def _halves_aligned(n: int) -> bool:
+    return n % 4 == 0  # (n = C H W floats per half and sample)
+
+
+def _split_empty(x: Tensor, B: int, c: int, h: int, w: int) -> tuple[tuple, tuple]:
+    r"""An uninitialised split-complex (B, 2 c, h, w) buffer like ``x``: (tensors, planes)."""
+    n = c * h * w
+    if _halves_aligned(n):
+        whole = _aligned(x.new_empty(B, 2 * c, h, w), 16)
+        return (whole,), (whole.data_ptr(), whole.data_ptr() + 4 * n, 2 * n)
+    re, im = _aligned(x.new_empty(B, c, h, w), 16), _aligned(x.new_empty(B, c, h, w), 16)
+    return (re, im), (re.data_ptr(), im.data_ptr(), n)
+
+
+def _split_of(v: Tensor, c: int, n: int) -> tuple[tuple, tuple]:
+    r"""The contiguous, aligned (B, 2 c, h, w) tensor ``v``, ``n = c h w``, as a split-complex buffer, (tensors, planes): in
+    place, or its halves copied."""
+    if _halves_aligned(n):
+        return (v,), (v.data_ptr(), v.data_ptr() + 4 * n, 2 * n)
+    re, im = _aligned(v[:, :c].contiguous(), 16), _aligned(v[:, c:].contiguous(), 16)
+    return (re, im), (re.data_ptr(), im.data_ptr(), n)
+
+
+def _whole(tensors: tuple) -> Tensor:
+    r"""The (B, 2 C, H, W) tensor of a split-complex buffer's tensors."""
+    return tensors[0] if len(tensors) == 1 else _aligned(torch.cat(tensors, dim=1), 16)
+
+
+def _fft2(dst: tuple, src: tuple, like: Tensor, B: int, c: int, h: int, w: int, inverse: int, scale: float) -> None:
+    r"""One ``az_op_fft2_f32`` launch on ``B c`` planes from the planes ``src`` to the planes ``dst``.  Real ``dst`` planes (the real
+    part of an inverse transform) need scratch: ``az_op_fft2_work`` says how much, and it is made like ``like``."""
+    work = None
+    if dst[1] is None:
+        floats = C.c_int64(0)
+        _lib.call("az_op_fft2_work", B, c, h, w, C.byref(floats))
+        work = _aligned(like.new_empty(floats.value), 16) if floats.value else None
+    _launch("az_op_fft2_f32", *dst, *src, None if work is None else work.data_ptr(), B, c, h, w, inverse, scale)
 
 
 class FourierOperator(LinearOperator):
@@ -730,7 +808,9 @@ class FourierOperator(LinearOperator):
     an FFT-based ``pinv`` for the circular :class:`BlurOperator`.  Coil sensitivity maps: :class:`MultiCoilMRIOperator`.
     """
 
-    _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "pinv": "pinv_t", "pinv_t": "pinv"}
+    _TRANSPOSE = _WITH_PINV
+    _STRIDED = True  # (a strided view too: the Function makes it contiguous)
+    _check_kernel_input = _check_fft_input
 
     def __init__(self, norm: str = "ortho", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
@@ -758,32 +838,15 @@ class FourierOperator(LinearOperator):
         B, c, h, w = x.shape
         scale = self._scale(h * w, mode)
         if mode in ("apply", "pinv_t"):  # real -> split complex
-            n = c * h * w
-            if n % 4 == 0:  # (both halves of y start 16-byte aligned)
-                y = _aligned(x.new_empty(B, 2 * c, h, w), 16)
-                if y.numel():
-                    _launch("az_op_fft2_f32", y.data_ptr(), y.data_ptr() + 4 * n, 2 * n, x.data_ptr(), None, n, None, B, c, h, w, 0,
-                            scale)
-                return y
-            re, im = _aligned(torch.empty_like(x), 16), _aligned(torch.empty_like(x), 16)
+            y, y_planes = _split_empty(x, B, c, h, w)
             if x.numel():
-                _launch("az_op_fft2_f32", re.data_ptr(), im.data_ptr(), n, x.data_ptr(), None, n, None, B, c, h, w, 0, scale)
-            return torch.cat([re, im], dim=1)
+                _fft2(y_planes, (x.data_ptr(), None, c * h * w), x, B, c, h, w, 0, scale)
+            return _whole(y)
         c //= 2  # split complex -> real: the inverse transform's real part
-        n = c * h * w
         y = _aligned(x.new_empty(B, c, h, w), 16)
-        if not y.numel():
-            return y
-        floats = C.c_int64(0)
-        _lib.call("az_op_fft2_work", B, c, h, w, C.byref(floats))
-        work = _aligned(x.new_empty(floats.value), 16) if floats.value else None
-        if n % 4 == 0:
-            re_ptr, im_ptr, stride = x.data_ptr(), x.data_ptr() + 4 * n, 2 * n
-        else:
-            re, im = _aligned(x[:, :c].contiguous(), 16), _aligned(x[:, c:].contiguous(), 16)
-            re_ptr, im_ptr, stride = re.data_ptr(), im.data_ptr(), n
-        _launch("az_op_fft2_f32", y.data_ptr(), None, n, re_ptr, im_ptr, stride, None if work is None else work.data_ptr(), B, c, h,
-                w, 1, scale)
+        if y.numel():
+            z, z_planes = _split_of(x, c, c * h * w)  # (z: the halves stay alive until the launch is queued)
+            _fft2((y.data_ptr(), None, c * h * w), z_planes, x, B, c, h, w, 1, scale)
         return y
 
     def _torch(self, x: Tensor, mode: str) -> Tensor:
@@ -797,22 +860,8 @@ class FourierOperator(LinearOperator):
         c = x.shape[1] // 2
         return torch.fft.ifft2(torch.complex(x[:, :c], x[:, c:]), norm="forward").real * scale  # ("forward": unscaled inverse)
 
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        return _Apply.apply(g, self, self._TRANSPOSE[mode])
-
-    def _run(self, x: Tensor, mode: str) -> Tensor:
-        if _use_kernels(x) or (x.is_cuda and x.dtype == torch.float32):  # (a strided view too: the Function makes it contiguous)
-            h, w = x.shape[2:]
-            if not (_fft_kernel_size(h) and _fft_kernel_size(w)):
-                raise NotImplementedError(f"FourierOperator on an fp32 device tensor needs a height and width that are powers of "
-                                          f"two of at most {MAX_FFT}, got {h} x {w}; host and fp64 tensors take any size")
-            return _Apply.apply(x, self, mode)
-        return self._torch(x, mode)
-
     def pinv(self, y: Tensor) -> Tensor:
-        y = self._image(y, "pinv")
-        self._in_shape_of(tuple(y.shape[1:]))
-        return self._run(y, "pinv")
+        return self._from_observation(y, "pinv")
 
 
 def cartesian_mask(H: int, W: int, acceleration: float, center_fraction: float = 0.08, seed: int = 0) -> Tensor:
@@ -883,6 +932,8 @@ class MRIOperator(LinearOperator):
     Out of scope: see :class:`FourierOperator`.  Complex images and coil sensitivity maps: :class:`MultiCoilMRIOperator`.
     """
 
+    _TRANSPOSE = _WITH_PINV  # (the modes of _run: the composition has no _kernel / _torch of its own)
+
     def __init__(self, mask: Tensor, norm: str = "ortho", flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
         super().__init__(flatten, in_shape)
         self.fourier = FourierOperator(norm)
@@ -901,17 +952,18 @@ class MRIOperator(LinearOperator):
         return self.fourier._in_shape_of(self.sampling._out_shape(out_shape))
 
     def _run(self, x: Tensor, mode: str) -> Tensor:
-        if mode == "apply":
-            return self.sampling._run(self.fourier._run(x, "apply"), "apply")
-        return self.fourier._run(self.sampling._run(x, "pinv" if mode == "pinv" else "apply"), mode)
+        r"""No dispatch of its own: the two operators' ``_run``, each with its own choice.  "pinv_t" completes the table and is
+        reached by direct calls only: a gradient runs through the two operators' own Functions."""
+        factor = "pinv" if mode in ("pinv", "pinv_t") else "apply"
+        if mode in ("apply", "pinv_t"):
+            return self.sampling._run(self.fourier._run(x, mode), factor)
+        return self.fourier._run(self.sampling._run(x, factor), mode)
 
     def pinv(self, y: Tensor) -> Tensor:
         if not self.symmetric:
             raise NotImplementedError("MRIOperator.pinv is the Moore-Penrose inverse only for a mask that is symmetric under "
                                       "k -> -k mod (H, W): F F^+ does not commute with this one")
-        y = self._image(y, "pinv")
-        self._in_shape_of(tuple(y.shape[1:]))
-        return self._run(y, "pinv")
+        return self._from_observation(y, "pinv")
 
 
 # ------------------------------------------------------------------------------------------------------------ multi-coil
@@ -970,6 +1022,8 @@ class MultiCoilMRIOperator(LinearOperator):
     """
 
     _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "zero_filled": "zero_filled_t", "zero_filled_t": "zero_filled"}
+    _STRIDED = True  # (a strided view too: the Function makes it contiguous)
+    _check_kernel_input = _check_fft_input
 
     def __init__(self, mask: Tensor, maps: Tensor, norm: str = "ortho", complex_image: bool = True, flatten: bool = False,
                  in_shape: Sequence[int] | None = None) -> None:
@@ -987,7 +1041,6 @@ class MultiCoilMRIOperator(LinearOperator):
             raise ValueError("maps has a non-finite value")
         self.maps_re, self.maps_im = maps.real.contiguous(), maps.imag.contiguous()  # fp64 split planes
         self.complex_image = bool(complex_image)
-        self._cache: dict = {}
 
     @property
     def mask(self) -> Tensor:
@@ -1036,48 +1089,34 @@ class MultiCoilMRIOperator(LinearOperator):
 
     def _maps(self, x: Tensor, normalized: bool) -> tuple[Tensor, Tensor]:
         r"""(re, im) of :math:`S`, or of :math:`S / \sum_k |S_k|^2` (0 where that is 0), in ``x``'s dtype on its device."""
-        key = (x.device, x.dtype, normalized)
-        m = self._cache.get(key)
-        if m is None:
+        def make() -> tuple[Tensor, Tensor]:
             re, im = self.maps_re, self.maps_im
             if normalized:
-                D = (re * re + im * im).sum(-3, keepdim=True)
-                inv = torch.where(D != 0, 1 / torch.where(D != 0, D, torch.ones_like(D)), torch.zeros_like(D))
+                inv = _reciprocal_or_zero((re * re + im * im).sum(-3, keepdim=True))
                 re, im = re * inv, im * inv
-            m = self._cache[key] = tuple(_aligned(v.to(device=x.device, dtype=x.dtype).contiguous(), 16) for v in (re, im))
-        return m
+            return re, im
+
+        return self._constant(x, ("maps", normalized), make)
 
     # -- the kernels ----------------------------------------------------------------------------------------------------
-    def _coil_buffers(self, x: Tensor, B: int, K: int, h: int, w: int) -> tuple[Tensor | None, Tensor, Tensor, int]:
-        r"""A split-complex (B, 2 K, h, w) buffer as (whole, re, im, sample stride): the halves of one tensor where both start
-        16-byte aligned (K h w % 4 == 0), else two tensors."""
-        n = K * h * w
-        if n % 4 == 0:
-            whole = _aligned(x.new_empty(B, 2 * K, h, w), 16)
-            return whole, whole[:, :K], whole[:, K:], 2 * n
-        return None, _aligned(x.new_empty(B, K, h, w), 16), _aligned(x.new_empty(B, K, h, w), 16), n
-
     def _kernel(self, x: Tensor, mode: str) -> Tensor:
         self._check_batch(x)
         B, _, h, w = x.shape
         K, hw = self.coils, h * w
-        n = K * hw
         s_re, s_im = self._maps(x, mode == "zero_filled_t")
-        s_bs = n if s_re.ndim == 4 else 0
+        maps = s_re.data_ptr(), s_im.data_ptr(), K * hw if s_re.ndim == 4 else 0  # (re, im, sample stride)
         c = 2 if self.complex_image else 1
         if mode in ("apply", "zero_filled_t"):  # image -> coil images -> k-space -> mask
             if not x.numel():
                 return x.new_empty(B, 2 * K, h, w)
-            _, c_re, c_im, c_bs = self._coil_buffers(x, B, K, h, w)
-            _launch("az_op_coil_expand_f32", c_re.data_ptr(), c_im.data_ptr(), c_bs, x.data_ptr(),
-                    x.data_ptr() + 4 * hw if c == 2 else None, c * hw, s_re.data_ptr(), s_im.data_ptr(), s_bs, B, K, hw)
-            y, y_re, y_im, y_bs = self._coil_buffers(x, B, K, h, w)
-            _launch("az_op_fft2_f32", y_re.data_ptr(), y_im.data_ptr(), y_bs, c_re.data_ptr(), c_im.data_ptr(), c_bs, None, B, K, h,
-                    w, 0, self.fourier._scale(hw, "apply" if mode == "apply" else "pinv_t"))
-            if y is None:
-                y = _aligned(torch.cat([y_re, y_im], dim=1), 16)
+            coil, coil_planes = _split_empty(x, B, K, h, w)
+            _launch("az_op_coil_expand_f32", *coil_planes, x.data_ptr(), x.data_ptr() + 4 * hw if c == 2 else None, c * hw, *maps, B, K,
+                    hw)
+            k, k_planes = _split_empty(x, B, K, h, w)
+            _fft2(k_planes, coil_planes, x, B, K, h, w, 0, self.fourier._scale(hw, "apply" if mode == "apply" else "pinv_t"))
+            y = _whole(k)
             self._check_mask_batch(y)
-            m = self.sampling._factor(y, mode == "zero_filled_t")
+            m = self.sampling._factor(y, mode == "zero_filled_t", True)
             _launch("az_op_mul_f32", y.data_ptr(), y.data_ptr(), m.data_ptr(), y.numel(), m.numel())  # (in place: y is ours)
             return y
         # k-space -> mask -> coil images -> image
@@ -1085,23 +1124,14 @@ class MultiCoilMRIOperator(LinearOperator):
         if not out.numel():
             return out
         self._check_mask_batch(x)
-        m = self.sampling._factor(x, mode == "zero_filled")
+        m = self.sampling._factor(x, mode == "zero_filled", True)
         v = _aligned(torch.empty_like(x), 16)
         _launch("az_op_mul_f32", v.data_ptr(), x.data_ptr(), m.data_ptr(), x.numel(), m.numel())
-        if n % 4 == 0:
-            v_re, v_im, v_bs = v.data_ptr(), v.data_ptr() + 4 * n, 2 * n
-        else:
-            halves = _aligned(v[:, :K].contiguous(), 16), _aligned(v[:, K:].contiguous(), 16)
-            v_re, v_im, v_bs = halves[0].data_ptr(), halves[1].data_ptr(), n
-        _, c_re, c_im, c_bs = self._coil_buffers(x, B, K, h, w)
-        _launch("az_op_fft2_f32", c_re.data_ptr(), c_im.data_ptr(), c_bs, v_re, v_im, v_bs, None, B, K, h, w, 1,
-                self.fourier._scale(hw, "adjoint" if mode == "adjoint" else "pinv"))
-        _launch("az_op_coil_combine_f32", out.data_ptr(), out.data_ptr() + 4 * hw if c == 2 else None, c * hw, c_re.data_ptr(),
-                c_im.data_ptr(), c_bs, s_re.data_ptr(), s_im.data_ptr(), s_bs, B, K, hw, int(mode == "zero_filled"))
+        (k, k_planes), (coil, coil_planes) = _split_of(v, K, K * hw), _split_empty(x, B, K, h, w)
+        _fft2(coil_planes, k_planes, x, B, K, h, w, 1, self.fourier._scale(hw, "adjoint" if mode == "adjoint" else "pinv"))
+        _launch("az_op_coil_combine_f32", out.data_ptr(), out.data_ptr() + 4 * hw if c == 2 else None, c * hw, *coil_planes, *maps,
+                B, K, hw, int(mode == "zero_filled"))
         return out
-
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        return _Apply.apply(g, self, self._TRANSPOSE[mode])
 
     # -- the torch path -------------------------------------------------------------------------------------------------
     def _torch(self, x: Tensor, mode: str) -> Tensor:
@@ -1124,15 +1154,6 @@ class MultiCoilMRIOperator(LinearOperator):
             img = torch.where(D != 0, img / torch.where(D != 0, D, torch.ones_like(D)), torch.zeros_like(img))
         return torch.cat([img.real, img.imag], dim=1) if self.complex_image else img.real
 
-    def _run(self, x: Tensor, mode: str) -> Tensor:
-        if _use_kernels(x) or (x.is_cuda and x.dtype == torch.float32):  # (a strided view too: the Function makes it contiguous)
-            h, w = x.shape[2:]
-            if not (_fft_kernel_size(h) and _fft_kernel_size(w)):
-                raise NotImplementedError(f"MultiCoilMRIOperator on an fp32 device tensor needs a height and width that are powers "
-                                          f"of two of at most {MAX_FFT}, got {h} x {w}; host and fp64 tensors take any size")
-            return _Apply.apply(x, self, mode)
-        return self._torch(x, mode)
-
     # -- the public maps ------------------------------------------------------------------------------------------------
     def pinv(self, y: Tensor) -> Tensor:
         raise NotImplementedError("MultiCoilMRIOperator has no closed-form pseudo-inverse under undersampling; zero_filled is the "
@@ -1142,9 +1163,7 @@ class MultiCoilMRIOperator(LinearOperator):
     def zero_filled(self, y: Tensor) -> Tensor:
         r"""The coil-combined zero-filled reconstruction of a :math:`(B, 2 K, H, W)` or flat observation:
         :math:`\sum_k \bar S_k \odot F^+ M^+ y_k \,/\, \sum_k |S_k|^2`."""
-        y = self._image(y, "zero_filled")
-        self._out_shape(self._in_shape_of(tuple(y.shape[1:])))
-        return self._run(y, "zero_filled")
+        return self._from_observation(y, "zero_filled")
 
 
 # ----------------------------------------------------------------------------------------------------------------- Radon
@@ -1172,28 +1191,6 @@ def _cos_sin_degrees(deg: float) -> tuple[float, float]:
     for _ in range(int(q) % 4):
         c, s = -s, c
     return c + 0.0, s + 0.0  # (+ 0.0: no negative zero)
-
-
-class _ApplyMatrix(torch.autograd.Function):
-    r"""``op``'s map ``mode`` as products with its sparse matrix, for the tensors the kernels do not take.  ``torch.sparse.mm``
-    has a backward but no forward-mode rule, and ``MMPSDenoiser`` calls ``torch.func.jvp``; the map is linear, so -- as for
-    :class:`_Apply` -- ``backward`` and ``jvp`` are applications of this Function."""
-
-    @staticmethod
-    def forward(x: Tensor, op: RadonOperator, mode: str) -> Tensor:
-        return op._product(x, mode)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output) -> None:
-        _, ctx.op, ctx.mode = inputs
-
-    @staticmethod
-    def backward(ctx, g: Tensor):
-        return _ApplyMatrix.apply(g, ctx.op, ctx.op._TRANSPOSE[ctx.mode]), None, None
-
-    @staticmethod
-    def jvp(ctx, tx: Tensor, *_):
-        return _ApplyMatrix.apply(tx, ctx.op, ctx.mode)
 
 
 class RadonOperator(LinearOperator):
@@ -1228,14 +1225,15 @@ class RadonOperator(LinearOperator):
     Every fp32 device tensor takes the kernels (made contiguous and aligned first).  Host and fp64 tensors take products with the
     sparse matrix of the same fp32 weights, cast to the tensor's dtype and built once per device and dtype; half tensors take
     the fp32 product and round its result (``torch.sparse.mm`` has no half-precision form on the device).  ``torch.sparse.mm``
-    has no forward-mode rule either, so that path is an ``autograd.Function`` of its own whose ``backward`` and ``jvp`` are
-    products with the same matrices.
+    has no forward-mode rule either, so that path goes through the same ``autograd.Function`` as the kernels: its ``backward``
+    and ``jvp`` are products with the same matrices.
 
     Out of scope: fan-beam and cone-beam geometry, ray-driven (Siddon, Joseph) weights, :math:`d < 1`, other filters, a
     pseudo-inverse, half-precision kernels, 3-D.
     """
 
     _TRANSPOSE = {"apply": "adjoint", "adjoint": "apply", "fbp": "fbp_t", "fbp_t": "fbp"}
+    _STRIDED = True  # (a strided view too: the Function makes it contiguous)
 
     def __init__(self, theta, size: Sequence[int], det_count: int | None = None, det_spacing: float = 1.0,
                  flatten: bool = False) -> None:
@@ -1261,7 +1259,6 @@ class RadonOperator(LinearOperator):
         taps[1::2] = -1.0 / (math.pi * n[1::2] * d) ** 2
         self.taps = taps.to(torch.float32)
         self.fbp_scale = float(torch.tensor(math.pi / theta.numel(), dtype=torch.float32))  # (pi / A as the kernel receives it)
-        self._cache: dict = {}
 
     @property
     def angles(self) -> int:
@@ -1289,12 +1286,8 @@ class RadonOperator(LinearOperator):
 
     # -- the kernels ----------------------------------------------------------------------------------------------------
     def _on(self, x: Tensor, what: str) -> Tensor:
-        r"""The angle table or the filter taps on ``x``'s device, uploaded once."""
-        key = (what, x.device)
-        t = self._cache.get(key)
-        if t is None:
-            t = self._cache[key] = (self.table if what == "table" else self.taps).to(x.device).contiguous()
-        return t
+        r"""The angle table ("table") or the filter taps ("taps") on ``x``'s device, uploaded once."""
+        return self._constant(x, what, lambda: getattr(self, what))
 
     def _project(self, x: Tensor) -> Tensor:
         (B, c, H, W), A, D = x.shape, self.angles, self.det_count
@@ -1332,46 +1325,40 @@ class RadonOperator(LinearOperator):
             return self._backproject(self._filter(x, 1.0), scale)
         return self._filter(self._project(x), scale)  # "fbp_t": the filter is symmetric Toeplitz, so (A^T F)^T = F A
 
-    def _transposed(self, g: Tensor, mode: str) -> Tensor:
-        return _Apply.apply(g, self, self._TRANSPOSE[mode])
-
     # -- the torch path -------------------------------------------------------------------------------------------------
+    @functools.cached_property
     def _weights(self) -> tuple[Tensor, Tensor, Tensor]:
         r"""The nonzero weights as (row a D + k, column i W + j, fp32 value): the kernels' arithmetic, one rounded operation at
         a time, on the bins floor(p) and floor(p) + 1 -- all that can have a weight."""
-        w = self._cache.get("weights")
-        if w is None:
-            (H, W), D, f = self.size, self.det_count, torch.float32
-            x = (torch.arange(W, dtype=f) - (W - 1) / 2)[None, :]
-            y = (torch.arange(H, dtype=f) - (H - 1) / 2)[:, None]
-            inv, off = torch.tensor(1.0 / self.det_spacing, dtype=f), torch.tensor((D - 1) / 2, dtype=f)
-            rows, cols, vals = [], [], []
-            for a in range(self.angles):
-                p = ((x * self.table[a, 0] + y * self.table[a, 1]) * inv + off).reshape(-1)  # (eager fp32 ops: nothing is fused)
-                k0 = p.floor()
-                for k in (k0, k0 + 1):
-                    wk = (1 - (p - k).abs()).clamp_min(0)
-                    keep = ((k >= 0) & (k < D) & (wk > 0)).nonzero()[:, 0]
-                    rows.append(a * D + k[keep].long())
-                    cols.append(keep)
-                    vals.append(wk[keep])
-            w = self._cache["weights"] = (torch.cat(rows), torch.cat(cols), torch.cat(vals))
-        return w
+        (H, W), D, f = self.size, self.det_count, torch.float32
+        x = (torch.arange(W, dtype=f) - (W - 1) / 2)[None, :]
+        y = (torch.arange(H, dtype=f) - (H - 1) / 2)[:, None]
+        inv, off = torch.tensor(1.0 / self.det_spacing, dtype=f), torch.tensor((D - 1) / 2, dtype=f)
+        rows, cols, vals = [], [], []
+        for a in range(self.angles):
+            p = ((x * self.table[a, 0] + y * self.table[a, 1]) * inv + off).reshape(-1)  # (eager fp32 ops: nothing is fused)
+            k0 = p.floor()
+            for k in (k0, k0 + 1):
+                wk = (1 - (p - k).abs()).clamp_min(0)
+                keep = ((k >= 0) & (k < D) & (wk > 0)).nonzero()[:, 0]
+                rows.append(a * D + k[keep].long())
+                cols.append(keep)
+                vals.append(wk[keep])
+        return torch.cat(rows), torch.cat(cols), torch.cat(vals)
 
     def _matrices(self, x: Tensor) -> tuple[Tensor, Tensor, Tensor]:
         r"""(M, M^T, the Toeplitz matrix of the taps) in ``x``'s dtype on its device, built once per device and dtype."""
-        key = ("matrix", x.device, x.dtype)
-        m = self._cache.get(key)
-        if m is None:
-            rows, cols, vals = self._weights()
+        def make() -> tuple[Tensor, Tensor, Tensor]:  # (the sparse matrices on x's device at once: it coalesces faster)
+            rows, cols, vals = self._weights
             (H, W), A, D = self.size, self.angles, self.det_count
             vals = vals.to(device=x.device, dtype=x.dtype)
             rows, cols = rows.to(x.device), cols.to(x.device)
             M = torch.sparse_coo_tensor(torch.stack([rows, cols]), vals, (A * D, H * W)).coalesce()
             Mt = torch.sparse_coo_tensor(torch.stack([cols, rows]), vals, (H * W, A * D)).coalesce()
             idx = (torch.arange(D)[:, None] - torch.arange(D)[None, :]).abs()
-            m = self._cache[key] = (M, Mt, self.taps[idx].to(device=x.device, dtype=x.dtype))
-        return m
+            return M, Mt, self.taps[idx]
+
+        return self._constant(x, "matrix", make)
 
     def _product(self, x: Tensor, mode: str) -> Tensor:
         if x.dtype not in (torch.float32, torch.float64):  # (torch has no half-precision sparse product on the device)
@@ -1389,12 +1376,10 @@ class RadonOperator(LinearOperator):
         return y * scale if mode == "fbp" else y
 
     def _torch(self, x: Tensor, mode: str) -> Tensor:
-        return _ApplyMatrix.apply(x, self, mode)
-
-    def _run(self, x: Tensor, mode: str) -> Tensor:
-        if _use_kernels(x) or (x.is_cuda and x.dtype == torch.float32):  # (a strided view too: the Function makes it contiguous)
-            return _Apply.apply(x, self, mode)
-        return self._torch(x, mode)
+        r"""The sparse products, inside the Function: ``torch.sparse.mm`` has no forward-mode rule of its own.  For the tensors
+        ``_run`` sends here, that is: the Function gives an fp32 device tensor to the kernels, so the products of such a tensor
+        are ``_product``."""
+        return _Apply.apply(x, self, mode)
 
     # -- the public maps ------------------------------------------------------------------------------------------------
     def pinv(self, y: Tensor) -> Tensor:
@@ -1403,6 +1388,4 @@ class RadonOperator(LinearOperator):
 
     def fbp(self, y: Tensor) -> Tensor:
         r"""Filtered back-projection of a :math:`(B, C, A, D)` or flat sinogram: :math:`(\pi / A) A^\top (h * y)`."""
-        y = self._image(y, "fbp")
-        self._in_shape_of(tuple(y.shape[1:]))
-        return self._run(y, "fbp")
+        return self._from_observation(y, "fbp")

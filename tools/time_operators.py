@@ -199,9 +199,10 @@ def radon(args: list[str]) -> None:
     A = RadonOperator(radon_angles(n), (H, W))
     D = A.det_count
     x, v = torch.randn(B, Cc, H, W, device="cuda"), torch.randn(B, Cc, n, D, device="cuda")
-    # what a user can write today on the same device tensor: torch.sparse.mm with the same matrix (the operator's torch path)
+    # what a user can write today on the same device tensor: torch.sparse.mm with the same matrix (the operator's torch path,
+    # called as `_product`: inside the Function an fp32 device tensor is the kernels')
     forms = {"apply": (lambda: A(x), 20), "adjoint": (lambda: A.adjoint(v), 20), "fbp": (lambda: A.fbp(v), 20),
-             "sparse_mm_apply": (lambda: A._torch(x, "apply"), 5), "sparse_mm_adjoint": (lambda: A._torch(v, "adjoint"), 5)}
+             "sparse_mm_apply": (lambda: A._product(x, "apply"), 5), "sparse_mm_adjoint": (lambda: A._product(v, "adjoint"), 5)}
     ref, ref_t, ref_f = (A._torch(t.double(), m) for t, m in ((x, "apply"), (v, "adjoint"), (v, "fbp")))
     refs = {"apply": ref, "sparse_mm_apply": ref, "adjoint": ref_t, "sparse_mm_adjoint": ref_t, "fbp": ref_f}
     err = {k: float((fn().double() - refs[k]).abs().max()) for k, (fn, _) in forms.items()}
