@@ -46,7 +46,19 @@ class AzStepCoef(C.Structure):
 # column order of the float32 view of an AzStepCoef row (ints are bit-cast into their slots)
 COEF_FIELDS = [f[0] for f in AzStepCoef._fields_[:14]]
 COEF_WORDS = 16
+COEF_SPARE = (14, 15)  # AzStepCoef.pad: two spare coefficients of a row (``pad0``, ``pad1`` of ``Sampler._fused_rows``)
 assert C.sizeof(AzStepCoef) == 64
+
+# The fp64 row of the captured fp64 loop: four blocks of 12 doubles, each in the field order az_transition_f64 reads
+# ("`coef` points to 12 doubles in AzStepCoef's field order", include/azula_amd.h at az_transition_f64).
+ROW64_FIELDS = COEF_FIELDS[:12]
+ROW64_DENOISER, ROW64_TRANSITION, ROW64_CLAMP, ROW64_SAMPLER, ROW64_WORDS = 0, 12, 24, 36, 48  # (.., clamp / CFG, the sampler's own)
+ROW64_SPARE = (4, 5)  # the fp64 twins of COEF_SPARE: the denoiser block's alpha_t / alpha_s slots, which no kernel reads there
+
+
+def row64_word(name: str, block: int = ROW64_DENOISER) -> int:
+    r"""Word of field ``name`` in the block that starts at word ``block`` of the fp64 row."""
+    return block + ROW64_FIELDS.index(name)
 
 
 class AzTransitionArgs(C.Structure):

@@ -112,8 +112,8 @@ class RePaintSampler(DDIMSampler):
     def _fusable(self, x: Tensor) -> bool:
         if type(self).step is not RePaintSampler.step:
             return False  # a subclass overrides step: generic loop
-        if x.ndim < 2 or x.dtype != torch.float32 or self.dtype not in (None, torch.float32) or self.iterations < 1:
-            return False
+        if x.ndim < 2 or self._clock(x) != "f32" or self.iterations < 1:
+            return False  # (the fp64 clock runs the generic loop: the masked replacement has no fp64 kernel)
         y, m = self.y, self.mask
         if not (torch.is_tensor(y) and torch.is_tensor(m)):
             return False

@@ -1,7 +1,8 @@
-r"""Reverse-diffusion samplers -- drop-in for ``azula.sample`` (DDPM / DDIM).
+r"""Reverse-diffusion samplers -- drop-in for ``azula.sample``: DDPM, DDIM, Euler, Heun, Ito, the Adams-Bashforth multistep
+family (zAB, vAB, zEAB, xEAB, REAB) and predictor-corrector (``guidance/repaint.py`` adds RePaint on the same hooks).
 
 Same constructors, ``timesteps``, ``init``, ``__call__`` and overridable ``step`` as the reference
-(``azula/sample.py:54-261``).  What changes is *how* a step executes on an AMD GPU:
+(``azula/sample.py:54-993``).  What changes is *how* a step executes on an AMD GPU:
 
 reference (per step)                         | azula_amd (per step)
 ---------------------------------------------|---------------------------------------------------
@@ -9,10 +10,12 @@ reference (per step)                         | azula_amd (per step)
 c_in*x, c_skip*x, c_out*F, +, 9 more passes  | ONE fused pass ``az_transition_f32`` (12-16 B/elem)
 ~1000 ATen launches for the backbone         | one hipGraph replay of hand-written kernels
 
-The fused path is taken when the denoiser exposes a compiled program (``Denoiser._az_fused``)
-and ``step`` is not overridden; any other denoiser / subclass runs the generic loop, whose
-``step`` still uses the HIP transition kernel for device tensors.  Host tensors follow the
-reference's torch op sequence (its CPU-runnable README configuration).
+The fused path is taken when the denoiser exposes a compiled program (``Denoiser._az_fused``) and ``step`` is not overridden:
+the captured fp32 loop (``_FusedLoop``), or under ``Sampler(dtype=float64)`` the same tapes with fp64 elementwise kernels around
+the fp32 backbone (``_FusedLoopWide``); ``Sampler._clock`` decides.  Both read per-evaluation scalars from host tables that ONE walk
+(``Sampler._fused_walk``) feeds: ``_host_table`` (AzStepCoef words) and ``_host_table_wide`` (the fp64 row of ``_lib.ROW64_*``).
+Any other denoiser / subclass runs the generic loop, whose ``step`` still uses the HIP transition kernel for device tensors.
+Host tensors follow the reference's torch op sequence (its CPU-runnable README configuration).
 """
 
 from __future__ import annotations
@@ -21,17 +24,20 @@ import abc
 import ctypes as C
 import math
 import os
-from collections.abc import Iterable, Sequence
+import weakref
+from collections.abc import Iterable, Iterator, Sequence
 from dataclasses import dataclass, field
 from typing import Callable
 
 import torch
 from torch import Tensor
 
-from . import _lib
-from ._lib import COEF_FIELDS, COEF_WORDS
+from . import _lib, rng
+from ._lib import (COEF_FIELDS, COEF_SPARE, COEF_WORDS, ROW64_CLAMP, ROW64_DENOISER, ROW64_FIELDS, ROW64_SAMPLER, ROW64_SPARE,
+                   ROW64_TRANSITION, ROW64_WORDS, row64_word)
 from .denoise import Denoiser, axpby_wide, is_wide, require_f32_cuda
 from .engine import StepGraph, Tape, plan_mode, transition_args
+from .plan_key import _SMALL_VALUES, _attr_key, _kwargs_signature, _schedule_key, module_fingerprint  # noqa: F401  (re-exported)
 
 SLICED_NOISE = os.environ.get("AZ_SLICED_NOISE", "1") != "0"  # sharded batches: draw only the rank's slice of the full-batch noise
 WIDE_FUSED = os.environ.get("AZ_WIDE_FUSED", "1") != "0"  # captured loop for Sampler(dtype=float64) ("0": the generic fp64 loop)
@@ -168,8 +174,8 @@ class Sampler(abc.ABC):
             return torch.randn_like(like) if out is None else out.normal_()
         rank, world = self.shard
         if (like.is_cuda and like.dtype == torch.float32 and SLICED_NOISE and world * like.numel() < 2**31
-                and _randn_slice_verified(like.device)):
-            return _randn_slice(like, rank, world, out)  # this rank's elements of the full-batch draw only (bit-identical)
+                and rng._randn_slice_verified(like.device)):
+            return rng._randn_slice(like, rank, world, out)  # this rank's elements of the full-batch draw only (bit-identical)
         full = torch.randn((world * like.shape[0], *like.shape[1:]), dtype=like.dtype, device=like.device)
         mine = full[rank * like.shape[0] : (rank + 1) * like.shape[0]]
         return mine.contiguous() if out is None else out.copy_(mine)
@@ -202,112 +208,87 @@ class Sampler(abc.ABC):
         q_t = self.denoiser(x_t, t, **kwargs)
         if not x_t.is_cuda:
             return self._host_step(x_t, q_t.mean, t, s)
-        return self._device_transition(x_t, q_t.mean, t, s)
-
-    def _device_transition(self, x_t: Tensor, mean: Tensor, t: Tensor, s: Tensor) -> Tensor:
         _, _, _, _, alpha_t, alpha_s, k_x, k_eps = self._transition_scalars(t, s)
-        return self._device_kernel(x_t, mean, alpha_t, alpha_s, k_x, k_eps, True)
+        return self._device_kernel(x_t, q_t.mean, alpha_t, alpha_s, k_x, k_eps, True)
 
     def _device_kernel(self, x_t: Tensor, mean: Tensor, alpha_t, alpha_s, k_x, k_eps, draw: bool) -> Tensor:
-        r"""x_s = alpha_s m + k_x (x_t - alpha_t m) + k_eps eps through ``az_transition_f32``; ``draw=False``
-        skips the noise draw and the eps stream (the kernel's EPS=false instantiation)."""
-        if is_wide(x_t, mean):
-            return self._device_kernel_wide(x_t, mean, alpha_t, alpha_s, k_x, k_eps, draw)
-        require_f32_cuda(x_t, type(self).__name__)
-        dev = x_t.device
-        zero = torch.zeros((), device=dev)
-        row = torch.zeros(COEF_WORDS, dtype=torch.float32, device=dev)
-        vals = {
-            "c_skip": zero, "c_out": zero + 1, "alpha_t": alpha_t, "alpha_s": alpha_s, "k_x": k_x, "k_eps": k_eps,
-            "clip_lo": zero - math.inf, "clip_hi": zero + math.inf,
-        }
-        for name, v in vals.items():
-            row[COEF_FIELDS.index(name)] = v.to(device=dev, dtype=torch.float32)
-        x_c = x_t.contiguous()
+        r"""x_s = alpha_s m + k_x (x_t - alpha_t m) + k_eps eps in ONE launch, in the tensors' precision: ``az_transition_f32``,
+        or ``az_transition_f64`` for fp64 latents or an fp64 posterior mean -- what a ``Sampler(dtype=float64)`` produces from
+        its first step on (the reference's promotion, ``azula/sample.py:257-259``).  ``draw=False`` skips the noise draw and the
+        eps stream (the kernel's EPS=false instantiation).  The noise is drawn in ``x_t``'s own dtype, like the reference's
+        ``randn_like(x_t)`` (``_noise_like_update``: in the updated state's, which the fp64 scalars have promoted already)."""
+        wide = is_wide(x_t, mean)
+        if not wide:
+            require_f32_cuda(x_t, type(self).__name__)
+        dev, dtype = x_t.device, torch.float64 if wide else torch.float32
+        row = torch.zeros(len(ROW64_FIELDS) if wide else COEF_WORDS, dtype=dtype, device=dev)
+        vals = {"c_out": 1.0, "alpha_t": alpha_t, "alpha_s": alpha_s, "k_x": k_x, "k_eps": k_eps, "clip_lo": -math.inf, "clip_hi": math.inf}
+        for name, v in vals.items():  # (ROW64_FIELDS is the head of COEF_FIELDS: one index serves both rows)
+            row[ROW64_FIELDS.index(name)] = v.to(device=dev, dtype=dtype) if torch.is_tensor(v) else v
+        x_c = x_t.to(dtype).contiguous()
         mean = mean.to(x_c).contiguous()
-        eps = self._draw_noise(x_c) if draw else None
+        like = x_c if (x_t.dtype == dtype or self._noise_like_update) else x_t.contiguous()
+        eps = self._draw_noise(like).to(dtype) if draw else None
         x_s = torch.empty_like(x_c)
         a = transition_args(
             x_t=x_c.data_ptr(), F=mean.data_ptr(), eps=eps.data_ptr() if draw else 0, x_s=x_s.data_ptr(), batch=1, channels=1,
             inner=x_c.numel(), f_channels=1, coef=row.data_ptr(),
         )
-        _lib.call("az_transition_f32", C.byref(a), _lib.stream_ptr())
-        return x_s
-
-    def _device_kernel_wide(self, x_t: Tensor, mean: Tensor, alpha_t, alpha_s, k_x, k_eps, draw: bool) -> Tensor:
-        r"""The same update in fp64 (``az_transition_f64``): fp64 latents, or an fp64 posterior mean -- what a
-        ``Sampler(dtype=float64)`` produces from its first step on (the reference's promotion, ``azula/sample.py:257-259``).
-        The noise is drawn in ``x_t``'s own dtype, like the reference's ``randn_like(x_t)`` (``_noise_like_update``: in the
-        updated state's, fp64)."""
-        dev = x_t.device
-        row = torch.zeros(12, dtype=torch.float64, device=dev)
-        names = ["c_in", "c_skip", "c_out", "c_time", "alpha_t", "alpha_s", "k_x", "k_eps", "c_in_next", "clip_lo", "clip_hi", "guidance"]
-        vals = {"c_out": 1.0, "alpha_t": alpha_t, "alpha_s": alpha_s, "k_x": k_x, "k_eps": k_eps, "clip_lo": -math.inf, "clip_hi": math.inf}
-        for name, v in vals.items():
-            row[names.index(name)] = v.to(device=dev, dtype=torch.float64) if torch.is_tensor(v) else v
-        x64, m64 = x_t.to(torch.float64).contiguous(), mean.to(torch.float64).contiguous()
-        # (the Ito step draws randn_like(x_s), which the fp64 scalars have promoted already: azula/sample.py:427-429)
-        eps = self._draw_noise(x64 if self._noise_like_update else x_t.contiguous()).to(torch.float64) if draw else None
-        x_s = torch.empty_like(x64)
-        a = transition_args(x_t=x64.data_ptr(), F=m64.data_ptr(), eps=eps.data_ptr() if draw else 0, x_s=x_s.data_ptr(), batch=1,
-                            channels=1, inner=x64.numel(), f_channels=1, coef=row.data_ptr())
-        _lib.call("az_transition_f64", C.byref(a), _lib.stream_ptr())
+        _lib.call("az_transition_f64" if wide else "az_transition_f32", C.byref(a), _lib.stream_ptr())
         return x_s
 
     # ---------------------------------------------------------------------------- fused path
     def _fusable(self, x: Tensor) -> bool:
-        if type(self).step not in _FUSED_STEPS:
-            return False  # a user subclass overrides step (guidance samplers ...): generic loop
-        if x.ndim < 2:
-            return False
-        if x.dtype == torch.float32 and self.dtype in (None, torch.float32):
-            return True
-        # fp64 time grid (fp32 or fp64 latents): the captured loop with fp64 elementwise kernels (_FusedLoopWide) for the
-        # samplers whose step is one evaluation + one transition
-        return self._wide_fusable(x)
+        # (a user subclass that overrides step -- guidance samplers ... -- runs the generic loop)
+        return type(self).step in _FUSED_STEPS and x.ndim >= 2 and self._clock(x) is not None
 
     # True: the step's randn_like takes the UPDATED state (already fp64 under an fp64 clock) as its model, not x_t (ItoSampler)
     _noise_like_update = False
+    # Stated by the class that DEFINES ``_fused_step_tapes``: True if ``_FusedLoopWide`` can lay those tapes out in fp64 (they use
+    # the loop's own blocks alone, or dispatch on ``loop.wide``): the default tapes (DDPM, DDIM, Euler, Ito), Heun, PC, multistep.
+    # A subclass that overrides the tapes without stating it (RePaint, user code) runs the generic loop under an fp64 clock.
+    _fused_wide = True
 
-    def _wide_fusable(self, x: Tensor) -> bool:
-        r"""The one-evaluation samplers (DDPM, DDIM, Euler, Ito), the two whose tapes are built from the loop's own blocks
-        (Heun, PC) and the multistep family (its fp64 weights in words 36 .. 47 of the row)."""
-        tapes = (Sampler._fused_step_tapes, HeunSampler._fused_step_tapes, PCSampler._fused_step_tapes, _MultistepSampler._fused_step_tapes)
-        return (self.dtype == torch.float64 and x.dtype in (torch.float32, torch.float64) and WIDE_FUSED
-                and type(self)._fused_step_tapes in tapes)
+    def _clock(self, x: Tensor) -> str | None:
+        r"""Which clock a call on ``x`` runs on: ``"f32"`` (fp32 latents and time grid: ``_FusedLoop``), ``"f64"`` (an fp64 time
+        grid, for the samplers whose tapes ``_FusedLoopWide`` can lay out) or ``None`` (neither: the generic loop)."""
+        if x.dtype == torch.float32 and self.dtype in (None, torch.float32):
+            return "f32"
+        if self.dtype == torch.float64 and x.dtype in (torch.float32, torch.float64) and WIDE_FUSED:
+            owner = next(c for c in type(self).__mro__ if "_fused_step_tapes" in vars(c))
+            if vars(owner).get("_fused_wide", False):
+                return "f64"
+        return None
+
+    def _fused_walk(self, fused: "FusedDenoiser") -> Iterator[tuple[int, dict, dict]]:
+        r"""(step index, ``_fused_rows`` spec, the denoiser's coefficients there) per DENOISER EVALUATION of a sampling, in execution
+        order: 0-d host scalars in the reference's op order.  ``_host_table`` and ``_host_table_wide`` encode this one sequence."""
+        ts = torch.linspace(self.start, self.stop, self.steps + 1, dtype=self.dtype)
+        for i, (t, s) in enumerate(ts.unfold(0, 2, 1).unbind()):
+            for spec in self._fused_rows(t, s, fused):
+                yield i, spec, fused.coefficients(spec["alpha"], spec["sigma"])
 
     def _host_table_wide(self, fused: "FusedDenoiser") -> Tensor:
-        r"""(steps * evaluations per step, 24) fp64: per evaluation the denoiser's row [c_in, c_skip, c_out, c_time, ...] and the transition's row
-        [.., c_skip = 0, c_out = 1, alpha_t, alpha_s, k_x, k_eps, .., clip_lo = -inf, clip_hi = inf, ..] in the field order of
-        ``az_transition_f64``'s coefficient row -- the 0-d host scalars of the fp64 time grid, in the reference's op order;
-        words 24 .. 35 the clamp / CFG row, words 36 .. 47 free for the sampler (the multistep family's weights)."""
-        names = ["c_in", "c_skip", "c_out", "c_time", "alpha_t", "alpha_s", "k_x", "k_eps", "c_in_next", "clip_lo", "clip_hi", "guidance"]
-        ts = torch.linspace(self.start, self.stop, self.steps + 1, dtype=self.dtype)
-        out = []
+        r"""(steps * evaluations per step, ``ROW64_WORDS``) fp64, four blocks in ``ROW64_FIELDS`` order (``az_transition_f64``'s
+        coefficient row): the denoiser's [c_in, c_skip, c_out, c_time, spare p, spare q, ..], the transition's [.., c_out = 1,
+        alpha_t, alpha_s, k_x, k_eps, .., clip_lo = -inf, clip_hi = inf, ..], the CLAMP row of the posterior mean (a transition row that
+        only clips: c_out = alpha_s = 1; -1, +1 and the CFG guidance in its unused slots), then the sampler's own block (multistep)."""
         f64 = lambda v: v.to(torch.float64) if torch.is_tensor(v) else float(v)  # noqa: E731
-        for t, s in ts.unfold(0, 2, 1).unbind():
-            for spec in self._fused_rows(t, s, fused):  # one row per denoiser evaluation, like _host_table
-                row = torch.zeros(_FusedLoopWide.WORDS, dtype=torch.float64)
-                co = fused.coefficients(spec["alpha"], spec["sigma"])
-                for n in ("c_in", "c_skip", "c_out", "c_time"):
-                    if n in co:  # (ADM reads an integer time index from the fp32 row instead of c_time)
-                        row[names.index(n)] = co[n].to(torch.float64)
-                # (words 4, 5 of the denoiser half are free: the two spare coefficients of a row, HeunSampler's p and q)
-                row[4], row[5] = f64(spec.get("pad0", 0.0)), f64(spec.get("pad1", 0.0))
-                row[names.index("clip_lo")], row[names.index("clip_hi")] = -math.inf, math.inf
-                b = 12
-                row[b + names.index("c_out")] = 1.0
-                row[b + names.index("alpha_t")], row[b + names.index("alpha_s")] = f64(spec["a_t"]), f64(spec["a_s"])
-                row[b + names.index("k_x")], row[b + names.index("k_eps")] = f64(spec["k_x"]), f64(spec["k_eps"])
-                row[b + names.index("clip_lo")], row[b + names.index("clip_hi")] = -math.inf, math.inf
-                # words 24 .. 35: the CLAMP row of the posterior mean (a transition row that only clips: c_out = 1, alpha_s = 1)
-                # with the constants -1 / +1 and the guidance of the CFG combination in its unused slots
-                b = 24
-                row[b + names.index("c_out")], row[b + names.index("alpha_s")] = 1.0, 1.0
-                row[b + names.index("clip_lo")], row[b + names.index("clip_hi")] = fused.clip
-                row[b + names.index("c_time")], row[b + names.index("c_in_next")] = -1.0, 1.0
-                row[b + names.index("guidance")] = fused.guidance
-                out.append(row)
+        out = []
+        for _, spec, co in self._fused_walk(fused):
+            blocks = {  # (ADM reads an integer time index from the fp32 row instead of c_time)
+                ROW64_DENOISER: {**{n: co[n] for n in ("c_in", "c_skip", "c_out", "c_time") if n in co}, "clip_lo": -math.inf, "clip_hi": math.inf},
+                ROW64_TRANSITION: dict(c_out=1.0, alpha_t=spec["a_t"], alpha_s=spec["a_s"], k_x=spec["k_x"], k_eps=spec["k_eps"],
+                                       clip_lo=-math.inf, clip_hi=math.inf),
+                ROW64_CLAMP: dict(c_out=1.0, alpha_s=1.0, clip_lo=fused.clip[0], clip_hi=fused.clip[1], c_time=-1.0, c_in_next=1.0,
+                                  guidance=fused.guidance),
+            }
+            row = torch.zeros(ROW64_WORDS, dtype=torch.float64)
+            for block, vals in blocks.items():
+                for n, v in vals.items():
+                    row[row64_word(n, block)] = f64(v)
+            row[ROW64_SPARE[0]], row[ROW64_SPARE[1]] = f64(spec.get("pad0", 0.0)), f64(spec.get("pad1", 0.0))  # (HeunSampler's p and q)
+            out.append(row)
         return torch.stack(out)
 
     # -- what a step looks like inside the captured graph ----------------------------------------------------------
@@ -328,25 +309,23 @@ class Sampler(abc.ABC):
 
     def _host_table(self, fused: FusedDenoiser) -> Tensor:
         r"""(steps * rows_per_step, 16) fp32 table of AzStepCoef rows, from 0-d CPU tensors in reference op order."""
-        ts = torch.linspace(self.start, self.stop, self.steps + 1, dtype=self.dtype)
         col = {n: i for i, n in enumerate(COEF_FIELDS)}
         out = []
-        for i, (t, s) in enumerate(ts.unfold(0, 2, 1).unbind()):
-            for spec in self._fused_rows(t, s, fused):
-                row = torch.zeros(COEF_WORDS, dtype=torch.float32)
-                irow = row.view(torch.int32)  # integer slots (time_index, step) are bit-cast in place
-                for name, v in fused.coefficients(spec["alpha"], spec["sigma"]).items():
-                    if name == "time_index":
-                        irow[col[name]] = int(v)
-                    else:
-                        row[col[name]] = v.to(torch.float32)
-                row[col["alpha_t"]], row[col["alpha_s"]] = spec["a_t"], spec["a_s"]
-                row[col["k_x"]], row[col["k_eps"]] = spec["k_x"], spec["k_eps"]
-                row[col["clip_lo"]], row[col["clip_hi"]] = fused.clip
-                row[col["guidance"]] = fused.guidance
-                irow[col["step"]] = i
-                row[14], row[15] = spec.get("pad0", 0.0), spec.get("pad1", 0.0)
-                out.append(row)
+        for i, spec, co in self._fused_walk(fused):
+            row = torch.zeros(COEF_WORDS, dtype=torch.float32)
+            irow = row.view(torch.int32)  # integer slots (time_index, step) are bit-cast in place
+            for name, v in co.items():
+                if name == "time_index":
+                    irow[col[name]] = int(v)
+                else:
+                    row[col[name]] = v.to(torch.float32)
+            row[col["alpha_t"]], row[col["alpha_s"]] = spec["a_t"], spec["a_s"]
+            row[col["k_x"]], row[col["k_eps"]] = spec["k_x"], spec["k_eps"]
+            row[col["clip_lo"]], row[col["clip_hi"]] = fused.clip
+            row[col["guidance"]] = fused.guidance
+            irow[col["step"]] = i
+            row[COEF_SPARE[0]], row[COEF_SPARE[1]] = spec.get("pad0", 0.0), spec.get("pad1", 0.0)
+            out.append(row)
         rows = torch.stack(out)
         rows[:-1, col["c_in_next"]] = rows[1:, col["c_in"]]  # each evaluation pre-scales the NEXT evaluation's input
         return rows
@@ -393,7 +372,7 @@ class Sampler(abc.ABC):
         g = kwargs.get("guidance")
         if torch.is_tensor(g) and g.numel() != 1:
             return None  # per-sample guidance: generic loop
-        wide = not (x.dtype == torch.float32 and self.dtype in (None, torch.float32))
+        wide = self._clock(x) != "f32"
         key = (
             tuple(x.shape), str(dev), _kwargs_signature(kwargs), self._fused_structure(), id(self.denoiser),
             module_fingerprint(self.denoiser), str(x.dtype), wide, getattr(self.denoiser, "_az_fused_key", tuple)(), plan_mode(),
@@ -425,141 +404,6 @@ class Sampler(abc.ABC):
 _NOT_WIDE = object()  # plan-cache entry: the denoiser's program does not run under an fp64 clock
 
 
-def module_fingerprint(module: torch.nn.Module) -> tuple:
-    r"""Identity of a module's state as the compiled plans see it: (address, in-place version, dtype) of every
-    parameter and buffer plus the train/eval flags.  Packed weight copies (direct, Winograd, half) are valid exactly
-    as long as this tuple is unchanged."""
-    tensors = tuple((t.data_ptr(), t._version, t.dtype) for t in (*module.parameters(), *module.buffers()))
-    return tensors + tuple(m.training for m in module.modules())
-
-
-def _schedule_key(sched) -> tuple:
-    r"""Scalar attributes of a schedule object (alpha_min, sigma_min, gamma, ...) and, for ``nn.Module`` schedules,
-    the fingerprint of their tensors."""
-    return _attr_key(getattr(sched, "__dict__", {})) + (module_fingerprint(sched) if isinstance(sched, torch.nn.Module) else ())
-
-
-def _value_key(v):
-    r"""A hashable stand-in for one attribute value, or ``_SKIP``: numbers / strings / dtypes by value, small tensors by
-    VALUE (eta, temperature, alpha_min held as 0-d or short tensors: the reference re-reads them on every call), larger
-    tensors by (address, version), tuples / lists recursively.  Modules and other objects are not hyper-parameters."""
-    if isinstance(v, (int, float, bool, str, type(None), torch.dtype)):
-        return v
-    if torch.is_tensor(v):
-        if v.numel() <= 16:
-            # `.tolist()` on a device tensor is a blocking sync: read the value only when the tensor's identity
-            # (object, storage address, version counter) changes.  Writes through `.data` do not bump the version counter and
-            # are NOT tracked -- neither here nor by the (address, version) key of larger tensors (documented in DESIGN.md).
-            ident = (v.data_ptr(), v._version, tuple(v.shape), v.dtype, v.device)
-            hit = _SMALL_VALUES.get(id(v))
-            if hit is None or hit[0] != ident or hit[1]() is not v:
-                import weakref
-
-                if len(_SMALL_VALUES) > 256:
-                    for k in [k for k, h in _SMALL_VALUES.items() if h[1]() is None]:
-                        del _SMALL_VALUES[k]
-                hit = (ident, weakref.ref(v), tuple(v.detach().reshape(-1).tolist()))
-                _SMALL_VALUES[id(v)] = hit
-            return ("t", tuple(v.shape), str(v.dtype), hit[2])
-        return ("T", v.data_ptr(), v._version, tuple(v.shape), str(v.dtype))
-    if isinstance(v, (tuple, list)):
-        items = tuple(_value_key(x) for x in v)
-        return _SKIP if any(x is _SKIP for x in items) else ("seq", items)
-    return _SKIP
-
-
-_SKIP = object()
-_SMALL_VALUES: dict = {}  # id(tensor) -> ((address, version, shape, dtype, device), weakref, value tuple)
-
-
-def _attr_key(attrs: dict) -> tuple:
-    out = []
-    for k, v in sorted(attrs.items()):
-        if k.startswith("_fused") or isinstance(v, torch.nn.Module):
-            continue
-        kv = _value_key(v)
-        if kv is not _SKIP:
-            out.append((k, kv))
-    return tuple(out)
-
-
-def _kwargs_signature(kw) -> tuple:
-    r"""Structure of the keyword arguments (names, nesting, which values are None) -- not their values: label and
-    guidance VALUES are uploaded per call, their presence decides which programs exist."""
-    if isinstance(kw, dict):
-        return tuple((k, _kwargs_signature(v)) for k, v in sorted(kw.items()))
-    if kw is None:
-        return ("none",)
-    if torch.is_tensor(kw):
-        return ("tensor", tuple(kw.shape))
-    return ("value",)
-
-
-_SLICE_VERIFIED: dict = {}  # (device index, torch version) -> bool
-
-
-def _randn_slice_verified(dev: torch.device) -> bool:
-    r"""One-time self-check per (device, torch version): :func:`_randn_slice` re-derives ATen's launch policy (grid rule, unroll 4,
-    offset arithmetic) from the torch it was written against.  A torch whose policy differs would still hand out valid noise,
-    but the 1-GPU == N-GPU bit-reproducibility of ``parallel.py`` would break silently.  So the first sharded draw on a device
-    compares two slices -- a tensor under one grid's worth of elements and one that spans several grid iterations -- and the
-    generator's offset afterwards against ``torch.randn`` of the full shape, under a saved / restored generator state; on any
-    mismatch it warns once and every later sharded draw takes the draw-and-slice path."""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (idx, torch.__version__)
-    ok = _SLICE_VERIFIED.get(key)
-    if ok is None:
-        gen = torch.cuda.default_generators[idx]
-        saved = gen.get_state()
-        ok = True
-        try:
-            for total, world, rank in ((3 * 1000, 3, 1), (3 * (1 << 20) + 3 * 4096, 3, 2), (2 * 65536, 2, 0)):
-                gen.manual_seed(1234567)
-                gen.set_offset(8)
-                full = torch.randn(total, device=dev)
-                off_full = gen.get_offset()
-                gen.manual_seed(1234567)
-                gen.set_offset(8)
-                n = total // world
-                mine = _randn_slice(torch.empty(n, device=dev), rank, world)
-                ok = ok and gen.get_offset() == off_full and bool(torch.equal(mine, full[rank * n : (rank + 1) * n]))
-        except Exception:  # noqa: BLE001  (a generator API that moved: same verdict)
-            ok = False
-        finally:
-            gen.set_state(saved)
-        _SLICE_VERIFIED[key] = ok
-        if not ok:
-            import warnings
-
-            warnings.warn(
-                f"azula_amd: the sliced Philox draw does not reproduce torch.randn on torch {torch.__version__} (device {idx}); "
-                "sharded sampling falls back to drawing the full batch on every rank and slicing (same result, more work)",
-                RuntimeWarning, stacklevel=3)
-    return ok
-
-
-def _randn_slice(like: Tensor, rank: int, world: int, out: Tensor | None = None) -> Tensor:
-    r"""Elements [rank n, (rank + 1) n) of ``torch.randn(world * n)`` on ``like``'s device, without drawing the rest: ATen's
-    launch policy for the FULL tensor (``ATen/native/cuda/DistributionTemplates.h: calc_execution_policy``) fixes which Philox
-    subsequence / call / component produces every element; the kernel evaluates exactly those."""
-    dev = like.device
-    gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
-    n = like.numel()
-    total = world * n
-    props = torch.cuda.get_device_properties(dev)
-    grid = min(props.multi_processor_count * (props.max_threads_per_multi_processor // 256), (total + 255) // 256)
-    threads = 256 * grid
-    seed, offset = gen.initial_seed(), gen.get_offset()
-    dst = out if (out is not None and out.is_contiguous()) else torch.empty_like(like, memory_format=torch.contiguous_format)
-    with torch.cuda.device(dev):
-        _lib.call("az_randn_slice_f32", dst.data_ptr(), seed, offset, threads, rank * n, n, _lib.stream_ptr())
-    gen.set_offset(offset + ((total - 1) // (threads * 4) + 1) * 4)  # (the full draw's counter_offset)
-    if out is not None and dst is not out:
-        out.copy_(dst)
-        return out
-    return dst
-
-
 class _FusedLoop:
     r"""Static buffers + step tapes + hipGraphs for one (sampler, denoiser, shape).
 
@@ -568,6 +412,8 @@ class _FusedLoop:
     loop replays the captured graph of ``period`` consecutive steps (1 except for the multistep family, whose history
     ring makes the buffer addresses cycle with period ``order``)."""
 
+    wide = False  # (True: the fp64 layout of the same tapes, _FusedLoopWide)
+
     @property
     def sampler(self) -> "Sampler":
         return self._sampler()
@@ -575,8 +421,6 @@ class _FusedLoop:
     def __init__(self, sampler: Sampler, fused: FusedDenoiser, x: Tensor, cur: Tensor) -> None:
         # (a weak reference: the loop lives in sampler._fused_cache -- a strong one would make a cycle, and a dropped plan's pool,
         #  tens of GB of HBM at ADM sizes, would wait for the cycle collector instead of going with the last reference)
-        import weakref
-
         self._sampler, self.fused, self.cur = weakref.ref(sampler), fused, cur
         dev = x.device
         self.x = torch.empty_like(x, memory_format=torch.contiguous_format)
@@ -633,7 +477,8 @@ class _FusedLoop:
 
     def add_spare_axpby(self, tape: Tape, y: Tensor, x: Tensor, z: Tensor) -> None:
         r"""y = p x + q z with the current row's two spare coefficients (``pad0``, ``pad1`` of ``Sampler._fused_rows``)."""
-        tape.add("az_axpby_f32", y.data_ptr(), self.coef_ptr(14), x.data_ptr(), self.coef_ptr(15), z.data_ptr(), 1, x.numel(), 0)
+        p, q = COEF_SPARE
+        tape.add("az_axpby_f32", y.data_ptr(), self.coef_ptr(p), x.data_ptr(), self.coef_ptr(q), z.data_ptr(), 1, x.numel(), 0)
 
     def coef_ptr(self, name_or_word) -> int:
         r"""Device address of one float of the current row (``cur``): kernels that take coefficient POINTERS read the
@@ -665,28 +510,35 @@ class _FusedLoop:
             s._fused_upload_extra(self)
             self.table_key = key
 
+    def _first_input(self) -> None:
+        r"""Backbone input of the first evaluation: c_in[0] * x_T, in the backbone's layout (a transition writes every later one)."""
+        self.add_input_relayout(None, self.x, self.table[0, COEF_FIELDS.index("c_in")].data_ptr())
+
+    def _draw_group(self, g: int) -> None:
+        r"""Noise of the group of steps starting at step ``g``: the reference's generator calls (randn_like), in its order."""
+        s = self.sampler
+        for buf in s._fused_draws(self):
+            s._draw_noise(buf, out=buf)
+
     def run(self, x: Tensor, kwargs: dict) -> Tensor:
         s = self.sampler
         self._upload_table(kwargs)
         for p in self.fused.programs:
             if p.prepare is not None:
                 p.prepare(kwargs)
-        self.x.copy_(x)
+        self.x.copy_(x)  # (fp32 -> fp64 under an fp64 clock is exact: what the first fp64 multiplication of the reference's step does)
         self.counter.zero_()
         s._fused_reset(self)
         stream = _lib.stream_ptr()
-        # backbone input of the first evaluation: c_in[0] * x_T, in the backbone's layout
-        self.add_input_relayout(None, self.x, self.table[0, COEF_FIELDS.index("c_in")].data_ptr())
+        self._first_input()
         for g in s.progress_bar(range(0, s.steps, self.period)):
             n = min(self.period, s.steps - g)
-            for buf in s._fused_draws(self):
-                s._draw_noise(buf, out=buf)  # same generator calls, in the same order, as the reference's randn_like
+            self._draw_group(g)
             graph = self.graphs.get(n)
             if graph is None:  # first group of this length: run eagerly (loads code objects), then capture for the next
-                for t in self.step_tapes[:n]:
-                    t.run(stream)
                 cat = Tape()
                 for t in self.step_tapes[:n]:
+                    t.run(stream)
                     cat.extend(t)
                 self.graphs[n] = StepGraph(cat, x.device)
             else:
@@ -703,11 +555,13 @@ class _FusedLoopWide(_FusedLoop):
     the device-resident current row, as ONE hipGraph per step.  Noise is drawn in the dtype of x_t like the reference's
     ``randn_like(x_t)``: fp32 in the first step of an fp32 input (x_t is promoted by that step), fp64 afterwards."""
 
-    WORDS = 48  # [0, 12) the denoiser's row, [12, 24) the transition's, [24, 36) clamp / CFG constants, [36, 48) the sampler's own
+    WORDS = ROW64_WORDS  # (the row's blocks and field order: _lib.ROW64_*)
+    wide = True
 
     def __init__(self, sampler: "Sampler", fused: FusedDenoiser, x: Tensor, cur: Tensor) -> None:
         dev = x.device
-        self.in_dtype = x.dtype
+        # the state the next evaluation laid on a tape reads: what the tape's previous transition wrote (None: ``x``, the head of a step)
+        self.src: Tensor | None = None
         self.cur64 = torch.zeros(self.WORDS, dtype=torch.float64, device=dev)
         n_rows = len(sampler._host_table(fused))
         self.table64 = torch.zeros(n_rows, self.WORDS, dtype=torch.float64, device=dev)
@@ -718,27 +572,27 @@ class _FusedLoopWide(_FusedLoop):
         # (CFG: the negative program's posterior mean and the difference of the two)
         self.cfg64 = [torch.empty(x.shape, dtype=torch.float64, device=dev) for _ in range(2)] if len(fused.programs) == 2 else None
         super().__init__(sampler, fused, torch.empty(x.shape, dtype=torch.float64, device=dev), cur)
-        n32 = min(1, len(self.noise)) if x.dtype == torch.float32 else 0
-        self.noise32 = [torch.empty(x.shape, dtype=torch.float32, device=dev) for _ in range(n32)]
-        self.dummy32 = torch.empty(x.shape, dtype=torch.float32, device=dev) if (self.dummy is not None and x.dtype == torch.float32) else None
+        assert self.period == 1 or (not self.noise and self.dummy is None)  # (the multistep family: several steps per graph, no noise)
+        # randn_like(x_t) is fp32 only for the FIRST draw of an fp32 input -- the update it feeds promotes the state; a sampler
+        # whose draw is modelled on the updated state never draws fp32
+        draws32 = x.dtype == torch.float32 and not sampler._noise_like_update and (self.noise or self.dummy is not None)
+        self.first32 = torch.empty(x.shape, dtype=torch.float32, device=dev) if draws32 else None
 
-    def _c64(self, name: str, block: int = 0) -> int:
-        names = ["c_in", "c_skip", "c_out", "c_time", "alpha_t", "alpha_s", "k_x", "k_eps", "c_in_next", "clip_lo", "clip_hi", "guidance"]
-        return self.cur64.data_ptr() + 8 * (names.index(name) + 12 * int(block))
+    def _c64(self, name: str, block: int = ROW64_DENOISER) -> int:
+        r"""Device address of field ``name`` in one block of the current fp64 row."""
+        return self.cur64.data_ptr() + 8 * row64_word(name, block)
 
     def add_evaluation(self, tape: Tape) -> None:
         r"""The evaluation reads the state the previous transition of the tape wrote (``x`` at the head of a step): the fp32
         loop's transition kernel leaves the pre-scaled backbone input behind, here it is a pass of its own."""
         p0 = self.fused.programs[0]
-        src = getattr(self, "_src", None)
-        src = self.x if src is None else src
+        src = self.x if self.src is None else self.src
         tape.add("az_step_begin", self.cur.data_ptr(), self.table.data_ptr(), self.counter.data_ptr(), self.n_rows)
         tape.add("az_step_row_f64", self.cur64.data_ptr(), self.table64.data_ptr(), self.counter.data_ptr(), self.n_rows, self.WORDS)
+        xin = p0.x_in if self.xin32 is None else self.xin32
+        tape.add("az_scale_f64_to_f32", xin.data_ptr(), src.data_ptr(), self._c64("c_in"), 1, src.numel(), 0)
         if self.xin32 is not None:
-            tape.add("az_scale_f64_to_f32", self.xin32.data_ptr(), src.data_ptr(), self._c64("c_in"), 1, src.numel(), 0)
             tape.add("az_nchw_to_nhwc_f32", p0.x_in.data_ptr(), self.xin32.data_ptr(), None, self.B, self.C, self.inner, p0.x_in_cs)
-        else:
-            tape.add("az_scale_f64_to_f32", p0.x_in.data_ptr(), src.data_ptr(), self._c64("c_in"), 1, src.numel(), 0)
         for p in self.fused.programs:
             tape.extend(p.tape)
 
@@ -761,7 +615,7 @@ class _FusedLoopWide(_FusedLoop):
                              p.out.data_ptr() + 4 * b * p.f_channels * self.inner, 1, 1, per, 0)
             if clip:
                 a = transition_args(x_t=dst.data_ptr(), F=dst.data_ptr(), x_s=dst.data_ptr(), batch=1, channels=1, inner=n, f_channels=1,
-                                    coef=self.cur64.data_ptr() + 8 * 24)
+                                    coef=self.cur64.data_ptr() + 8 * ROW64_CLAMP)
                 tape.add("az_transition_f64", C.byref(a), keep=[a])
 
         progs = self.fused.programs
@@ -771,7 +625,7 @@ class _FusedLoopWide(_FusedLoop):
         neg, diff = self.cfg64
         raw(mean, progs[0])
         raw(neg, progs[1])
-        one, minus, g = self._c64("c_in_next", 2), self._c64("c_time", 2), self._c64("guidance", 2)
+        one, minus, g = (self._c64(name, ROW64_CLAMP) for name in ("c_in_next", "c_time", "guidance"))  # (+1, -1, g: _host_table_wide)
         tape.add("az_axpby_f64", diff.data_ptr(), one, mean.data_ptr(), minus, neg.data_ptr(), 0, 1, n, 0)
         tape.add("az_axpby_f64", mean.data_ptr(), one, mean.data_ptr(), g, diff.data_ptr(), 0, 1, n, 0)
 
@@ -781,13 +635,13 @@ class _FusedLoopWide(_FusedLoop):
         mean = self.mean64 if mean_out is None else mean_out  # (Heun keeps the first evaluation's posterior mean)
         self.add_mean(tape, x_t, mean)
         a = transition_args(x_t=x_t.data_ptr(), F=mean.data_ptr(), eps=eps.data_ptr() if eps is not None else None,
-                            x_s=x_s.data_ptr(), batch=1, channels=1, inner=n, f_channels=1, coef=self.cur64.data_ptr() + 8 * 12)
+                            x_s=x_s.data_ptr(), batch=1, channels=1, inner=n, f_channels=1, coef=self.cur64.data_ptr() + 8 * ROW64_TRANSITION)
         tape.add("az_transition_f64", C.byref(a), keep=[a])
-        self._src = x_s
+        self.src = x_s
 
     def add_spare_axpby(self, tape: Tape, y: Tensor, x: Tensor, z: Tensor) -> None:
-        tape.add("az_axpby_f64", y.data_ptr(), self.cur64.data_ptr() + 8 * 4, x.data_ptr(), self.cur64.data_ptr() + 8 * 5, z.data_ptr(), 0, 1,
-                 x.numel(), 0)
+        p, q = (self.cur64.data_ptr() + 8 * w for w in ROW64_SPARE)
+        tape.add("az_axpby_f64", y.data_ptr(), p, x.data_ptr(), q, z.data_ptr(), 0, 1, x.numel(), 0)
 
     def _upload_table(self, kwargs: dict) -> None:
         before = self.table_key
@@ -795,50 +649,21 @@ class _FusedLoopWide(_FusedLoop):
         if self.table_key != before:
             self.table64.copy_(self.sampler._host_table_wide(self.fused))
 
-    def run(self, x: Tensor, kwargs: dict) -> Tensor:
+    def _first_input(self) -> None:
+        r"""Nothing to prepare: every evaluation of this loop scales its own backbone input (``add_evaluation``)."""
+
+    def _draw_group(self, g: int) -> None:
         s = self.sampler
-        self._upload_table(kwargs)
-        for p in self.fused.programs:
-            if p.prepare is not None:
-                p.prepare(kwargs)
-        self.x.copy_(x)  # (fp32 -> fp64 is exact: what the first fp64 multiplication of the reference's step does)
-        self.counter.zero_()
-        s._fused_reset(self)
-        stream = _lib.stream_ptr()
-        if self.period > 1:  # (the multistep family: `period` consecutive steps per graph, no noise)
-            assert not self.noise and self.dummy is None
-            for g in s.progress_bar(range(0, s.steps, self.period)):
-                n = min(self.period, s.steps - g)
-                graph = self.graphs.get(n)
-                if graph is None:
-                    cat = Tape()
-                    for t in self.step_tapes[:n]:
-                        t.run(stream)
-                        cat.extend(t)
-                    self.graphs[n] = StepGraph(cat, x.device)
-                else:
-                    graph.launch()
-            return self.x.clone()
-        for g in s.progress_bar(range(s.steps)):
-            # (randn_like(x_t): fp32 only for the FIRST draw of an fp32 input -- the update it feeds promotes the state; a
-            #  sampler whose draw is modelled on the updated state never draws fp32)
-            first32 = g == 0 and self.in_dtype == torch.float32 and not s._noise_like_update
-            for k, buf in enumerate(self.noise):
-                if first32 and k == 0:
-                    s._draw_noise(self.noise32[k], out=self.noise32[k])
-                    buf.copy_(self.noise32[k])
-                else:
-                    s._draw_noise(buf, out=buf)
-            if self.dummy is not None:
-                d = self.dummy32 if first32 else self.dummy
-                s._draw_noise(d, out=d)
-            graph = self.graphs.get(1)
-            if graph is None:
-                self.step_tapes[0].run(stream)
-                self.graphs[1] = StepGraph(self.step_tapes[0], x.device)
+        first32 = self.first32 if g == 0 else None
+        for k, buf in enumerate(self.noise):
+            if first32 is not None and k == 0:
+                s._draw_noise(first32, out=first32)
+                buf.copy_(first32)
             else:
-                graph.launch()
-        return self.x.clone()
+                s._draw_noise(buf, out=buf)
+        if self.dummy is not None:
+            d = self.dummy if first32 is None else first32
+            s._draw_noise(d, out=d)
 
 
 class DDPMSampler(Sampler):
@@ -961,6 +786,8 @@ class HeunSampler(EulerSampler):
             dict(alpha=alpha_s, sigma=sigma_s, a_t=zero, a_s=-c * alpha_s / (2 * sigma_s), k_x=c / (2 * sigma_s), k_eps=one,
                  pad0=alpha_s / alpha_t + c / (2 * sigma_t), pad1=-c * alpha_t / (2 * sigma_t)),
         ]
+
+    _fused_wide = True  # (the loop's own blocks only)
 
     def _fused_step_tapes(self, loop):
         xp, m, e = (torch.empty_like(loop.x) for _ in range(3))
@@ -1138,10 +965,15 @@ class _MultistepSampler(Sampler):
         zero = torch.zeros_like(alpha_t)
         return [dict(alpha=alpha_t, sigma=sigma_t, a_t=zero, a_s=zero, k_x=zero, k_eps=zero)]  # only the mean is used
 
-    def _ring_table(self) -> Tensor:
-        r"""``_device_table`` with the history weights RIGHT-aligned over order - 1 slots (slot k <-> step i - (order-1) + k)."""
+    def _check_order(self) -> None:
+        if self.order < 1 or self.order > _lib.MULTISTEP_MAX_HIST + 1:
+            raise ValueError(f"order must be in [1, {_lib.MULTISTEP_MAX_HIST + 1}], got {self.order}")
+
+    def _ring_table(self, dtype: torch.dtype = torch.float32) -> Tensor:
+        r"""``_device_table`` in ``dtype`` with the history weights RIGHT-aligned over order - 1 slots (slot k <-> step
+        i - (order-1) + k): the fp32 loop's ``mtable``, and in fp64 the head of the sampler's block of the fp64 row."""
         alpha, sigma = self.denoiser.schedule(torch.linspace(self.start, self.stop, self.steps + 1, dtype=self.dtype))
-        rows = self._device_table(alpha, sigma)
+        rows = self._device_table(alpha, sigma, dtype=dtype)
         nh = self.order - 1
         out = torch.zeros_like(rows)
         out[:, :4] = rows[:, :4]
@@ -1150,35 +982,47 @@ class _MultistepSampler(Sampler):
             out[i, 4 + nh - n : 4 + nh] = rows[i, 4 : 4 + n]
         return out
 
+    _RING_WORDS = 4 + _lib.MULTISTEP_MAX_HIST  # [a, b, p, w_new, w_hist x 7]; in the fp64 row the word after them holds 1
+    _fused_wide = True  # (`_fused_step_tapes` dispatches on loop.wide)
+
+    def _host_table_wide(self, fused: "FusedDenoiser") -> Tensor:
+        rows = super()._host_table_wide(fused)
+        rows[:, ROW64_SAMPLER : ROW64_SAMPLER + self._RING_WORDS] = self._ring_table(torch.float64)
+        rows[:, ROW64_SAMPLER + self._RING_WORDS] = 1.0
+        return rows
+
     def _fused_step_tapes(self, loop):
-        if self.order < 1 or self.order > _lib.MULTISTEP_MAX_HIST + 1:
-            raise ValueError(f"order must be in [1, {_lib.MULTISTEP_MAX_HIST + 1}], got {self.order}")
-        dev, nh = loop.x.device, self.order - 1
-        ncols = 4 + _lib.MULTISTEP_MAX_HIST
+        self._check_order()
         loop.ring = [torch.zeros_like(loop.x) for _ in range(self.order)]
-        if isinstance(loop, _FusedLoopWide):
-            # fp64 clock: the statements of `_call_wide` (pred = a x_t + b mean; acc = p x_t + w_new pred; acc += w_j pred_j, oldest
-            # first) as az_axpby_f64 launches reading words 36 .. 47 of the current fp64 row: [a, b, p, w_new, w_hist x 7, 1]
-            mean, scratch = torch.empty_like(loop.x), torch.empty_like(loop.x)
-            loop.keep += [mean, scratch]
-            w = lambda k: loop.cur64.data_ptr() + 8 * (36 + k)  # noqa: E731
-            n = loop.x.numel()
-            tapes = []
-            for j in range(self.order):
-                tape = Tape()
-                loop._src = loop.x
-                loop.add_evaluation(tape)
-                loop.add_mean(tape, loop.x, mean)
-                pred = loop.ring[j]
-                tape.add("az_axpby_f64", pred.data_ptr(), w(0), loop.x.data_ptr(), w(1), mean.data_ptr(), 0, 1, n, 0)
-                acc = scratch if nh else loop.x
-                tape.add("az_axpby_f64", acc.data_ptr(), w(2), loop.x.data_ptr(), w(3), pred.data_ptr(), 0, 1, n, 0)
-                for k in range(nh):  # slot k <-> step i - nh + k (right-aligned weights: zero while that step does not exist)
-                    dst = loop.x if k == nh - 1 else scratch
-                    tape.add("az_axpby_f64", dst.data_ptr(), w(11), scratch.data_ptr(), w(4 + k),
-                             loop.ring[(j - nh + k) % self.order].data_ptr(), 0, 1, n, 0)
-                tapes.append(tape)
-            return tapes
+        return self._wide_step_tapes(loop) if loop.wide else self._narrow_step_tapes(loop)
+
+    def _wide_step_tapes(self, loop: "_FusedLoopWide") -> list[Tape]:
+        r"""fp64 clock: the statements of ``_call_wide`` (pred = a x_t + b mean; acc = p x_t + w_new pred; acc += w_j pred_j,
+        oldest first) as az_axpby_f64 launches reading the sampler's block of the current fp64 row (``_host_table_wide``)."""
+        nh, n = self.order - 1, loop.x.numel()
+        mean, scratch = torch.empty_like(loop.x), torch.empty_like(loop.x)
+        loop.keep += [mean, scratch]
+        w = lambda k: loop.cur64.data_ptr() + 8 * (ROW64_SAMPLER + k)  # noqa: E731
+        tapes = []
+        for j in range(self.order):
+            tape = Tape()
+            loop.src = None  # (no transition: every step's evaluation reads x)
+            loop.add_evaluation(tape)
+            loop.add_mean(tape, loop.x, mean)
+            pred = loop.ring[j]
+            tape.add("az_axpby_f64", pred.data_ptr(), w(0), loop.x.data_ptr(), w(1), mean.data_ptr(), 0, 1, n, 0)
+            acc = scratch if nh else loop.x
+            tape.add("az_axpby_f64", acc.data_ptr(), w(2), loop.x.data_ptr(), w(3), pred.data_ptr(), 0, 1, n, 0)
+            for k in range(nh):  # slot k <-> step i - nh + k (right-aligned weights: zero while that step does not exist)
+                dst = loop.x if k == nh - 1 else scratch
+                tape.add("az_axpby_f64", dst.data_ptr(), w(self._RING_WORDS), scratch.data_ptr(), w(4 + k),
+                         loop.ring[(j - nh + k) % self.order].data_ptr(), 0, 1, n, 0)
+            tapes.append(tape)
+        return tapes
+
+    def _narrow_step_tapes(self, loop: "_FusedLoop") -> list[Tape]:
+        r"""fp32 clock: ``az_multistep_f32`` on this step's row of ``mtable`` (``_ring_table``), then the next backbone input."""
+        dev, nh, ncols = loop.x.device, self.order - 1, self._RING_WORDS
         loop.mtable = torch.zeros(self.steps, ncols, dtype=torch.float32, device=dev)
         mrow = torch.zeros(ncols, dtype=torch.float32, device=dev)
         mean, scratch = torch.empty_like(loop.x), torch.empty_like(loop.x)
@@ -1201,6 +1045,30 @@ class _MultistepSampler(Sampler):
             tapes.append(tape)
         return tapes
 
+    def _fused_upload_extra(self, loop) -> None:
+        if not loop.wide:
+            loop.mtable.copy_(self._ring_table())
+
+    def _fused_reset(self, loop) -> None:
+        for r in loop.ring:
+            r.zero_()
+
+    @torch.no_grad()
+    @_lib.on_device
+    def __call__(self, x: Tensor, **kwargs) -> Tensor:
+        r"""Four loops: host tensors, the captured loop, and the generic device loops in fp64 (``_call_wide``) and fp32."""
+        self._check_order()
+        time = self.timesteps.to(device=x.device)
+        if not x.is_cuda:
+            return self._call_host(x, time, kwargs)
+        if type(self).__call__ is _MultistepSampler.__call__ and x.ndim >= 2 and self._clock(x) is not None:
+            out = self._call_fused(x, kwargs)
+            if out is not None:
+                return out
+        if self.dtype == torch.float64 or x.dtype == torch.float64:
+            return self._call_wide(x, time, kwargs)
+        return self._call_narrow(x, time, kwargs)
+
     def _call_wide(self, x: Tensor, time: Tensor, kwargs: dict) -> Tensor:
         r"""fp64 latents / an fp64 time grid (the reference's promotion makes every elementwise op of the loop fp64 around
         the fp32 backbone, ``sample.py:69-94``): the same linear form as the fp32 kernel -- pred = a x_t + b mean,
@@ -1222,41 +1090,8 @@ class _MultistepSampler(Sampler):
             x_t = acc
         return x_t
 
-    def _fused_upload_extra(self, loop) -> None:
-        if not isinstance(loop, _FusedLoopWide):
-            loop.mtable.copy_(self._ring_table())
-
-    def _host_table_wide(self, fused: "FusedDenoiser") -> Tensor:
-        rows = super()._host_table_wide(fused)
-        alpha, sigma = self.denoiser.schedule(torch.linspace(self.start, self.stop, self.steps + 1, dtype=self.dtype))
-        tab = self._device_table(alpha, sigma, dtype=torch.float64)
-        nh = self.order - 1
-        rows[:, 36:40] = tab[:, :4]
-        for i in range(self.steps):
-            n = min(self.order, i + 1) - 1
-            rows[i, 40 + nh - n : 40 + nh] = tab[i, 4 : 4 + n]
-        rows[:, 47] = 1.0
-        return rows
-
-    def _fused_reset(self, loop) -> None:
-        for r in loop.ring:
-            r.zero_()
-
-    @torch.no_grad()
-    @_lib.on_device
-    def __call__(self, x: Tensor, **kwargs) -> Tensor:
-        if self.order < 1 or self.order > _lib.MULTISTEP_MAX_HIST + 1:
-            raise ValueError(f"order must be in [1, {_lib.MULTISTEP_MAX_HIST + 1}], got {self.order}")
-        time = self.timesteps.to(device=x.device)
-        if not x.is_cuda:
-            return self._call_host(x, time, kwargs)
-        if type(self).__call__ is _MultistepSampler.__call__ and x.ndim >= 2 and (
-                (x.dtype == torch.float32 and self.dtype in (None, torch.float32)) or self._wide_fusable(x)):
-            out = self._call_fused(x, kwargs)
-            if out is not None:
-                return out
-        if self.dtype == torch.float64 or x.dtype == torch.float64:
-            return self._call_wide(x, time, kwargs)
+    def _call_narrow(self, x: Tensor, time: Tensor, kwargs: dict) -> Tensor:
+        r"""fp32 device tensors without a captured loop: one ``az_multistep_f32`` per step on the uploaded ``_device_table``."""
         require_f32_cuda(x, type(self).__name__)
         alpha, sigma = self.denoiser.schedule(self.timesteps.cpu())
         table = self._device_table(alpha, sigma).to(x.device)
@@ -1424,6 +1259,8 @@ class PCSampler(Sampler):
         corr = dict(alpha=alpha_t, sigma=sigma_t, a_t=alpha_t, a_s=alpha_t, k_x=keep + 0 * alpha_t, k_eps=kick * sigma_t)
         pred = dict(alpha=alpha_t, sigma=sigma_t, a_t=alpha_t, a_s=alpha_s, k_x=sigma_s / sigma_t, k_eps=0 * alpha_t)
         return [corr] * self.corrections + [pred]
+
+    _fused_wide = True  # (the loop's own blocks only)
 
     def _fused_step_tapes(self, loop):
         tape = Tape()

@@ -86,6 +86,10 @@ def test_temporaries_swapping_pool_buffers_differ():
     assert ts.signature(tape, allocs) != sig()
 
 
+def test_case_groups_selectable_with_only():
+    assert list(ts.CASES) == ["unet", "adm", "dit", "jit", "samplers"] and all(callable(f) for f in ts.CASES.values())
+
+
 def test_unknown_address_gets_an_ordinal_of_its_own():
     tape, allocs = build(BASE_A)
     known = ts.signature(tape, allocs)

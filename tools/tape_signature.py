@@ -9,7 +9,7 @@ no known allocation gets an ordinal of its own (``["?", n, 0]``) by first appear
 are addresses; no size on the plans of this package reaches that.  What a kernel reads through a table on the device (the
 descriptors of ``az_linear_small_grouped_f32``) is not on the tape; the bit-equal outputs cover it.
 
-    python tools/tape_signature.py run DIR [--only unet,adm,dit,jit]    # builds the plans below, writes signatures + outputs
+    python tools/tape_signature.py run DIR [--only unet,adm,dit,jit,samplers]    # builds the plans below, writes signatures + outputs
     python tools/tape_signature.py compare DIR_A DIR_B                  # equal signatures?  bit-equal outputs?
 """
 
@@ -369,7 +369,46 @@ def jit_cases(rec: Recorder) -> None:
             rec.save("jit.bf16", net, {"y": net(x.bfloat16(), t3.cuda(), y)})
 
 
-CASES = {"unet": unet_cases, "adm": adm_cases, "dit": dit_cases, "jit": jit_cases}
+def sampler_cases(rec: Recorder) -> None:
+    r"""Every step tape of the captured sampling loops and the sample they produce: each sampler on the fp32 clock and, where it
+    takes the captured fp64 loop, with ``dtype=float64``.  Reads ``_fused_cache`` and ``step_tapes`` only, so the same file runs
+    on an older checkout."""
+    import torch
+
+    from azula_amd import sample as S
+    from azula_amd.denoise import KarrasDenoiser
+    from azula_amd.guidance.repaint import RePaintSampler
+    from azula_amd.nn import TimeModulated, UNet
+    from azula_amd.noise import VPSchedule
+    from oracle import synth
+
+    net = TimeModulated(UNet(3, 3, hid_channels=(8, 16), hid_blocks=(1, 1), norm="group", groups=4, mod_features=16), 16, name="unet")
+    net.load_state_dict(synth.synth_state_dict(synth.shapes_of(net.state_dict()), seed=42))
+    den = KarrasDenoiser(net, VPSchedule()).cuda().eval()
+    gen = torch.Generator().manual_seed(41)
+    x1, y = torch.randn(2, 3, 16, 16, generator=gen).cuda(), torch.randn(2, 3, 16, 16, generator=gen).cuda()
+    mask = (torch.rand(2, 1, 16, 16, generator=gen) < 0.5).cuda()
+    cases = {  # name -> (class, arguments, takes the captured fp64 loop)
+        "ddim_eta0": (S.DDIMSampler, {}, True), "ddim_eta05": (S.DDIMSampler, dict(eta=0.5), True), "ddpm": (S.DDPMSampler, {}, True),
+        "euler": (S.EulerSampler, {}, True), "heun": (S.HeunSampler, {}, True), "ito_eta07": (S.ItoSampler, dict(eta=0.7), True),
+        "pc_2": (S.PCSampler, dict(corrections=2), True), "zab_3": (S.zABSampler, dict(order=3), True),
+        "repaint_2": (RePaintSampler, dict(y=y, mask=mask, iterations=2), False),
+    }
+    for name, (cls, kw, wide) in cases.items():
+        for clock, dtype in (("f32", None), ("f64", torch.float64))[: 2 if wide else 1]:
+            smp = cls(den, steps=5, silent=True, dtype=dtype, **kw)
+            torch.manual_seed(43)
+            x0 = smp(x1)
+            loop = next(iter(smp._fused_cache.values()), None)
+            assert hasattr(loop, "step_tapes"), f"{name} on the {clock} clock did not take the captured loop"
+            assert x0.dtype == (torch.float64 if dtype else torch.float32)
+            roots = [loop, *(m._plans for m in den.modules() if hasattr(m, "_plans"))]
+            plans = {j: _LoopTape(t, roots) for j, t in enumerate(loop.step_tapes)}
+            # (an fp64 sample as pairs of fp32 words: the recorder stores fp32, and the comparison is of bits)
+            rec.save(f"samplers.{name}.{clock}", den, {"x0": x0.view(torch.float32)}, plans=plans)
+
+
+CASES = {"unet": unet_cases, "adm": adm_cases, "dit": dit_cases, "jit": jit_cases, "samplers": sampler_cases}
 
 
 def run(out_dir: str, only: list[str]) -> None:
