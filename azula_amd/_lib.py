@@ -431,6 +431,14 @@ PROTOTYPES: dict[str, list] = {
     "az_op_radon_adj_f32": [vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, c_stream],
     "az_op_radon_filter_f32": [vp, vp, vp, i64, i32, f32, c_stream],
     "az_op_radon_work": [i64, i32, i32, C.POINTER(i64)],
+    "az_op_cmag_f32": [vp, i64, vp, vp, i64, i64, i64, i32, c_stream],
+    "az_op_cmag_vjp_f32": [vp, vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, c_stream],
+    "az_op_cmag_jvp_f32": [vp, i64, vp, vp, i64, vp, vp, i64, i64, i64, i32, c_stream],
+    "az_op_clip_f32": [vp, vp, i64, f32, f32, f32, c_stream],
+    "az_op_clip_jac_f32": [vp, vp, vp, i64, f32, f32, f32, c_stream],
+    "az_op_quantize_f32": [vp, vp, i64, f32, f32, f32, c_stream],
+    "az_op_pad_f32": [vp, vp, i64, i64, i64, i32, i32, i32, i32, i32, c_stream],
+    "az_op_nonlinear_trip": [C.POINTER(i64)],
     "az_tds_chunks": [i64, i64],
     "az_tds_resample_f32": [vp, vp, vp, vp, vp, i64, c_stream],
     "az_tds_propose_f32": [C.POINTER(AzTdsProposeArgs), c_stream],

@@ -15,7 +15,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["transition.hip", "layout.hip", "linear.hip", "norm.hip", "conv.hip", "wino_x3.hip", "attention.hip", "graph.hip", "rng.hip", "calib.hip", "repaint.hip", "krylov.hip", "covariance.hip", "backward.hip", "tds.hip", "attention_bwd.hip", "backward_adm.hip", "vdm.hip", "operators.hip", "fft.hip", "radon.hip", "coil.hip"]
+SOURCES = ["transition.hip", "layout.hip", "linear.hip", "norm.hip", "conv.hip", "wino_x3.hip", "attention.hip", "graph.hip", "rng.hip", "calib.hip", "repaint.hip", "krylov.hip", "covariance.hip", "backward.hip", "tds.hip", "attention_bwd.hip", "backward_adm.hip", "vdm.hip", "operators.hip", "fft.hip", "radon.hip", "coil.hip", "nonlinear.hip"]
 LIB = os.path.join(HERE, "libazula_amd.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 FLAGS = [

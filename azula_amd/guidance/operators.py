@@ -1,12 +1,13 @@
 r"""Measurement operators for the guidance methods: pixel mask, average-pool downsampling, separable blur, general 2-D PSF
 (motion blur), decimation (bicubic super-resolution), per-pixel channel mix (colourisation), the 2-D Fourier transform (k-space
-undersampling: accelerated MRI) and the parallel-beam Radon transform (sparse-view and limited-angle CT), with exact adjoints and
-(where one exists) the pseudo-inverse.
+undersampling: accelerated MRI), the parallel-beam Radon transform (sparse-view and limited-angle CT) and zero padding, with exact
+adjoints and (where one exists) the pseudo-inverse; and the nonlinear ones on :class:`NonlinearOperator`, whose derivative depends
+on where it is taken: the magnitude of a split-complex image (Fourier phase retrieval), saturation (HDR) and quantisation.
 
 The guidance classes take the operator :math:`A` of :math:`y = A x + n` as a callable and differentiate it with
 ``torch.autograd.grad`` (DPS, TMPD, MMPS, JFPS, DiffPIR) and ``torch.func.jvp`` (MMPS, JFPS).  The operators below are such
-callables whose maps are kernels of ``csrc/operators.hip``, ``csrc/fft.hip``, ``csrc/coil.hip`` and ``csrc/radon.hip``: no autograd
-graph of torch ops, no atomics (two runs give the same bits) and a fixed launch sequence.  The project's own extension: the
+callables whose maps are kernels of ``csrc/operators.hip``, ``csrc/fft.hip``, ``csrc/coil.hip``, ``csrc/radon.hip`` and
+``csrc/nonlinear.hip``: no autograd graph of torch ops, no atomics (two runs give the same bits) and a fixed launch sequence.  The project's own extension: the
 reference has no operator library.
 
     A = DownsampleOperator(2, flatten=True) @ BlurOperator.gaussian(1.0, 5)
@@ -18,6 +19,9 @@ reference has no operator library.
     MRIOperator(cartesian_mask(256, 256, 4), flatten=True)                       # 4x accelerated single-coil MRI
     MultiCoilMRIOperator(cartesian_mask(256, 256, 4), birdcage_maps(8, 256, 256), flatten=True)   # 8-coil SENSE MRI
     RadonOperator(radon_angles(30), (256, 256), flatten=True)                    # sparse-view CT, 30 views
+    DPSSampler(denoiser, y, PhaseRetrievalOperator(64, flatten=True))            # phase retrieval, 128 -> 256: 2x oversampling
+    DPSSampler(denoiser, y, ClipOperator(gain=2.0, flatten=True))                # HDR: saturation of a twice over-exposed image
+    PGDMSampler(denoiser, y, QuantizeOperator(16), lambda y: y)                  # 4-bit images: no derivative of A is taken
 
 Two paths, as ``RePaintSampler`` has them:
 
@@ -34,6 +38,10 @@ ops.  ``_TRANSPOSE`` lists every mode the two implement with the mode that is it
 ``_STRIDED = True`` sends strided fp32 device tensors to the kernels too (made contiguous first) where the torch path has no
 use for them, and ``_check_kernel_input`` refuses what the kernels cannot take.  Device constants come from ``_constant``; a
 public map of an observation (``pinv``, ``fbp``) is one call of ``_from_observation``.
+
+A nonlinear operator subclasses :class:`NonlinearOperator` the same way, with the map as ``_kernel(x)`` / ``_torch(x)`` and its
+linearisation at ``x`` as ``_jac_kernel(x, v, mode)`` / ``_jac_torch(x, v, mode)``; ``N.jacobian(x)`` is a :class:`LinearOperator`,
+and ``@`` chains operators of both kinds.
 """
 
 from __future__ import annotations
@@ -53,12 +61,15 @@ from .repaint import _aligned, _broadcasts_to
 
 __all__ = ["LinearOperator", "MaskOperator", "DownsampleOperator", "BlurOperator", "gaussian_taps", "PSFOperator", "motion_psf",
            "DecimateOperator", "bicubic_taps", "ChannelMixOperator", "FourierOperator", "MRIOperator", "cartesian_mask",
-           "MultiCoilMRIOperator", "birdcage_maps", "RadonOperator", "radon_angles"]
+           "MultiCoilMRIOperator", "birdcage_maps", "RadonOperator", "radon_angles", "PadOperator", "NonlinearOperator",
+           "MagnitudeOperator", "PhaseRetrievalOperator", "ClipOperator", "QuantizeOperator"]
 
 MAX_FACTOR, MAX_TAPS = 16, 65  # (the limits of az_op_avgpool_f32 / az_op_decimate_f32 and of az_op_blur_f32 / az_op_psf_f32)
 MAX_CHANNELS = 16  # (the limit of az_op_chanmix_f32)
 MAX_FFT = 1024  # (AZ_OP_FFT2_MAX: the largest height or width of az_op_fft2_f32)
 MAX_RADON_SIZE, MAX_RADON_DET, MAX_RADON_ANGLES = 1024, 2048, 4096  # (AZ_OP_RADON_MAX_SIZE / _DET / _ANGLES)
+MAX_PAD = 1 << 20  # (the limit of az_op_pad_f32 per side)
+MAX_LEVELS = 1 << 24  # (QuantizeOperator: the level index is an exact fp32 integer)
 
 
 def _launch(name: str, *args) -> None:
@@ -1389,3 +1400,507 @@ class RadonOperator(LinearOperator):
     def fbp(self, y: Tensor) -> Tensor:
         r"""Filtered back-projection of a :math:`(B, C, A, D)` or flat sinogram: :math:`(\pi / A) A^\top (h * y)`."""
         return self._from_observation(y, "fbp")
+
+
+# --------------------------------------------------------------------------------------------------------------- padding
+class PadOperator(LinearOperator):
+    r"""Creates the zero padding of every plane from :math:`H \times W` to
+    :math:`(t + H + b) \times (l + W + r)` (the support constraint of phase retrieval: oversampling of the spectrum).
+
+    Arguments:
+        pad: The number of zeros on each side, an int or ``(top, bottom, left, right)``, none negative.
+        flatten, in_shape: See :class:`LinearOperator`.
+
+    The adjoint is the crop.  :math:`P^\top P = I`, so ``pinv`` is the crop too.
+    """
+
+    _TRANSPOSE = _WITH_PINV
+    _STRIDED = True  # (a strided view too: the Function makes it contiguous)
+
+    def __init__(self, pad: int | Sequence[int], flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        sides = (pad,) * 4 if isinstance(pad, int) else tuple(pad) if isinstance(pad, Sequence) else ()
+        if len(sides) != 4 or not all(isinstance(p, int) and 0 <= p <= MAX_PAD for p in sides):
+            raise ValueError(f"pad is an int or (top, bottom, left, right), each in 0 .. {MAX_PAD}, got {pad}")
+        self.pad = sides
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        (c, h, w), (t, b, l, r) = in_shape, self.pad
+        return (c, h + t + b, w + l + r)
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        (c, h, w), (t, b, l, r) = out_shape, self.pad
+        if h < t + b or w < l + r:
+            raise ValueError(f"a plane padded by {self.pad} is at least {t + b} x {l + r}, got {h} x {w}")
+        return (c, h - t - b, w - l - r)
+
+    def _kernel(self, x: Tensor, mode: str) -> Tensor:
+        crop = mode in ("adjoint", "pinv")
+        B, c = x.shape[:2]
+        _, h, w = self._in_shape_of(tuple(x.shape[1:])) if crop else x.shape[1:]
+        y = _aligned(x.new_empty(B, c, h, w) if crop else x.new_empty(B, *self._out_shape((c, h, w))), 16)
+        if y.numel():
+            _launch("az_op_pad_f32", y.data_ptr(), x.data_ptr(), B * c, h, w, *self.pad, int(crop))
+        return y
+
+    def _torch(self, x: Tensor, mode: str) -> Tensor:
+        t, b, l, r = self.pad
+        if mode in ("apply", "pinv_t"):
+            return F.pad(x, (l, r, t, b))
+        return x[:, :, t:x.shape[2] - b, l:x.shape[3] - r]
+
+    def pinv(self, y: Tensor) -> Tensor:
+        return self._from_observation(y, "pinv")
+
+
+# ------------------------------------------------------------------------------------------------------------- nonlinear
+class _Map(torch.autograd.Function):
+    r"""``op``'s map: :class:`_Apply` for a :class:`NonlinearOperator`.  ``backward`` and ``jvp`` are applications of
+    :class:`_Linearised` at the saved ``x``.  What :class:`_Apply` says about ``torch.func`` holds here and more: the saved ``x`` is
+    a wrapper without storage too, so it is handed to :class:`_Linearised` as a TENSOR ARGUMENT, which functorch unwraps level by
+    level down to ``forward``; an operating point kept on the operator object would stay a wrapper."""
+
+    @staticmethod
+    def forward(x: Tensor, op: NonlinearOperator) -> Tensor:
+        if not _to_kernels(x, True):  # (reached through NonlinearOperator._function only)
+            return op._torch(x)
+        with device_context(x):
+            return op._kernel(_aligned(x.contiguous(), 16))
+
+    @staticmethod
+    def setup_context(ctx, inputs, output) -> None:
+        x, ctx.op = inputs
+        ctx.save_for_backward(x)
+        ctx.save_for_forward(x)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return _linearised(g, ctx.saved_tensors[0], ctx.op, "adjoint"), None
+
+    @staticmethod
+    def jvp(ctx, tx: Tensor, *_):
+        return _linearised(tx, ctx.saved_tensors[0], ctx.op, "apply")
+
+
+class _FirstOrderOnly(torch.autograd.Function):
+    r"""The identity on an operating point ``x`` on its way into :class:`_Linearised`, whose derivative raises: a second derivative
+    of the operator is not implemented on the kernel path, and must not silently be zero.  A node of its own, so that it raises
+    only where a derivative THROUGH ``x`` is asked for: autograd never reaches it while it differentiates a Jacobian with respect
+    to what it is applied to."""
+
+    @staticmethod
+    def forward(x: Tensor, op: NonlinearOperator) -> Tensor:
+        return x.view_as(x)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output) -> None:
+        ctx.op = inputs[1]
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise NotImplementedError(f"a derivative of {type(ctx.op).__name__}'s Jacobian with respect to the point where it is taken "
+                                  "(a second derivative of the operator) is not implemented on the kernel path")
+
+    jvp = backward
+
+
+class _Linearised(torch.autograd.Function):
+    r"""``op``'s Jacobian at ``x`` ("apply") or its transpose ("adjoint") applied to ``v``.  Linear in ``v``: the tangent map with
+    respect to ``v`` is the same map, its pullback the transposed one, both at the same ``x``.  ``x`` comes through
+    :class:`_FirstOrderOnly` (:func:`_linearised`), which answers every derivative with respect to it."""
+
+    @staticmethod
+    def forward(v: Tensor, x: Tensor, op: NonlinearOperator, mode: str) -> Tensor:
+        if not (_to_kernels(x, True) and _to_kernels(v, True)):  # (reached through NonlinearOperator._function only)
+            return op._jac_torch(x, v, mode)
+        with device_context(x):
+            return op._jac_kernel(_aligned(x.contiguous(), 16), _aligned(v.contiguous(), 16), mode)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output) -> None:
+        _, x, ctx.op, ctx.mode = inputs
+        ctx.save_for_backward(x)
+        ctx.save_for_forward(x)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x = ctx.saved_tensors[0]
+        # x's slot: a stand-in that autograd hands on to _FirstOrderOnly.backward, and only where x's derivative is asked for
+        gx = g.new_zeros(()).expand_as(x) if ctx.needs_input_grad[1] else None
+        return _Linearised.apply(g, x, ctx.op, _TRANSPOSED[ctx.mode]), gx, None, None
+
+    @staticmethod
+    def jvp(ctx, tv: Tensor, tx, *_):
+        if tv is None:  # (only x moves: _FirstOrderOnly.jvp has raised before this is reached)
+            raise NotImplementedError("a derivative with respect to the operating point of a Jacobian is not implemented")
+        return _Linearised.apply(tv, ctx.saved_tensors[0], ctx.op, ctx.mode)
+
+
+def _linearised(v: Tensor, x: Tensor, op: NonlinearOperator, mode: str) -> Tensor:
+    r"""Every application of :class:`_Linearised` from outside itself."""
+    return _Linearised.apply(v, _FirstOrderOnly.apply(x, op), op, mode)
+
+
+_TRANSPOSED = {"apply": "adjoint", "adjoint": "apply"}
+
+
+def _chw(in_shape: Sequence[int] | None) -> tuple | None:
+    r"""An ``in_shape`` argument as a tuple (C, H, W), or ``None``."""
+    if in_shape is None:
+        return None
+    shape = tuple(int(s) for s in in_shape)
+    if len(shape) != 3:
+        raise ValueError(f"in_shape is (C, H, W), got {shape}")
+    return shape
+
+
+class NonlinearOperator:
+    r"""A differentiable map :math:`N` on images :math:`(B, C, H, W)` whose derivative depends on where it is taken: what
+    ``DPSSampler``, ``TDSSampler`` (through its twist) and ``PGDMSampler`` take as a general callable ``A``.  Beside
+    :class:`LinearOperator`, not under it: there is no adjoint of the map itself.
+
+    Arguments:
+        flatten: Whether the observation is flattened to :math:`(B, D)`.
+        in_shape: The shape :math:`(C, H, W)` of an input.  Taken from the last forward call when not given.
+
+    ``N(x)`` is the observation.  ``N.jacobian(x)`` is the linearisation at ``x``, a :class:`LinearOperator`:
+    ``N.jacobian(x)(t)`` is the directional derivative, ``.adjoint(w)`` the pullback (of a flat or an image-shaped ``w``), with
+    ``.T`` and ``@`` as usual.  ``N @ A``, ``A @ N`` and ``N2 @ N1`` chain operators of either kind; the chain's Jacobian is the
+    chain rule.
+
+    Dispatch is the file's one rule.  Contiguous fp32 device tensors (strided ones too, made contiguous first) go to the kernels
+    through one ``torch.autograd.Function`` whose ``backward(g)`` is ``jacobian(x).adjoint(g)`` and whose ``jvp(t)`` is
+    ``jacobian(x)(t)``, so ``autograd.grad``, ``torch.func.vjp`` and ``torch.func.jvp`` end in the same launches.  Everything
+    else (host, fp64, half) takes a plain torch op sequence that torch differentiates itself.  On the kernel path a second
+    derivative through ``x`` raises ``NotImplementedError``.
+
+    A subclass states ``_out_shape`` / ``_in_shape_of`` as a :class:`LinearOperator` does, the map as ``_kernel(x)`` and
+    ``_torch(x)``, and its Jacobian (``mode`` "apply") and the transpose ("adjoint") as ``_jac_kernel(x, v, mode)`` and
+    ``_jac_torch(x, v, mode)``.
+    """
+
+    def __init__(self, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        self.flatten = bool(flatten)
+        self.in_shape = _chw(in_shape)
+
+    # -- what a subclass defines ----------------------------------------------------------------------------------------
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        return in_shape
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        return out_shape
+
+    def _kernel(self, x: Tensor) -> Tensor:
+        raise NotImplementedError
+
+    def _torch(self, x: Tensor) -> Tensor:
+        raise NotImplementedError
+
+    def _jac_kernel(self, x: Tensor, v: Tensor, mode: str) -> Tensor:
+        raise NotImplementedError
+
+    def _jac_torch(self, x: Tensor, v: Tensor, mode: str) -> Tensor:
+        raise NotImplementedError
+
+    # -- what the base class does with it -------------------------------------------------------------------------------
+    def _function(self, x: Tensor) -> Tensor:
+        r"""The map through the Function of the kernel path, whatever ``x`` is (a host or fp64 tensor runs the torch ops inside
+        it): how the Function's rules are tested without a device."""
+        return _Map.apply(x, self)
+
+    def _checked(self, x: Tensor) -> None:
+        if x.ndim != 4:
+            raise ValueError(f"{type(self).__name__} takes a (B, C, H, W) tensor, got {tuple(x.shape)}")
+        self._out_shape(tuple(x.shape[1:]))
+
+    # -- the public maps ------------------------------------------------------------------------------------------------
+    def __call__(self, x: Tensor) -> Tensor:
+        self._checked(x)
+        self.in_shape = tuple(x.shape[1:])
+        y = _Map.apply(x, self) if _to_kernels(x, True) else self._torch(x)
+        return y.flatten(1) if self.flatten else y
+
+    def jacobian(self, x: Tensor) -> LinearOperator:
+        r"""The linearisation of the operator at ``x``."""
+        self._checked(x)
+        return _Jacobian(self, x)
+
+    def __matmul__(self, other):
+        if not isinstance(other, (LinearOperator, NonlinearOperator)):
+            return NotImplemented
+        return _Chain(self, other)
+
+    def __rmatmul__(self, other):  # (a LinearOperator on the left: its own __matmul__ returns NotImplemented for us)
+        if not isinstance(other, LinearOperator):
+            return NotImplemented
+        return _Chain(other, self)
+
+
+class _Jacobian(LinearOperator):
+    r"""``N.jacobian(x)``.  The operating point is a tensor argument of every application of :class:`_Linearised`.  Every shape
+    comes from ``x``: the kernels take their counts from it, so what the Jacobian is applied to has exactly the shape of ``x``
+    ("apply") or of ``N(x)`` ("adjoint"), and nothing a call receives replaces the recorded one."""
+
+    def __init__(self, op: NonlinearOperator, x: Tensor) -> None:
+        super().__init__(op.flatten, tuple(x.shape[1:]))
+        self.op, self.x = op, x
+        self._out_shape, self._in_shape_of = op._out_shape, op._in_shape_of
+
+    def _run(self, v: Tensor, mode: str) -> Tensor:
+        x = self.x
+        want = (x.shape[0], *(self.in_shape if mode == "apply" else self._out_shape(self.in_shape)))
+        if tuple(v.shape) != want:
+            raise ValueError(f"the Jacobian of {type(self.op).__name__} at a point of shape {tuple(x.shape)} "
+                             f"{'takes' if mode == 'apply' else 'pulls back'} a tensor of shape {want}, got {tuple(v.shape)}")
+        if _to_kernels(x, True) and _to_kernels(v, True):
+            return _linearised(v, x, self.op, mode)
+        return self.op._jac_torch(x, v, mode)
+
+    def __call__(self, t: Tensor) -> Tensor:
+        y = self._run(t, "apply")
+        return y.flatten(1) if self.flatten else y
+
+    def adjoint(self, w: Tensor) -> Tensor:
+        return self._run(self._image(w, "adjoint"), "adjoint")
+
+
+class _Chain(NonlinearOperator):
+    r"""``P_k @ ... @ P_1`` with at least one nonlinear part: :math:`x \mapsto P_k(\dots P_1(x))`, every part with its own dispatch
+    and its own Function.  The Jacobian at ``x`` is the composition of the parts' Jacobians (a linear part is its own), each taken
+    at the point the parts before it map ``x`` to: the chain rule, as the ``A2 @ A1`` of :class:`LinearOperator` s.  Only the
+    outermost part may flatten."""
+
+    def __init__(self, *parts, in_shape: Sequence[int] | None = None) -> None:  # (outermost first, as written)
+        self.in_shape = _chw(in_shape)  # (no flatten of its own: the outermost part's)
+        self.parts = tuple(q for p in parts for q in (p.parts if isinstance(p, _Chain) else (p,)))
+        if any(p.flatten for p in self.parts[1:]):
+            raise ValueError("only the outermost operator of a composition may flatten its observation")
+
+    @property
+    def flatten(self) -> bool:
+        return self.parts[0].flatten
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        for p in reversed(self.parts):
+            in_shape = p._out_shape(in_shape)
+        return in_shape
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        for p in self.parts:
+            out_shape = p._in_shape_of(out_shape)
+        return out_shape
+
+    def __call__(self, x: Tensor) -> Tensor:
+        self._checked(x)
+        self.in_shape = tuple(x.shape[1:])
+        for p in reversed(self.parts):
+            x = p(x)
+        return x
+
+    def jacobian(self, x: Tensor) -> LinearOperator:
+        self._checked(x)
+        J = None
+        for k, p in enumerate(reversed(self.parts)):
+            Jp = p.jacobian(x) if isinstance(p, NonlinearOperator) else p
+            J = Jp if J is None else Jp @ J
+            if k + 1 < len(self.parts):
+                x = p(x)  # (the next part's operating point: the forward launches again, nothing is kept between calls)
+            elif isinstance(p, LinearOperator):
+                p.in_shape = tuple(x.shape[1:])  # (what a call would record: a flat cotangent is un-flattened with it)
+        return J
+
+
+class MagnitudeOperator(NonlinearOperator):
+    r"""Creates the magnitude :math:`|z|` (or the intensity :math:`|z|^2`) of a split-complex image: a :math:`(B, 2 C, H, W)` input
+    whose channels :math:`[0, C)` are :math:`\Re z` and :math:`[C, 2 C)` are :math:`\Im z`, as :class:`FourierOperator` writes
+    them, gives :math:`(B, C, H, W)`.
+
+    Arguments:
+        squared: Whether the observation is the intensity :math:`|z|^2`.
+        flatten, in_shape: See :class:`NonlinearOperator`.
+
+    The Jacobian at :math:`z` maps :math:`t` to :math:`(\Re z \, t_{re} + \Im z \, t_{im}) / |z|` and its transpose :math:`w` to
+    :math:`w \, (\Re z, \Im z) / |z|`; both are exactly 0 where :math:`z = 0` (torch's ``sgn`` convention for ``abs`` of a complex
+    tensor).  ``squared``: :math:`2 (\Re z \, t_{re} + \Im z \, t_{im})` and :math:`2 w (\Re z, \Im z)`.  The kernels
+    (``az_op_cmag_f32`` and its ``_vjp`` / ``_jvp``) scale by a power of two first, so nothing overflows or underflows wherever
+    :math:`|z|` is a normal number.  Half precision is not provided.
+    """
+
+    def __init__(self, squared: bool = False, flatten: bool = False, in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(flatten, in_shape)
+        self.squared = bool(squared)
+
+    def _out_shape(self, in_shape: tuple) -> tuple:
+        if in_shape[0] % 2:
+            raise ValueError(f"a split-complex image has an even channel count (re, then im), got {in_shape[0]}")
+        return (in_shape[0] // 2, *in_shape[1:])
+
+    def _in_shape_of(self, out_shape: tuple) -> tuple:
+        return (2 * out_shape[0], *out_shape[1:])
+
+    def _kernel(self, x: Tensor) -> Tensor:
+        B, c2, h, w = x.shape
+        n = c2 // 2 * h * w
+        y = _aligned(x.new_empty(B, c2 // 2, h, w), 16)
+        if y.numel():
+            _launch("az_op_cmag_f32", y.data_ptr(), n, x.data_ptr(), x.data_ptr() + 4 * n, 2 * n, B, n, int(self.squared))
+        return y
+
+    def _jac_kernel(self, x: Tensor, v: Tensor, mode: str) -> Tensor:
+        B, c2, h, w = x.shape
+        n = c2 // 2 * h * w
+        z = x.data_ptr(), x.data_ptr() + 4 * n, 2 * n  # (re, im, sample stride)
+        if mode == "apply":
+            y = _aligned(x.new_empty(B, c2 // 2, h, w), 16)
+            if y.numel():
+                _launch("az_op_cmag_jvp_f32", y.data_ptr(), n, v.data_ptr(), v.data_ptr() + 4 * n, 2 * n, *z, B, n, int(self.squared))
+            return y
+        d = _aligned(torch.empty_like(x), 16)
+        if d.numel():
+            _launch("az_op_cmag_vjp_f32", d.data_ptr(), d.data_ptr() + 4 * n, 2 * n, v.data_ptr(), n, *z, B, n, int(self.squared))
+        return d
+
+    def _parts(self, x: Tensor) -> tuple[Tensor, Tensor]:
+        if x.dtype not in (torch.float32, torch.float64):
+            raise NotImplementedError(f"MagnitudeOperator runs in fp32 and fp64, got {x.dtype}")
+        c = x.shape[1] // 2
+        return x[:, :c], x[:, c:]
+
+    def _torch(self, x: Tensor) -> Tensor:
+        re, im = self._parts(x)
+        return re * re + im * im if self.squared else torch.complex(re, im).abs()
+
+    def _jac_torch(self, x: Tensor, v: Tensor, mode: str) -> Tensor:
+        re, im = self._parts(x)
+        if self.squared:
+            u_re, u_im = 2 * re, 2 * im
+        else:
+            inv = _reciprocal_or_zero(torch.complex(re, im).abs())
+            u_re, u_im = re * inv, im * inv
+        if mode == "apply":
+            c = x.shape[1] // 2
+            return u_re * v[:, :c] + u_im * v[:, c:]
+        return torch.cat([v * u_re, v * u_im], dim=1)
+
+
+def _finite(*values: float) -> bool:
+    return all(isinstance(v, (int, float)) and math.isfinite(v) for v in values)
+
+
+class _ClampedOperator(NonlinearOperator):
+    r"""What :class:`ClipOperator` and :class:`QuantizeOperator` share: the bounds, and the Jacobian of
+    ``clamp(gain * x, low, high)`` -- ``gain`` where ``low <= gain * x <= high`` (bounds inclusive, ``torch.clamp``'s backward),
+    0 elsewhere and where ``x`` is NaN.  Diagonal, so its own transpose: one kernel entry, ``az_op_clip_jac_f32``."""
+
+    gain = 1.0
+
+    def __init__(self, low: float, high: float, flatten: bool, in_shape: Sequence[int] | None) -> None:
+        super().__init__(flatten, in_shape)
+        if not _finite(low, high) or not low < high:
+            raise ValueError(f"{type(self).__name__} needs finite bounds with low < high, got low {low}, high {high}")
+        self.low, self.high = float(low), float(high)
+
+    def _jac_kernel(self, x: Tensor, v: Tensor, mode: str) -> Tensor:
+        d = _aligned(torch.empty_like(x), 16)
+        if d.numel():
+            _launch("az_op_clip_jac_f32", d.data_ptr(), v.data_ptr(), x.data_ptr(), x.numel(), self.gain, self.low, self.high)
+        return d
+
+    def _jac_torch(self, x: Tensor, v: Tensor, mode: str) -> Tensor:
+        u = self.gain * x
+        return torch.where((u >= self.low) & (u <= self.high), v, torch.zeros_like(v)) * self.gain
+
+
+class ClipOperator(_ClampedOperator):
+    r"""Creates sensor saturation :math:`x \mapsto \min(\max(g x, l), h)`.  The HDR task of the DPS paper is
+    ``ClipOperator(gain=2.0)``.
+
+    Arguments:
+        low, high: The bounds :math:`l < h`, finite.
+        gain: The factor :math:`g`, finite.
+        flatten, in_shape: See :class:`NonlinearOperator`.
+
+    The Jacobian at :math:`x` is diagonal: :math:`g` where :math:`l \le g x \le h` -- the bounds are inclusive, as in
+    ``torch.clamp``'s backward -- and 0 elsewhere.  A NaN stays NaN and passes no cotangent.
+    """
+
+    def __init__(self, low: float = -1.0, high: float = 1.0, gain: float = 1.0, flatten: bool = False,
+                 in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(low, high, flatten, in_shape)
+        if not _finite(gain):
+            raise ValueError(f"ClipOperator needs a finite gain, got {gain}")
+        self.gain = float(gain)
+
+    def _kernel(self, x: Tensor) -> Tensor:
+        y = _aligned(torch.empty_like(x), 16)
+        if y.numel():
+            _launch("az_op_clip_f32", y.data_ptr(), x.data_ptr(), x.numel(), self.gain, self.low, self.high)
+        return y
+
+    def _torch(self, x: Tensor) -> Tensor:
+        return torch.clamp(self.gain * x, self.low, self.high)
+
+
+class QuantizeOperator(_ClampedOperator):
+    r"""Creates bit-depth reduction: ``levels`` evenly spaced values from ``low`` to ``high``,
+    :math:`x \mapsto \mathrm{rint}((u - l) / s) \, s + l` with :math:`u = \min(\max(x, l), h)` and the step
+    :math:`s = (h - l) / (\text{levels} - 1)` rounded to fp32; halves round to even.
+
+    Arguments:
+        levels: The number of values, at least 2 (256: 8 bits).
+        low, high: The range :math:`l < h`, finite.
+        flatten, in_shape: See :class:`NonlinearOperator`.
+
+    The map is piecewise constant: its derivative is 0 almost everywhere.  ``jacobian(x)`` is therefore the STRAIGHT-THROUGH one,
+    the clamp's -- 1 where :math:`l \le x \le h`, 0 elsewhere (``az_op_clip_jac_f32`` with gain 1) -- which is what gradient
+    guidance (``DPSSampler``) then follows.  ``PGDMSampler(denoiser, y, Q, lambda y: y)`` needs no derivative of the operator at
+    all: it only calls ``Q`` and ``A_inv``.
+    """
+
+    def __init__(self, levels: int, low: float = -1.0, high: float = 1.0, flatten: bool = False,
+                 in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(low, high, flatten, in_shape)
+        if not (isinstance(levels, int) and 2 <= levels <= MAX_LEVELS):
+            raise ValueError(f"levels is an int in 2 .. {MAX_LEVELS}, got {levels}")
+        self.levels = levels
+        self.step = float(torch.tensor((self.high - self.low) / (levels - 1), dtype=torch.float32))  # (as the kernel receives it)
+        if not self.step > 0:
+            raise ValueError(f"the step of {levels} levels from {low} to {high} is not a positive fp32 number")
+
+    def _kernel(self, x: Tensor) -> Tensor:
+        y = _aligned(torch.empty_like(x), 16)
+        if y.numel():
+            _launch("az_op_quantize_f32", y.data_ptr(), x.data_ptr(), x.numel(), self.low, self.high, self.step)
+        return y
+
+    def _torch(self, x: Tensor) -> Tensor:
+        r"""The kernel's sequence.  ``round`` has a zero derivative, so the straight-through rule is written out: the value of
+        the sequence, the gradient of the clamp."""
+        u = torch.clamp(x, self.low, self.high)
+        q = torch.round((u - self.low) / self.step) * self.step + self.low
+        return q.detach() + (u - u.detach())  # (q + 0 exactly; a NaN stays NaN)
+
+
+class PhaseRetrievalOperator(_Chain):
+    r"""Creates Fourier phase retrieval, the task of the DPS paper: the magnitude of the oversampled spectrum of a real image,
+    exactly ``MagnitudeOperator(squared) @ FourierOperator(norm) @ PadOperator(pad)``.  A :math:`(B, C, H, W)` input gives
+    :math:`(B, C, t + H + b, l + W + r)`.
+
+    Arguments:
+        pad: The zero padding, see :class:`PadOperator`.  ``PhaseRetrievalOperator(H // 2)`` is 2x oversampling of an
+            :math:`H \times H` image.
+        norm: See :class:`FourierOperator`.
+        squared: See :class:`MagnitudeOperator`.
+        flatten, in_shape: See :class:`NonlinearOperator`.
+
+    On fp32 device tensors the PADDED size follows :class:`FourierOperator`'s rule: powers of two up to 1024, else
+    ``NotImplementedError``.  The launches are ``az_op_pad_f32``, ``az_op_fft2_f32`` and ``az_op_cmag_f32``, and
+    ``az_op_cmag_vjp_f32`` / ``az_op_cmag_jvp_f32`` with the first two again for a derivative.
+
+    Out of scope: non-power-of-two transforms on the device, half-precision kernel paths (half tensors take the torch path where
+    it has one), JPEG and other block-transform degradations, and second derivatives through the operating point.
+    """
+
+    def __init__(self, pad: int | Sequence[int], norm: str = "ortho", squared: bool = False, flatten: bool = False,
+                 in_shape: Sequence[int] | None = None) -> None:
+        super().__init__(MagnitudeOperator(squared, flatten), FourierOperator(norm), PadOperator(pad), in_shape=in_shape)

@@ -301,6 +301,61 @@ int az_op_radon_filter_f32(float* dst, const float* src, const float* taps, int6
                            az_stream_t stream);
 int az_op_radon_work(int64_t planes, int32_t H, int32_t W, int64_t* floats);
 
+/* ---- Nonlinear measurement maps and their linearisations (csrc/nonlinear.hip; MagnitudeOperator, ClipOperator, QuantizeOperator,
+ * PadOperator) -------------------------------------------------------------------------------------------------------------
+ * Elementwise fp32 maps whose derivative depends on where it is taken: the linearisation entries receive the operating point (z or
+ * x) again and re-read it -- the forward entries save nothing.  The cmag entries take SPLIT-complex data in az_op_fft2_f32's
+ * convention: sample b of a tensor is the n floats at base + b * bstride, and the real and imaginary parts have separate bases, so
+ * the two halves of a (B, 2 C, H, W) tensor are passed in place (n = C H W, bstride = 2 n).  One work item owns 4 consecutive
+ * floats: bases and strides that are multiples of 4 floats with n % 4 == 0 take 16-byte loads and stores, anything else a scalar
+ * form.  No atomics; a sample's result does not depend on the other samples of the launch.
+ *
+ * az_op_cmag_f32: y = |z|, z = re + i im, or |z|^2 (squared = 1).  With h / l the part of larger / smaller magnitude and e the
+ * exponent that brings |h| into [0.5, 1): a = |h| 2^-e, b = |l| 2^-e, y = sqrt(fma(a, a, b b)) 2^e with b b rounded on its own and
+ * an IEEE square root: no overflow or underflow wherever |z| is a normal number, within 2^-23 |z|, exact on integer Pythagorean
+ * pairs below 2^12 at any scale.  squared: fma(re, re, im im), Inf beyond fp32's range.  A NaN part gives NaN.  12 bytes / element.
+ *
+ * az_op_cmag_vjp_f32: (d_re, d_im) = g u with the unit vector u = (re, im) / |z| = (re 2^-e / s, im 2^-e / s), s = |z| 2^-e as
+ * above and one IEEE division per part, and exactly (0, 0) where z = 0 whatever g is: torch's sgn convention for abs of a complex
+ * tensor.  squared: (2 g) re, (2 g) im, one rounding each.  20 bytes / element.
+ *
+ * az_op_cmag_jvp_f32: t_y = fma(u_re, t_re, u_im t_im), 0 where z = 0.  squared: 2 fma(re, t_re, im t_im).  20 bytes / element.
+ *
+ * az_op_clip_f32: y = min(max(gain x, lo), hi): the product rounded once, a NaN stays NaN and a zero keeps its sign -- what
+ * torch.clamp(gain * x, lo, hi) gives.  8 bytes / element.
+ *
+ * az_op_clip_jac_f32: d = (lo <= gain x <= hi ? g : 0) gain -- bounds INCLUSIVE, 0 where x is NaN: torch.clamp's backward followed
+ * by the product's.  The Jacobian is diagonal, so the entry is the vjp and the jvp.  12 bytes / element.
+ *
+ * az_op_quantize_f32: u = min(max(x, lo), hi), q = fadd(fmul(rint(fdiv(fsub(u, lo), step)), step), lo), every operation rounded
+ * once and never fused, rint to nearest even: torch.round((torch.clamp(x, lo, hi) - lo) / step) * step + lo.  8 bytes / element.
+ * Its straight-through linearisation is az_op_clip_jac_f32 with gain 1.
+ *
+ * az_op_pad_f32: zero padding of `planes` contiguous H x W planes to (top + H + bottom) x (left + W + right) in one launch, every
+ * destination float written exactly once; adjoint = 1 is the crop, from the padded planes `src` to H x W planes `dst` (H and W
+ * are the SMALL plane's in both directions).  16-byte form where W, left + W + right and left are multiples of 4.
+ *
+ * Limits.  cmag: B, n >= 0, n <= 2^40, strides >= 0 and, for B > 1, at least n; squared 0 or 1.  clip, quantize: n >= 0, finite
+ * parameters, lo < hi, step > 0.  pad: planes, H, W, pads >= 0, each of H, W and the pads at most 2^20; adjoint 0 or 1 (else
+ * AZ_E_SHAPE).  An empty tensor (B == 0 or n == 0, no destination float) launches nothing and returns AZ_OK.  Every pointer is
+ * required (AZ_E_NULL) and 4-byte aligned (AZ_E_ALIGN); no destination shares a float with another destination or with a source
+ * -- never in place (AZ_E_SHAPE).
+ *
+ * az_op_nonlinear_trip: the floats one trip of the capped grid covers (a launch of more walks the grid-stride loop again).  Host
+ * arithmetic. */
+int az_op_cmag_f32(float* y, int64_t y_bstride, const float* z_re, const float* z_im, int64_t z_bstride, int64_t B, int64_t n,
+                   int32_t squared, az_stream_t stream);
+int az_op_cmag_vjp_f32(float* d_re, float* d_im, int64_t d_bstride, const float* g, int64_t g_bstride, const float* z_re,
+                       const float* z_im, int64_t z_bstride, int64_t B, int64_t n, int32_t squared, az_stream_t stream);
+int az_op_cmag_jvp_f32(float* t_y, int64_t y_bstride, const float* t_re, const float* t_im, int64_t t_bstride, const float* z_re,
+                       const float* z_im, int64_t z_bstride, int64_t B, int64_t n, int32_t squared, az_stream_t stream);
+int az_op_clip_f32(float* y, const float* x, int64_t n, float gain, float lo, float hi, az_stream_t stream);
+int az_op_clip_jac_f32(float* d, const float* g, const float* x, int64_t n, float gain, float lo, float hi, az_stream_t stream);
+int az_op_quantize_f32(float* q, const float* x, int64_t n, float lo, float hi, float step, az_stream_t stream);
+int az_op_pad_f32(float* dst, const float* src, int64_t planes, int64_t H, int64_t W, int32_t top, int32_t bottom, int32_t left,
+                  int32_t right, int32_t adjoint, az_stream_t stream);
+int az_op_nonlinear_trip(int64_t* floats);
+
 /* ---- Twisted diffusion sampler: resample and proposal -------------------------------------------------------------
  * The non-network part of TDSSampler.step (azula/guidance/tds.py:70-102) for K particles of N elements each.
  *

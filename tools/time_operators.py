@@ -6,6 +6,7 @@ r"""Time ``az_op_blur_f32`` (through ``BlurOperator``), ``az_op_psf_f32`` (throu
     python tools/time_operators.py fft [B] [C] [H] [W]             # 2-D Fourier transform
     python tools/time_operators.py radon [B] [C] [H] [W] [angles]  # parallel-beam Radon transform
     python tools/time_operators.py sense [B] [K] [H] [W]           # multi-coil (SENSE) MRI
+    python tools/time_operators.py nonlinear [B] [C] [H] [W]       # magnitude, clip, quantize entries and their linearisations
 
 Blur, default: the 61-tap Gaussian of DPS's deblurring setup on 4 x 3 x 256 x 256.  HIP events around back-to-back calls after a
 warm-up, the forms alternating over ``ROUNDS`` rounds; prints the median time per call of
@@ -44,7 +45,12 @@ operator, the two coil entries alone on buffers made once, and the torch lambda 
 same 6.29 TB/s: ``8 + 16 K`` bytes per pixel for either entry, and for the operator the sum over its three launches (the entry,
 the FFT's 24 or 56 bytes per coil pixel complex to complex, the mask's 16 bytes per coil pixel).
 
-The figures in DESIGN.md sections 9c, 9d, 9e and 9f come from this script.
+Nonlinear, default 4 x 3 x 512 x 512 elements (``nonlinear B C H W``; run it on 16 3 1024 1024 for tensors that no longer fit the
+256 MB Infinity Cache): the six elementwise entries of ``csrc/nonlinear.hip`` alone on buffers made once, each against its byte
+model (12 / 20 / 20 / 8 / 12 / 8 bytes per element) as GB/s, and ``PhaseRetrievalOperator`` / ``ClipOperator`` as a user calls
+them against the torch lambda a user writes today.
+
+The figures in DESIGN.md sections 9c, 9d, 9e, 9f and 9g come from this script.
 """
 
 from __future__ import annotations
@@ -67,6 +73,7 @@ from azula_amd import _lib  # noqa: E402
 from azula_amd.guidance import BlurOperator, FourierOperator, PSFOperator, gaussian_taps, motion_psf  # noqa: E402
 from azula_amd.guidance import MultiCoilMRIOperator, birdcage_maps, cartesian_mask  # noqa: E402
 from azula_amd.guidance import RadonOperator, radon_angles  # noqa: E402
+from azula_amd.guidance import ClipOperator, PhaseRetrievalOperator  # noqa: E402
 
 HBM = 6.29e12
 FP32_PEAK = 157.3e12  # vector fp32, FLOP/s
@@ -270,12 +277,51 @@ def sense(args: list[str]) -> None:
                       "model_fraction_combine": entry_floor / med["entry_combine"]}))
 
 
+def nonlinear(args: list[str]) -> None:
+    B, Cc, H, W = (int(v) for v in (args + ["4", "3", "512", "512"][len(args):]))
+    n, stream = Cc * H * W, _lib.stream_ptr()
+    z, t = torch.randn(B, 2 * Cc, H, W, device="cuda"), torch.randn(B, 2 * Cc, H, W, device="cuda")
+    g, y, d = torch.randn(B, Cc, H, W, device="cuda"), torch.empty(B, Cc, H, W, device="cuda"), torch.empty_like(z)
+    zp, tp, dp = ((v.data_ptr(), v.data_ptr() + 4 * n, 2 * n) for v in (z, t, d))  # (re, im, sample stride): the halves in place
+    x = z[:, :Cc].contiguous()
+    step = float(torch.tensor(2 / 255, dtype=torch.float32))
+    entries = {  # name -> (call, bytes per element)
+        "cmag": (lambda: _lib.call("az_op_cmag_f32", y.data_ptr(), n, *zp, B, n, 0, stream), 12),
+        "cmag_squared": (lambda: _lib.call("az_op_cmag_f32", y.data_ptr(), n, *zp, B, n, 1, stream), 12),
+        "cmag_vjp": (lambda: _lib.call("az_op_cmag_vjp_f32", *dp, g.data_ptr(), n, *zp, B, n, 0, stream), 20),
+        "cmag_jvp": (lambda: _lib.call("az_op_cmag_jvp_f32", y.data_ptr(), n, *tp, *zp, B, n, 0, stream), 20),
+        "clip": (lambda: _lib.call("az_op_clip_f32", y.data_ptr(), x.data_ptr(), B * n, 2.0, -1.0, 1.0, stream), 8),
+        "clip_jac": (lambda: _lib.call("az_op_clip_jac_f32", y.data_ptr(), g.data_ptr(), x.data_ptr(), B * n, 2.0, -1.0, 1.0, stream), 12),
+        "quantize": (lambda: _lib.call("az_op_quantize_f32", y.data_ptr(), x.data_ptr(), B * n, -1.0, 1.0, step, stream), 8),
+    }
+    times = measure({k: (fn, 50) for k, (fn, _) in entries.items()})
+    out = {"nonlinear": [B, Cc, H, W]}
+    for k, (_, nbytes) in entries.items():
+        med = statistics.median(times[k])
+        out[f"{k}_us"], out[f"{k}_GBps"] = med * 1e6, nbytes * B * n / med / 1e9
+        print(f"{k}: {med * 1e6:.1f} us per call (min {min(times[k]) * 1e6:.1f}, max {max(times[k]) * 1e6:.1f}), {nbytes} B per element: "
+              f"{nbytes * B * n / med / 1e9:.0f} GB/s, {nbytes * B * n / med / HBM:.1%} of {HBM / 1e12:.2f} TB/s")
+    if H == W and H <= 512 and H & (H - 1) == 0:  # the operators as a user calls them, against the lambda a user writes today
+        A, Hc = PhaseRetrievalOperator(H // 2), ClipOperator(gain=2.0)
+        lam = lambda v: torch.fft.fft2(F.pad(v, (H // 2,) * 4), norm="ortho").abs()  # noqa: E731
+        forms = {"phase_retrieval": (lambda: A(x), 50), "torch_phase_retrieval": (lambda: lam(x), 50), "hdr": (lambda: Hc(x), 50),
+                 "torch_hdr": (lambda: torch.clamp(2.0 * x, -1.0, 1.0), 50)}
+        ref = lam(x.double())
+        err = {"phase_retrieval": float((A(x).double() - ref).abs().max()), "torch_phase_retrieval": float((lam(x).double() - ref).abs().max()),
+               "hdr": float((Hc(x) - torch.clamp(2.0 * x, -1.0, 1.0)).abs().max()), "torch_hdr": 0.0}
+        med = report(forms, measure(forms), err)
+        out.update({f"{k}_us": v * 1e6 for k, v in med.items()})
+    print(json.dumps(out))
+
+
 def main() -> None:
     if not torch.cuda.is_available():
         raise SystemExit("time_operators.py measures on the GPU: no device visible")
     torch.manual_seed(0)
     if sys.argv[1:2] == ["radon"]:
         radon(sys.argv[2:7])
+    elif sys.argv[1:2] == ["nonlinear"]:
+        nonlinear(sys.argv[2:6])
     elif sys.argv[1:2] == ["sense"]:
         sense(sys.argv[2:6])
     elif sys.argv[1:2] == ["psf"]:
