@@ -1127,6 +1127,7 @@ int az_attention_f32(const AzAttnArgs* a, az_stream_t stream) {
 int az_swiglu_f32(float* y, const float* x, int64_t rows, int64_t cout, int64_t xs, int64_t ys, az_stream_t stream) {
   AZ_REQUIRE(y && x, AZ_E_NULL);
   AZ_REQUIRE(rows > 0 && cout > 0 && xs >= 2 * cout && ys >= cout && xs % 2 == 0, AZ_E_SHAPE);
+  AZ_REQUIRE((((uintptr_t)x) & 7u) == 0, AZ_E_ALIGN);  // (the kernel loads (value, gate) pairs as float2; xs % 2 keeps every row aligned)
   hipLaunchKernelGGL(swiglu_kernel, dim3(az_stream_grid(rows * ys, 256)), dim3(256), 0, az_s(stream), y, x, rows,
                      (int)cout, (int)xs, (int)ys);
   return az_launch_status();

@@ -1294,19 +1294,36 @@ def ada_zero_triple(bld: "Builder", ada_zero, channels: int, D: int, mod_rows: i
     return bld.const(abc), 0
 
 
-def mod_front_tape(bld: "Builder", mod_jobs: list, mod_buf: torch.Tensor, mod_rows: int, D: int) -> Tape:
-    r"""h_i = silu(W0_i mod + b0_i) for ALL queued blocks as one GEMV, abc_i = W2_i h_i + b2_i as one grouped GEMV."""
+def linear_groups(jobs: list):
+    r"""The ``AzLinearGroup`` array of ``(y, x, W, bias, ldy, ldx, N, K)`` jobs (addresses as integers, ``bias`` may be None) for
+    ``az_linear_small_grouped_f32``.  The descriptors are read on the device, so the entry cannot validate them, and its kernel has
+    only the 16-byte form (no scalar fallback): what ``az_linear_small_f32`` decides per launch is an error here, raised before
+    anything is launched."""
     from ._lib import AzLinearGroup
 
+    groups = (AzLinearGroup * len(jobs))()
+    for i, (y, x, W, bias, ldy, ldx, N, K) in enumerate(jobs):
+        if not (y and x and W):
+            raise ValueError(f"grouped linear, group {i}: null y / x / W")
+        if not (N > 0 and K > 0 and ldy >= N and ldx >= K):
+            raise ValueError(f"grouped linear, group {i}: N {N}, K {K}, ldy {ldy}, ldx {ldx} are not a (M, K) x (N, K) product")
+        if K % 4 or ldx % 4 or x % 16 or W % 16:
+            raise ValueError(f"grouped linear, group {i}: the kernel reads x and W as 16-byte vectors and needs K % 4 == 0, ldx % 4 == 0 "
+                             f"and 16-byte aligned x / W (K {K}, ldx {ldx}, x % 16 = {x % 16}, W % 16 = {W % 16})")
+        g = groups[i]
+        g.y, g.x, g.W, g.bias = y, x, W, bias
+        g.ldy, g.ldx, g.N, g.K = ldy, ldx, N, K
+    return groups
+
+
+def mod_front_tape(bld: "Builder", mod_jobs: list, mod_buf: torch.Tensor, mod_rows: int, D: int) -> Tape:
+    r"""h_i = silu(W0_i mod + b0_i) for ALL queued blocks as one GEMV, abc_i = W2_i h_i + b2_i as one grouped GEMV."""
     nj, rows = len(mod_jobs), max(mod_rows, 1)
     w0 = bld.const(torch.cat([j[0].weight.detach() for j in mod_jobs]))
     b0 = bld.const(torch.cat([j[0].bias.detach() for j in mod_jobs]))
     h_all = bld.empty(rows, nj * D)
-    groups = (AzLinearGroup * nj)()
-    for i, (_, w2, b2, abc, n_out) in enumerate(mod_jobs):
-        g = groups[i]
-        g.y, g.x, g.W, g.bias = abc.data_ptr(), h_all.data_ptr() + 4 * i * D, w2.data_ptr(), b2.data_ptr()
-        g.ldy, g.ldx, g.N, g.K = n_out, nj * D, n_out, D
+    groups = linear_groups([(abc.data_ptr(), h_all.data_ptr() + 4 * i * D, w2.data_ptr(), b2.data_ptr(), n_out, nj * D, n_out, D)
+                            for i, (_, w2, b2, abc, n_out) in enumerate(mod_jobs)])
     gdev = torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(bld.device)
     pre = Tape()
     pre.add("az_linear_small_f32", h_all.data_ptr(), nj * D, mod_buf.data_ptr(), D, w0.data_ptr(), b0.data_ptr(), rows, nj * D, D, 0, 1)

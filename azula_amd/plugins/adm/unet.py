@@ -387,14 +387,11 @@ def _emit_forward(plan, net: "UNetModel", x_in: Act | None, B: int, H: int, W: i
         bld.conv(n_, _packed(bld, co), net.out_channels, dst_nchw=plan.out, winograd=wino)
     bld.free(n_)
     if film_jobs:
-        from ..._lib import AzLinearGroup, lib
+        from ..._lib import lib
 
         nj = len(film_jobs)
-        groups = (AzLinearGroup * nj)()
-        for i, (film, w, b_, n_out) in enumerate(film_jobs):
-            g = groups[i]
-            g.y, g.x, g.W, g.bias = film.data_ptr(), emb.data_ptr(), w.data_ptr(), b_.data_ptr()
-            g.ldy, g.ldx, g.N, g.K = n_out, E, n_out, E
+        groups = engine.linear_groups([(film.data_ptr(), emb.data_ptr(), w.data_ptr(), b_.data_ptr(), n_out, E, n_out, E)
+                                       for film, w, b_, n_out in film_jobs])
         gdev = torch.frombuffer(bytearray(bytes(groups)), dtype=torch.uint8).to(device)
         bld.tape.keep.append(gdev)
         bld.tape.ops.insert(film_at, (

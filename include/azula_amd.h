@@ -1118,7 +1118,8 @@ typedef struct AzAttnBwdArgs {
 } AzAttnBwdArgs;
 int az_attention_bwd_f32(const AzAttnBwdArgs* args, az_stream_t stream);
 
-/* y[r, c] = x[r, 2c] * silu(x[r, 2c+1]), c < cout (SwiGLU, azula/nn/layers.py:89-110); xs / ys = row strides. */
+/* y[r, c] = x[r, 2c] * silu(x[r, 2c+1]), c < cout (SwiGLU, azula/nn/layers.py:89-110); xs / ys = row strides.  The (value, gate)
+ * pairs are read as 8-byte vectors: xs % 2 == 0 (AZ_E_SHAPE), x 8-byte aligned (AZ_E_ALIGN).  Lanes cout .. ys of y are zeroed. */
 int az_swiglu_f32(float* y, const float* x, int64_t rows, int64_t cout, int64_t xs, int64_t ys, az_stream_t stream);
 
 /* Token-window helpers for sequences that grow / shrink inside a backbone (JiT in-context class
