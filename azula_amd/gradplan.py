@@ -6,7 +6,26 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from .engine import Act, Builder, Tape, mod_front_tape
+from .engine import Act, Builder, Tape
+from .plan import mod_buffer, with_mod_front
+
+
+def vjp_scope(module: torch.nn.Module, x: Tensor, name: str, who: str | None = None) -> None:
+    r"""The input-gradient tapes of every backbone take fp32 parameters and fp32 device tensors (``who``: the backbone's name in
+    the forward's own device check).  What else a backbone leaves out (volumes, circular padding, head sizes) is its own check."""
+    from .nn.utils import backbone_io_dtype
+
+    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in module.parameters()):
+        raise NotImplementedError(f"{name}.vjp: fp32 parameters and tensors only (half-precision modules have no input-gradient plan)")
+    if not x.is_cuda:
+        raise NotImplementedError(f"{name}.vjp: device tensors only (CPU tensors have no input-gradient path)")
+    backbone_io_dtype(module, x, who or f"azula_amd.nn.{name}")
+
+
+def row_pullback(result: tuple) -> tuple:
+    r"""``(out, pullback)`` of a 1-D network from those of the one-row images (B, C, 1, L) it runs as."""
+    out, pullback = result
+    return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
 
 
 class _GradTapes:
@@ -24,17 +43,14 @@ class _GradTapes:
             self.out = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
             self.v_in = torch.empty(B, cout, H, W, dtype=torch.float32, device=device)
             self.dx = torch.empty(B, cin, H, W, dtype=torch.float32, device=device)
-        self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
+        self.mod = mod_buffer(device, mod_rows, D)
         self.mod_rows, self.D = mod_rows, D
         self.fwd = self.bld.tape  # (the builder records onto it until end_forward)
         self.bwd: Tape | None = None
         self.serial = 0  # forward-keep runs so far: a pullback belongs to one of them
 
     def end_forward(self, mod_jobs: list) -> None:
-        if mod_jobs:
-            pre = mod_front_tape(self.bld, mod_jobs, self.mod, self.mod_rows, self.D)
-            pre.extend(self.fwd)
-            self.fwd = pre
+        self.fwd = with_mod_front(self.bld, self.fwd, mod_jobs, self.mod, self.mod_rows, self.D)
         self.bld.tape = Tape()
 
     def end_backward(self) -> None:

@@ -24,8 +24,9 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from ..engine import Act, Builder, PlanCache, Tape, ada_zero_triple, mod_front_tape, mod_rows, pad4
-from ..gradplan import _GradTapes
+from ..engine import Act, Builder, PlanCache, Tape, ada_zero_triple, mod_rows, pad4
+from ..gradplan import _GradTapes, row_pullback, vjp_scope
+from ..plan import ForwardPlan
 from .. import _lib, engine
 
 __all__ = ["UNet", "UNetBlock"]
@@ -134,12 +135,6 @@ class UNetBlock(nn.Module):
         return y
 
     # -- input gradient (vector-Jacobian product) -------------------------------------------------------------------
-    def _vjp_supported(self) -> None:
-        if self.spatial == 3 or self.periodic:
-            raise NotImplementedError("UNetBlock.vjp: spatial = 1 / 2 with zero padding only")
-        if any(p.dtype != torch.float32 for p in self.parameters()):
-            raise NotImplementedError("UNetBlock.vjp: fp32 parameters only")
-
     def _emit_bwd(self, bld: Builder, g: Act, saved: dict, cache: dict) -> Act:
         r"""Cotangent of the block's output -> cotangent of its input: g2 = c g; g3 = dgrad(conv2)(g2); g4 = g3 silu'(h);
         g5 = dgrad(conv1)(g4); dx = g + norm_bwd(x, gamma = 1 + a, g5)."""
@@ -165,12 +160,9 @@ class UNetBlock(nn.Module):
         r"""``(out, pullback)``: ``out = self(x, mod)`` and ``pullback(v) = (d out / d x)^T v`` (like ``x``), both on the HIP
         tapes of a gradient plan (``mod`` is a constant of the pullback).  The pullback may be called any number of times
         until the next ``vjp`` of this module with the same shapes.  fp32, spatial = 1 / 2, zero padding."""
-        from .utils import backbone_io_dtype
-
-        self._vjp_supported()
-        backbone_io_dtype(self, x, "azula_amd.nn.UNetBlock")
-        if x.dtype != torch.float32:
-            raise NotImplementedError("UNetBlock.vjp: fp32 tensors only")
+        if self.spatial == 3 or self.periodic:
+            raise NotImplementedError("UNetBlock.vjp: spatial = 1 / 2 with zero padding only")
+        vjp_scope(self, x, "UNetBlock")
         one_d = self.spatial == 1
         if one_d:
             assert x.ndim == 3
@@ -198,10 +190,8 @@ class UNetBlock(nn.Module):
             plan.end_backward()
             return plan
 
-        out, pullback = self._cached_plan(x, mod, make, vjp=True)[0].run(x, mod)
-        if one_d:
-            return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
-        return out, pullback
+        res = self._cached_plan(x, mod, make, vjp=True)[0].run(x, mod)
+        return row_pullback(res) if one_d else res
 
     def _cached_plan(self, x: Tensor, mod: Tensor | None, make, vjp: bool = False):
         r"""(plan, modulation rows) of this block for ``x`` (B, C, *dims) and ``mod``: the cached plan, else ``make(rows)``.  A
@@ -218,55 +208,37 @@ class UNetBlock(nn.Module):
         from .utils import backbone_io_dtype
 
         out_dtype = backbone_io_dtype(self, x, "azula_amd.nn.UNetBlock")
-        if self.spatial == 1:  # (B, C, L): the same kernels and the same plan cache on a one-row image (no module state is touched)
+        one_d = self.spatial == 1
+        if one_d:  # (B, C, L): the same kernels and the same plan cache on a one-row image (no module state is touched)
             assert x.ndim == 3
-            return self._forward_nd(x[:, :, None], mod, out_dtype)[:, :, 0]
-        return self._forward_nd(x, mod, out_dtype)
+            x = x[:, :, None]
+        assert x.ndim == (5 if self.spatial == 3 else 4) and x.shape[1] == self.channels
+        plan, _ = self._cached_plan(x, mod, lambda rows: _BlockPlan(self, x.shape[0], tuple(x.shape[2:]), rows, x.device))
+        out = plan.run(x, mod, out_dtype=out_dtype)
+        return out[:, :, 0] if one_d else out
 
-    def _forward_nd(self, x: Tensor, mod: Tensor | None, out_dtype) -> Tensor:
-        r"""(B, C, H, W) images, or (B, C, D, H, W) volumes as B D planes on the volume form (see ``unet3d.py``): a one-block plan."""
-        vol = self.spatial == 3
-        assert x.ndim == (5 if vol else 4) and x.shape[1] == self.channels
-        B, Cc, *dims = x.shape
+
+class _BlockPlan(ForwardPlan):
+    r"""One-block plan on (B, C, H, W) images, or (B, C, D, H, W) volumes as B D planes on the volume form (see ``unet3d.py``)."""
+
+    def __init__(self, blk: UNetBlock, B: int, dims: tuple, rows: int, device) -> None:
+        super().__init__(device, half=next(blk.parameters()).dtype, mod_rows=rows, D=blk.mod_features)
+        vol = blk.spatial == 3
         planes, (H, W) = (dims[0] if vol else 1), dims[-2:]
-        D = self.mod_features
+        Cc, D, bld = blk.channels, blk.mod_features, self.bld
+        xin = self.nhwc_input(B * planes, H, W, Cc, pool=True)
+        if vol:
+            from .unet3d import Vol, block3d
 
-        def make(rows: int) -> tuple:
-            bld = Builder(x.device, half=next(self.parameters()).dtype)
-            xin = bld.new_act(B * planes, H, W, Cc, pinned=True)
-            mod_buf = torch.empty(max(rows, 1), max(D, 1), dtype=torch.float32, device=x.device)
-            jobs: list = []
-            if vol:
-                from .unet3d import Vol, block3d
-
-                out = block3d(self, bld, Vol(xin, B, planes), D, rows, jobs, keep_input=True)
-            else:
-                out = self._emit(bld, xin, D, rows, jobs, keep_input=True)
-            bld.finish()
-            tape = bld.tape
-            if jobs:
-                tape = mod_front_tape(bld, jobs, mod_buf, rows, D)
-                tape.extend(bld.tape)
-            res = torch.empty(B, Cc, *dims, dtype=torch.float32, device=x.device)
-            tape.add("az_nhwc_to_nchw_f32", res.data_ptr(), out.buf.data_ptr(), B, Cc, math.prod(dims), out.cs)
-            return (xin, mod_buf, tape, res)
-
-        (xin, mod_buf, tape, res), rows = self._cached_plan(x, mod, make)
-        xs = x.to(torch.float32).contiguous()
-        _lib.call("az_nchw_to_nhwc_f32", xin.ptr, xs.data_ptr(), None, B, Cc, math.prod(dims), xin.cs, _lib.stream_ptr())
-        if rows:
-            mod_buf.copy_(mod.to(torch.float32).reshape(rows, -1))
-        tape.run()
-        return res.to(out_dtype, copy=True)
+            out = block3d(blk, bld, Vol(xin, B, planes), D, rows, self.mod_jobs, keep_input=True)
+        else:
+            out = blk._emit(bld, xin, D, rows, self.mod_jobs, keep_input=True)
+        self.out = torch.empty(B, Cc, *dims, dtype=torch.float32, device=device)
+        bld.tape.add("az_nhwc_to_nchw_f32", self.out.data_ptr(), out.buf.data_ptr(), B, Cc, math.prod(dims), out.cs)
+        self.end()
 
 
-def _copy_tape(t):
-    c = Tape()
-    c.extend(t)
-    return c
-
-
-class UNetPlan:
+class UNetPlan(ForwardPlan):
     r"""Compiled forward for one (batch, H, W, modulation-rows) signature."""
 
     def __init__(self, net: "UNet", B: int, H: int, W: int, mod_rows: int, device: torch.device) -> None:
@@ -278,29 +250,13 @@ class UNetPlan:
         half_act = (net.spatial == 2 and all(c % 8 == 0 for c in net.hid_channels) and all(v in (1, 2, 4, 8, 16) for v in sv0)
                     and all(b.norm_kind != "group" or (b.channels // b.groups) % 4 == 0 for b in blocks)
                     and all(b.ffn[0].out_channels % 8 == 0 and b.channels <= 4096 for b in blocks))
-        bld = self.bld = Builder(device, half=next(net.parameters()).dtype, half_act=half_act)
-        cin = net.in_channels + net.cond_channels
-        D = net.mod_features
+        super().__init__(device, half=next(net.parameters()).dtype, half_act=half_act, mod_rows=mod_rows, D=net.mod_features)
         first = net.descent[0][0]
-        # <= 4 input channels through a 3 x 3 first convolution: it reads the latent PLANAR (x_in is then the loop's own
-        # (B, C, H, W) layout: channel stride 0 in the fused protocol), see Builder.conv_stem
-        self.planar = (engine.STEM_PLANAR and net.spatial == 2 and cin <= 4 and tuple(first.weight.shape[2:]) == (3, 3)
-                       and first.out_channels % 4 == 0 and bld.half is None)
-        if self.planar:
-            self.x_in = Act(torch.empty(B * cin * H * W, dtype=torch.float32, device=device), B, H, W, cin, 0, True)
-        else:
-            self.x_in = Act(torch.zeros(B * H * W * bld.pad(cin), dtype=torch.float32, device=device), B, H, W, cin, bld.pad(cin), True)
-        self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
-        self.mod_rows = mod_rows
+        stem = net.spatial == 2 and tuple(first.weight.shape[2:]) == (3, 3) and first.out_channels % 4 == 0
+        x_in = self.latent_input(B, H, W, net.in_channels + net.cond_channels, stem)
         self.out = torch.empty(B, net.out_channels, H, W, dtype=torch.float32, device=device)
-        mod_jobs: list[tuple] = []  # queued modulation MLPs (ada_zero_triple), emitted together at the tape front
-        _walk(net, bld, self.x_in, self.out, mod_rows, mod_jobs, planar=self.planar)
-        bld.finish()
-        self.tape = bld.tape
-        if mod_jobs:  # h_i = silu(W0_i mod + b0_i) for all blocks as ONE GEMV; abc_i = W2_i h_i + b2_i as ONE grouped GEMV
-            pre = mod_front_tape(bld, mod_jobs, self.mod, mod_rows, D)
-            pre.extend(self.tape)
-            self.tape = pre
+        _walk(net, self.bld, x_in, self.out, mod_rows, self.mod_jobs, planar=self.planar)
+        self.end()
 
 
 def _walk(net: "UNet", bld: Builder, cur: Act, out: Tensor, mod_rows: int, mod_jobs: list, *, planar: bool = False,
@@ -511,11 +467,9 @@ class UNet(nn.Module):
         constant of the pullback; it may be called any number of times until the next ``vjp`` with the same shapes.
         Scope: spatial = 1 / 2, zero padding, fp32 parameters and tensors, no ``cond_channels``; anything else raises
         ``NotImplementedError`` (the forward is not affected)."""
-        self._check_device(x)
         if self.spatial == 3 or self.periodic or self.cond_channels:
             raise NotImplementedError("UNet.vjp: spatial = 1 / 2, zero padding, no cond_channels")
-        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
-            raise NotImplementedError("UNet.vjp: fp32 parameters and tensors only")
+        vjp_scope(self, x, "UNet")
         one_d = self.spatial == 1
         if one_d:
             assert x.ndim == 3, "spatial = 1: expected (B, C, L)"
@@ -523,10 +477,8 @@ class UNet(nn.Module):
         B, Cin, H, W = x.shape
         assert Cin == self.in_channels
         rows = mod_rows(mod, B, self.mod_features, "UNet")
-        out, pullback = self.grad_plan(B, H, W, rows, x.device).run(x, mod)
-        if one_d:
-            return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
-        return out, pullback
+        res = self.grad_plan(B, H, W, rows, x.device).run(x, mod)
+        return row_pullback(res) if one_d else res
 
     def _check_device(self, x: Tensor) -> torch.dtype:
         from .utils import backbone_io_dtype
@@ -535,8 +487,6 @@ class UNet(nn.Module):
 
     # -- fused sampling (see azula_amd.sample.BackboneProgram) --------------------------------------
     def _program(self, x: Tensor, mod_rows: int):
-        from ..sample import BackboneProgram
-
         self._check_device(x)
         if self.cond_channels or x.ndim != (5 if self.spatial == 3 else 4):
             return None, None
@@ -548,21 +498,12 @@ class UNet(nn.Module):
             # the image form with its channel-padded second output (0.59 on volumes); one layout pass in front of
             # the first convolution makes the (B, D, H, W, cs) planes the depth-tap launches read.
             x_planar = torch.empty(B * self.in_channels * Dd * H * W, dtype=torch.float32, device=x.device)
-            tape = Tape()
-            tape.add("az_nchw_to_nhwc_f32", p.x_in.buf.data_ptr(), x_planar.data_ptr(), None, B, self.in_channels, Dd * H * W, p.x_in.cs,
-                     keep=[x_planar])
-            tape.extend(p.tape)
-            prog = BackboneProgram(tape=tape, x_in=x_planar, x_in_cs=0, out=p.out, f_channels=self.out_channels, f_nhwc=False)
-            prog.tape.keep.append(p)
-            return prog, p.mod
+            front = Tape()
+            front.add("az_nchw_to_nhwc_f32", p.x_in.ptr, x_planar.data_ptr(), None, B, self.in_channels, Dd * H * W, p.x_in.cs, keep=[x_planar])
+            return p.program(self.out_channels, front=front, x_in=x_planar, x_in_cs=0), p.mod
         B, _, H, W = x.shape
         p = self.plan(B, H, W, mod_rows, x.device)
-        prog = BackboneProgram(
-            tape=_copy_tape(p.tape), x_in=p.x_in.buf, x_in_cs=p.x_in.cs, out=p.out, f_channels=self.out_channels,
-            f_nhwc=False,
-        )
-        prog.tape.keep.append(p)
-        return prog, p.mod
+        return p.program(self.out_channels), p.mod
 
     def _az_compile_modulated(self, x: Tensor, mod_rows: int = 1):
         r"""(program, mod buffer): the caller's tape must fill the (mod_rows, D) buffer first."""
@@ -577,46 +518,19 @@ class UNet(nn.Module):
             return None
         return self._program(x, 0)[0]
 
-    def _forward_3d(self, x: Tensor, mod: Tensor | None, out_dtype) -> Tensor:
-        r"""(B, C, D, H, W) volumes: every 3-D convolution as depth taps of the 2-D kernels (``unet3d.py``)."""
-        assert x.ndim == 5, "spatial = 3: expected (B, C, D, H, W)"
-        B, Cin, D, H, W = x.shape
-        assert Cin == self.in_channels + self.cond_channels
-        rows = mod_rows(mod, B, self.mod_features, "UNet")
-        p = self.plan3d(B, D, H, W, rows, x.device)
-        s = _lib.stream_ptr()
-        _lib.call("az_nchw_to_nhwc_f32", p.x_in.buf.data_ptr(), x.data_ptr(), None, B, Cin, D * H * W, p.x_in.cs, s)
-        if rows:
-            p.mod.copy_(mod.to(torch.float32).reshape(rows, -1))
-        p.tape.run(s)
-        return p.out.to(out_dtype, copy=True)
-
     @torch.no_grad()
     @_lib.on_device
     def forward(self, x: Tensor, mod: Tensor | None = None, cond: Tensor | None = None) -> Tensor:
         r"""x: (B, C_i, H, W); mod: (D) or (B, D); cond: (B, C_c, H, W) -> (B, C_o, H, W).  With ``spatial = 1`` the
         tensors are (B, C, L): a one-row image through the same kernels (the 1-D filters sit in the middle row of
-        3 x 3 ones, the other rows only ever meet the padding)."""
+        3 x 3 ones, the other rows only ever meet the padding); with ``spatial = 3`` they are (B, C, D, H, W) volumes, every
+        3-D convolution as depth taps of the 2-D kernels (``unet3d.py``)."""
         out_dtype = self._check_device(x)
-        if cond is not None:
-            x = torch.cat((x, cond), dim=1)
+        assert x.ndim == self.spatial + 2, f"spatial = {self.spatial}: expected a {self.spatial + 2}-d input"
+        assert x.shape[1] + (cond.shape[1] if cond is not None else 0) == self.in_channels + self.cond_channels
         if self.spatial == 1:
-            assert x.ndim == 3, "spatial = 1: expected (B, C, L)"
-            x = x[:, :, None]
-        x = x.to(torch.float32).contiguous()
-        if self.spatial == 3:
-            return self._forward_3d(x, mod, out_dtype)
-        B, Cin, H, W = x.shape
-        assert Cin == self.in_channels + self.cond_channels
-        rows = mod_rows(mod, B, self.mod_features, "UNet")
-        p = self.plan(B, H, W, rows, x.device)
-        s = _lib.stream_ptr()
-        if p.planar:
-            p.x_in.buf.copy_(x.reshape(-1))
-        else:
-            _lib.call("az_nchw_to_nhwc_f32", p.x_in.ptr, x.data_ptr(), None, B, Cin, H * W, p.x_in.cs, s)
-        if rows:
-            p.mod.copy_(mod.to(torch.float32).reshape(rows, -1))
-        p.tape.run(s)
-        out = p.out.to(out_dtype, copy=True)
+            x, cond = x[:, :, None], (cond[:, :, None] if cond is not None else None)
+        rows = mod_rows(mod, x.shape[0], self.mod_features, "UNet")
+        p = (self.plan3d if self.spatial == 3 else self.plan)(x.shape[0], *x.shape[2:], rows, x.device)
+        out = p.run(x, mod, cond=cond, out_dtype=out_dtype)
         return out[:, :, 0] if self.spatial == 1 else out

@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import torch
 
-from ..engine import Act, Builder, ada_zero_triple, mod_front_tape, pad4
+from ..engine import Act, Builder, ada_zero_triple, pad4
+from ..plan import ForwardPlan
 
 
 class Vol:
@@ -216,24 +217,20 @@ def block3d(blk, bld: Builder, x: Vol, D_mod: int, mod_rows: int, mod_jobs: list
     return y
 
 
-class UNet3DPlan:
+class UNet3DPlan(ForwardPlan):
     r"""Compiled forward for one (batch, D, H, W, modulation-rows) signature."""
 
     def __init__(self, net, B: int, D: int, H: int, W: int, mod_rows: int, device: torch.device) -> None:
-        bld = self.bld = Builder(device, half=next(net.parameters()).dtype)
-        cin = net.in_channels + net.cond_channels
         Dm = net.mod_features
-        xa = Act(torch.empty(B * D * H * W * pad4(cin), dtype=torch.float32, device=device), B * D, H, W, cin, pad4(cin), True)
-        self.x_in = Vol(xa, B, D)
-        self.mod = torch.empty(max(mod_rows, 1), max(Dm, 1), dtype=torch.float32, device=device)
+        super().__init__(device, half=next(net.parameters()).dtype, mod_rows=mod_rows, D=Dm)
+        bld, mod_jobs = self.bld, self.mod_jobs
+        cur = Vol(self.nhwc_input(B * D, H, W, net.in_channels + net.cond_channels, zero=False), B, D)
         self.out = torch.empty(B, net.out_channels, D, H, W, dtype=torch.float32, device=device)
         L = len(net.hid_blocks)
         stride, per = net.stride, net.periodic
         sv = (stride,) * 3 if isinstance(stride, int) else tuple(stride)
         pow2 = all(v in (1, 2, 4, 8, 16) for v in sv)
         up = tuple(v.bit_length() - 1 for v in sv) if pow2 else 0
-        mod_jobs: list[tuple] = []
-        cur = self.x_in
         skips: list[Vol] = []
         for i in range(L):
             first = net.descent[i][0]
@@ -265,9 +262,4 @@ class UNet3DPlan:
                 head = conv3d(bld, cur, mods[idx], periodic=per)
                 bld.tape.add("az_nhwc_to_nchw_f32", self.out.data_ptr(), head.buf.data_ptr(), B, net.out_channels, D * H * W, head.cs)
                 free_vol(bld, cur)
-        bld.finish()
-        self.tape = bld.tape
-        if mod_jobs:
-            pre = mod_front_tape(bld, mod_jobs, self.mod, mod_rows, Dm)
-            pre.extend(self.tape)
-            self.tape = pre
+        self.end()

@@ -29,8 +29,9 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _lib, engine
-from ..engine import Act, Builder, LinearView, PlanCache, SharedResidual, ada_zero_triple, content_key, mod_front_tape, mod_rows, pad4
-from ..gradplan import _TokenGradTapes
+from ..engine import Act, Builder, LinearView, PlanCache, SharedResidual, ada_zero_triple, content_key, mod_rows, pad4
+from ..gradplan import _TokenGradTapes, vjp_scope
+from ..plan import ForwardPlan
 
 __all__ = ["DiT", "DiTBlock", "MultiheadSelfAttention", "ViT"]
 
@@ -145,7 +146,7 @@ class MultiheadSelfAttention(nn.Module):
 
         out_dtype = backbone_io_dtype(self, x, "azula_amd.nn.MultiheadSelfAttention")
         plan = _token_plan(self, x, pos, mask, 0, lambda bld, xin, pos_h, plan: self._emit(bld, xin, pos_h, mask))
-        return plan.run(x, None).to(out_dtype)
+        return plan.run(x, out_dtype=out_dtype)
 
 
 def _half_act_ok(module: nn.Module) -> bool:
@@ -165,36 +166,14 @@ def _half_act_ok(module: nn.Module) -> bool:
     return True
 
 
-class _TokenPlan:
+class _TokenPlan(ForwardPlan):
     r"""One-module plan on a (B, L, C) token tensor: input Act, optional modulation front, output Act."""
 
     def __init__(self, module: nn.Module, B: int, L: int, Cin: int, pos_h, mod_rows: int, D: int, emit, device) -> None:
-        bld = self.bld = Builder(device, half=next(module.parameters()).dtype, half_act=_half_act_ok(module) and Cin % 8 == 0)
-        self.x_in = bld.new_act(B, L, 1, Cin, pinned=True)
-        self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
-        self.mod_jobs: list = []
-        self.mod_rows = mod_rows
-        self.out = emit(bld, self.x_in, pos_h, self)
-        bld.finish()
-        self.tape = bld.tape
-        if self.mod_jobs:
-            pre = mod_front_tape(bld, self.mod_jobs, self.mod, mod_rows, D)
-            pre.extend(self.tape)
-            self.tape = pre
-
-    def run(self, x: Tensor, mod: Tensor | None) -> Tensor:
-        t, (B, L) = self.x_in, (self.x_in.B, self.x_in.H)
-        xf = x.to(torch.float32).reshape(B * L, -1)
-        if t.cs == xf.shape[1]:
-            t.buf.copy_(xf.reshape(-1))
-        else:
-            t.buf.zero_()
-            t.buf.view(B * L, t.cs)[:, : xf.shape[1]].copy_(xf)
-        if self.mod_rows:
-            self.mod.copy_(mod.to(torch.float32).reshape(self.mod_rows, -1))
-        self.tape.run()
-        o = self.out
-        return o.buf.view(B, L, o.cs)[..., : o.C].reshape(*x.shape[:-1], o.C).clone()
+        super().__init__(device, half=next(module.parameters()).dtype, half_act=_half_act_ok(module) and Cin % 8 == 0,
+                         mod_rows=mod_rows, D=D)
+        self.out_tokens = emit(self.bld, self.token_input(B, L, Cin), pos_h, self)
+        self.end()
 
 
 def _host_pos(pos: Tensor | None, L: int) -> Tensor | None:
@@ -220,12 +199,8 @@ def _token_plan(module, x: Tensor, pos, mask, D: int, emit, mod: Tensor | None =
 
 
 def _vjp_scope(module: nn.Module, x: Tensor, name: str) -> None:
-    r"""The input-gradient tapes take fp32 parameters and fp32 device tensors, and head sizes the backward kernels reach."""
-    from .utils import backbone_io_dtype
-
-    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in module.parameters()):
-        raise NotImplementedError(f"{name}.vjp: fp32 parameters and tensors only")
-    backbone_io_dtype(module, x, f"azula_amd.nn.{name}")
+    r"""``gradplan.vjp_scope``, and head sizes the backward kernels reach."""
+    vjp_scope(module, x, name)
     for m in module.modules():
         if isinstance(m, MultiheadSelfAttention):
             engine.attn_grad_padded_dim(m.qkv_proj.in_features // m.heads)  # (raises NotImplementedError above 128)
@@ -370,8 +345,7 @@ class DiTBlock(nn.Module):
         def emit(bld, xin, pos_h, plan):
             return self._emit(bld, xin, pos_h, mask, D, plan.mod_rows, plan.mod_jobs, keep_input=True)
 
-        plan = _token_plan(self, x, pos, mask, D, emit, mod)
-        return plan.run(x, mod).to(out_dtype)
+        return _token_plan(self, x, pos, mask, D, emit, mod).run(x, mod, out_dtype=out_dtype)
 
 
 def host_sine_encoding(x: Tensor, features: int, omega: float) -> Tensor:
@@ -398,27 +372,23 @@ def _pos_table(net: "DiT", bld: Builder, pos: Tensor, L: int) -> Act:
     return ptab
 
 
-class DiTPlan:
+class DiTPlan(ForwardPlan):
     r"""Compiled forward for (batch, tokens[, patch geometry], modulation rows)."""
 
     def __init__(self, net: "DiT", B: int, L: int, pos: Tensor, mod_rows: int, device, patch=None) -> None:
-        bld = self.bld = Builder(device, half=next(net.parameters()).dtype, half_act=_half_act_ok(net) and net.hid_channels % 8 == 0)
         D, C_ = net.mod_features, net.hid_channels
-        self.mod = torch.empty(max(mod_rows, 1), max(D, 1), dtype=torch.float32, device=device)
-        self.mod_rows = mod_rows
+        super().__init__(device, half=next(net.parameters()).dtype, half_act=_half_act_ok(net) and C_ % 8 == 0, mod_rows=mod_rows, D=D)
+        bld, mod_jobs = self.bld, self.mod_jobs
         cin = net.in_proj.in_features
         cout = net.out_proj.out_features
         if patch is not None:
             Z, H, W, p, pu = patch
-            self.x_nchw = torch.empty(B, Z, H, W, dtype=torch.float32, device=device)
-            tokens = bld.new_act(B, L, 1, cin, pinned=True, f32=True)  # (the plan's input stays fp32: the first GEMM rounds it per tile)
-            bld.tape.add("az_patchify_f32", tokens.ptr, self.x_nchw.data_ptr(), None, B, Z, H, W, p, tokens.cs)
+            x_nchw = self.nchw_input(B, Z, H, W)
+            tokens = self.tokens = bld.new_act(B, L, 1, cin, pinned=True, f32=True)  # (the plan's input stays fp32: the first GEMM rounds it per tile)
+            bld.tape.add("az_patchify_f32", tokens.ptr, x_nchw.data_ptr(), None, B, Z, H, W, p, tokens.cs)
             bld.wrote(tokens, bounded=False)
-            self.x_in_buf, self.x_in_cs = self.x_nchw, 0
         else:
-            tokens = bld.new_act(B, L, 1, cin, pinned=True, f32=True)
-            self.x_in_buf, self.x_in_cs = tokens.buf, tokens.cs
-        self.tokens = tokens
+            tokens = self.token_input(B, L, cin, f32=True)
 
         ptab = _pos_table(net, bld, pos, L)
         if bld.half_act:  # the residual operand of the first GEMM has the destination's element type
@@ -428,8 +398,7 @@ class DiTPlan:
         self.pos_table = ptab
 
         x = bld.conv(tokens, bld.pack_conv(net.in_proj.weight, net.in_proj.bias), C_, res=SharedResidual(ptab))
-        mod_jobs: list[tuple] = []  # queued modulation MLPs of the blocks, emitted together at the tape front
-        for blk in net.blocks:
+        for blk in net.blocks:  # (all blocks' modulation MLPs read only `mod`: one GEMV + one grouped GEMV at the front)
             x = blk._emit(bld, x, pos, None, D, mod_rows, mod_jobs)
         o = bld.conv(x, bld.pack_conv(net.out_proj.weight, net.out_proj.bias), cout, out_f32=True)  # (the plan's output: fp32)
         bld.free(x)
@@ -438,15 +407,9 @@ class DiTPlan:
             Zo, Ho, Wo = cout // (pu * pu), H // p * pu, W // p * pu
             self.out = torch.empty(B, Zo, Ho, Wo, dtype=torch.float32, device=device)
             bld.tape.add("az_unpatchify_f32", self.out.data_ptr(), o.ptr, B, Zo, Ho, Wo, pu, o.cs)
-            self.out_tokens = None
         else:
-            self.out, self.out_tokens = None, o
-        bld.finish()
-        self.tape = bld.tape
-        if mod_jobs:  # all blocks' modulation MLPs read only `mod`: one GEMV + one grouped GEMV at the front
-            pre = mod_front_tape(bld, mod_jobs, self.mod, mod_rows, D)
-            pre.extend(self.tape)
-            self.tape = pre
+            self.out_tokens = o
+        self.end()
 
 
 class DiTGradPlan(_TokenGradTapes):
@@ -531,25 +494,12 @@ class DiT(nn.Module):
     def forward(self, x: Tensor, mod: Tensor | None = None, pos: Tensor | None = None, cond: Tensor | None = None):
         r"""x: (B, L, C_i) tokens -> (B, L, C_o).  ``pos``: (L, P) or None (sequence indices)."""
         out_dtype = self._check_device(x)
-        if cond is not None:
-            x = torch.cat((x, cond), dim=-1)
         assert x.ndim == 3, "DiT.forward expects (B, L, C) tokens"
-        x = x.to(torch.float32).contiguous()
-        B, L, Cin = x.shape
+        B, L, _ = x.shape
         rows = self._mod_rows(mod, B)
         pkey, pos_h = self._pos(pos, L)
         plan = self._plans.get((B, L, rows, pkey, str(x.device)), lambda: DiTPlan(self, B, L, pos_h(), rows, x.device), self)
-        t = plan.tokens
-        if t.cs == Cin:
-            t.buf.copy_(x.reshape(-1))
-        else:
-            t.buf.zero_()
-            t.buf.view(B * L, t.cs)[:, :Cin].copy_(x.reshape(B * L, Cin))
-        if rows:
-            plan.mod.copy_(mod.to(torch.float32).reshape(rows, -1))
-        plan.tape.run()
-        o = plan.out_tokens
-        return o.buf.view(B, L, o.cs)[..., : o.C].to(out_dtype, copy=True)
+        return plan.run(x, mod, cond=cond, out_dtype=out_dtype)
 
     # -- input gradient --------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -656,16 +606,9 @@ class ViT(DiT):
         B, Z, H, W = x.shape
         assert Z == self.image_in and H % self.patch_size == 0 and W % self.patch_size == 0
         rows = self._mod_rows(mod, B)
-        plan = self._vit_plan(B, H, W, rows, x.device)
         # patchify(x) || patchify(cond) along the token features == patchify of the channel concatenation: the
         # feature index is (channel, a, b) with the channel slowest (reference vit.py:92-96, layers.py:198-222)
-        plan.x_nchw[:, :Z].copy_(x)
-        if cond is not None:
-            plan.x_nchw[:, Z:].copy_(cond)
-        if rows:
-            plan.mod.copy_(mod.to(torch.float32).reshape(rows, -1))
-        plan.tape.run()
-        return plan.out.to(out_dtype, copy=True)
+        return self._vit_plan(B, H, W, rows, x.device).run(x, mod, cond=cond, out_dtype=out_dtype)
 
     def _forward_rearranged(self, x: Tensor, mod, cond) -> Tensor:
         r"""Any number of spatial dimensions / anisotropic patches: ``Patchify`` and ``Unpatchify`` (reference
@@ -681,9 +624,6 @@ class ViT(DiT):
 
     # -- fused sampling ---------------------------------------------------------------------------
     def _az_compile_modulated(self, x: Tensor, mod_rows: int = 1):
-        from ..sample import BackboneProgram
-        from .unet import _copy_tape
-
         if not self.native:
             return None
         if self.mod_features == 0 or x.ndim != 4 or self.image_cond or self.unpatch_size != self.patch_size:
@@ -691,8 +631,4 @@ class ViT(DiT):
         self._check_device(x)
         B, _, H, W = x.shape
         plan = self._vit_plan(B, H, W, mod_rows, x.device)
-        prog = BackboneProgram(
-            tape=_copy_tape(plan.tape), x_in=plan.x_nchw, x_in_cs=0, out=plan.out, f_channels=self.image_out, f_nhwc=False
-        )
-        prog.tape.keep.append(plan)
-        return prog, plan.mod
+        return plan.program(self.image_out), plan.mod

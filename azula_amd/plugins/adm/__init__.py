@@ -200,9 +200,6 @@ class AblatedDenoiser(Denoiser):
     def _az_programs(self, x: Tensor, kwargs_list: list[dict], cur_coef: Tensor):
         r"""One compiled backbone program per kwargs dict (CFG: positive, negative), all reading
         the same pre-scaled NHWC input buffer."""
-        from ...sample import BackboneProgram
-        from ...nn.unet import _copy_tape
-
         bb = self.backbone
         if not isinstance(bb, unet.UNetModel) or x.ndim != bb.dims + 2 or get_module_dtype(bb) not in (torch.float32, torch.float16, torch.bfloat16):
             return None
@@ -228,12 +225,7 @@ class AblatedDenoiser(Denoiser):
                 if plan.labels is not None:
                     plan.labels.copy_(lab.to(torch.int64))
 
-            prog = BackboneProgram(
-                tape=_copy_tape(plan.tape), x_in=plan.x_in.buf, x_in_cs=plan.x_in.cs, out=plan.out,
-                f_channels=bb.out_channels, f_nhwc=False, prepare=prepare,
-            )
-            prog.tape.keep.append(plan)
-            programs.append(prog)
+            programs.append(plan.program(bb.out_channels, prepare=prepare))
         return programs
 
     def _az_cfg_batched(self, x: Tensor, kwargs_list: list[dict], cur_coef: Tensor):
@@ -242,7 +234,7 @@ class AblatedDenoiser(Denoiser):
         duplicates it, and the two halves of the output are its ``F`` / ``F_neg``.  Same arithmetic per sample as two
         sequential evaluations (the reference's ``cfg.py:60-61``), but the small feature maps fill the chip better."""
         from ...engine import Tape
-        from ...nn.unet import _copy_tape
+        from ...plan import copy_tape
         from ...sample import BackboneProgram
 
         bb = self.backbone
@@ -253,9 +245,9 @@ class AblatedDenoiser(Denoiser):
         plan = bb.plan(2 * B, H, W, 2 * B, x.device, coef_ptr=cur_coef.data_ptr(), tag="cfg2b", D=D)
         half_in = B * D * H * W * (plan.x_in.cs if plan.x_in.cs > 0 else plan.x_in.C)  # (channel stride 0: the planar latent layout)
         one = torch.ones(1, dtype=torch.float32, device=x.device)
-        tape = Tape()
-        tape.add("az_scale_f32", plan.x_in.ptr + 4 * half_in, plan.x_in.ptr, one.data_ptr(), half_in, keep=[one, plan])
-        tape.extend(_copy_tape(plan.tape))
+        front = Tape()
+        front.add("az_scale_f32", plan.x_in.ptr + 4 * half_in, plan.x_in.ptr, one.data_ptr(), half_in, keep=[one, plan])
+        tape = copy_tape(plan.tape, front)
 
         def prepare(call_kwargs: dict, key: int) -> None:
             lab = call_kwargs.get("_az_labels", {}).get(key)

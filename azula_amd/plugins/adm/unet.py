@@ -31,7 +31,8 @@ from torch import Tensor
 
 from ... import _lib, engine
 from ...engine import Act, Builder, PlanCache, pad8
-from ...gradplan import _GradTapes
+from ...gradplan import _GradTapes, row_pullback, vjp_scope
+from ...plan import ForwardPlan
 
 __all__ = ["UNetModel"]
 
@@ -401,7 +402,16 @@ def _emit_forward(plan, net: "UNetModel", x_in: Act | None, B: int, H: int, W: i
     return in_recs, mid_recs, out_recs, r_head, len(hs)
 
 
-class ADMPlan:
+def _set_embedding(plan, timesteps: Tensor, y: Tensor | None) -> None:
+    r"""The embedding inputs of a forward or gradient plan: time indices (or fractional timesteps), one or one per row, and labels."""
+    rows = plan.t_idx.numel()
+    t, dtype = (plan.t_frac, torch.float32) if plan.t_frac is not None else (plan.t_idx, torch.int64)
+    t.copy_(timesteps.to(dtype).expand(rows) if timesteps.numel() == 1 else timesteps.to(dtype))
+    if y is not None:
+        plan.labels.copy_(y.to(torch.int64))
+
+
+class ADMPlan(ForwardPlan):
     r"""Compiled forward for (batch, H, W, embedding rows).  ``emb_rows`` = 1 when all samples
     share the timestep and there are no labels, else the batch size."""
 
@@ -413,24 +423,15 @@ class ADMPlan:
         chans = sorted({m.num_channels for m in net.modules() if isinstance(m, nn.GroupNorm)})
         half_act = (net.dims != 3 and all(c % 128 == 0 for c in chans) and net.model_channels % 8 == 0
                     and (x_in is None or x_in.cs == pad8(net.in_channels)))  # (a shared input: the first program's, same stride)
-        bld = self.bld = Builder(device, half=next(net.parameters()).dtype, half_act=half_act)
+        super().__init__(device, half=next(net.parameters()).dtype, half_act=half_act)
         self.emb_rows = emb_rows
-        cin, three_d = net.in_channels, net.dims == 3
-        PB = B * D
+        three_d = net.dims == 3
         c_first = net.input_blocks[0][0]
-        # the first convolution reads the latent PLANAR (x_in = the loop's own (B, C, H, W) layout, channel stride 0): Builder.conv_stem
-        self.planar = (engine.STEM_PLANAR and cin <= 4 and not three_d and isinstance(c_first, (nn.Conv1d, nn.Conv2d)) and c_first.weight.shape[-1] == 3
-                       and c_first.out_channels % 4 == 0 and bld.half is None and (x_in is None or x_in.cs == 0))
-        if x_in is not None:
-            self.x_in = x_in
-        elif self.planar:
-            self.x_in = Act(torch.empty(B * cin * H * W, dtype=torch.float32, device=device), B, H, W, cin, 0, True)
-        else:
-            self.x_in = Act(torch.zeros(PB * H * W * bld.pad(cin), dtype=torch.float32, device=device), PB, H, W, cin, bld.pad(cin), True)
+        stem = not three_d and isinstance(c_first, (nn.Conv1d, nn.Conv2d)) and c_first.weight.shape[-1] == 3 and c_first.out_channels % 4 == 0
+        self.latent_input(B, H, W, net.in_channels, stem, planes=D, shared=x_in)
         self.out = torch.empty((B, net.out_channels) + ((D,) if three_d else ()) + (H, W), dtype=torch.float32, device=device)
         _emit_forward(self, net, self.x_in, B, H, W, emb_rows, coef_ptr=coef_ptr, frac=frac, D=D)
-        bld.finish()
-        self.tape = bld.tape
+        self.end()
 
 
 class ADMGradPlan(_GradTapes):
@@ -564,13 +565,7 @@ class ADMGradPlan(_GradTapes):
         self.end_backward()
 
     def run_adm(self, x: Tensor, timesteps: Tensor, y: Tensor | None):
-        rows = self.t_idx.numel()
-        if self.t_frac is not None:
-            self.t_frac.copy_(timesteps.to(torch.float32).expand(rows) if timesteps.numel() == 1 else timesteps.to(torch.float32))
-        else:
-            self.t_idx.copy_(timesteps.to(torch.int64).expand(rows) if timesteps.numel() == 1 else timesteps.to(torch.int64))
-        if y is not None:
-            self.labels.copy_(y.to(torch.int64))
+        _set_embedding(self, timesteps, y)
         return self.run(x, None)
 
 
@@ -678,10 +673,7 @@ class UNetModel(nn.Module):
         affected)."""
         if self.dims == 3:
             raise NotImplementedError("UNetModel.vjp: dims = 1 and 2 only (dims = 3 volumes have no input-gradient plan)")
-        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
-            raise NotImplementedError("UNetModel.vjp: fp32 parameters and tensors only (half-precision modules have no input-gradient plan)")
-        if not x.is_cuda:
-            raise NotImplementedError("UNetModel.vjp: device tensors only (CPU tensors have no input-gradient path)")
+        vjp_scope(self, x, "UNetModel", "azula_amd ADM UNetModel")
         assert (y is not None) == (self.num_classes is not None), "must specify y if and only if the model is class-conditional"
         assert x.ndim == self.dims + 2, f"dims={self.dims}: expected a {self.dims + 2}-d input, got {tuple(x.shape)}"
         one_d = self.dims == 1
@@ -692,10 +684,8 @@ class UNetModel(nn.Module):
         timesteps = timesteps.reshape(-1)
         frac = torch.is_floating_point(timesteps)
         rows = B if (timesteps.numel() > 1 or self.num_classes is not None) else 1
-        out, pullback = self.grad_plan(B, H, W, rows, x.device, frac=frac).run_adm(x, timesteps, y)
-        if one_d:
-            return out[:, :, 0], lambda v: pullback(v[:, :, None])[:, :, 0]
-        return out, pullback
+        res = self.grad_plan(B, H, W, rows, x.device, frac=frac).run_adm(x, timesteps, y)
+        return row_pullback(res) if one_d else res
 
     @torch.no_grad()
     @_lib.on_device
@@ -708,28 +698,16 @@ class UNetModel(nn.Module):
         from ...nn.utils import backbone_io_dtype
 
         out_dtype = backbone_io_dtype(self, x, "azula_amd ADM UNetModel")
-        x = x.to(torch.float32).contiguous()
         assert x.ndim == self.dims + 2, f"dims={self.dims}: expected a {self.dims + 2}-d input, got {tuple(x.shape)}"
         shape = x.shape
         if self.dims == 1:
             x = x[:, :, None, :]
         D = x.shape[2] if self.dims == 3 else 1
-        B, Cin, H, W = x.shape[0], x.shape[1], x.shape[-2], x.shape[-1]
+        B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
         timesteps = timesteps.reshape(-1)
         frac = torch.is_floating_point(timesteps)  # (azula itself passes integer indices; guided-diffusion allows fractions)
         rows = B if (timesteps.numel() > 1 or self.num_classes is not None) else 1
         p = self.plan(B, H, W, rows, x.device, frac=frac, D=D)
-        s = _lib.stream_ptr()
-        if p.planar:
-            p.x_in.buf.copy_(x.reshape(-1))
-        else:
-            _lib.call("az_nchw_to_nhwc_f32", p.x_in.ptr, x.data_ptr(), None, B, Cin, D * H * W, p.x_in.cs, s)
-        if frac:
-            p.t_frac.copy_(timesteps.to(torch.float32).expand(rows) if timesteps.numel() == 1 else timesteps.to(torch.float32))
-        else:
-            p.t_idx.copy_(timesteps.to(torch.int64).expand(rows) if timesteps.numel() == 1 else timesteps.to(torch.int64))
-        if y is not None:
-            assert y.shape == (B,)
-            p.labels.copy_(y.to(torch.int64))
-        p.tape.run(s)
-        return p.out.reshape(B, self.out_channels, *shape[2:]).to(out_dtype, copy=True)
+        assert y is None or y.shape == (B,)
+        _set_embedding(p, timesteps, y)
+        return p.run(x, out_dtype=out_dtype).reshape(B, self.out_channels, *shape[2:])

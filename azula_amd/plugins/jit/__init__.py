@@ -96,7 +96,7 @@ class JITDenoiser(Denoiser):
         r"""One compiled backbone program per kwargs dict (CFG: conditional, null class).  Each program owns
         its plan (labels differ) and copies the shared pre-scaled input produced by the transition kernel."""
         from ...engine import Tape
-        from ...nn.unet import _copy_tape
+        from ...plan import copy_tape
         from ...sample import BackboneProgram
 
         bb = self.backbone
@@ -109,10 +109,10 @@ class JITDenoiser(Denoiser):
 
             plan = JiTPlan(bb, 2 * B, True, x.device)
             half = plan.x_nchw[:B].numel()
-            tape = Tape()
-            tape.add("az_coef_c_time_f32", plan.t.data_ptr(), cur_coef.data_ptr())
-            tape.add("az_scale_f32", plan.x_nchw.data_ptr() + 4 * half, plan.x_nchw.data_ptr(), _one(x.device).data_ptr(), half)
-            tape.extend(_copy_tape(plan.tape))
+            front = Tape()
+            front.add("az_coef_c_time_f32", plan.t.data_ptr(), cur_coef.data_ptr())
+            front.add("az_scale_f32", plan.x_nchw.data_ptr() + 4 * half, plan.x_nchw.data_ptr(), _one(x.device).data_ptr(), half)
+            tape = copy_tape(plan.tape, front)
             tape.keep.append(plan)
 
             def prepare2(call_kwargs: dict, key: int) -> None:
@@ -133,14 +133,12 @@ class JITDenoiser(Denoiser):
             from .model import JiTPlan
 
             plan = JiTPlan(bb, B, True, x.device)
-            tape = Tape()
-            tape.add("az_coef_c_time_f32", plan.t.data_ptr(), cur_coef.data_ptr())
+            front = Tape()
+            front.add("az_coef_c_time_f32", plan.t.data_ptr(), cur_coef.data_ptr())
             if x_in is None:
                 x_in = plan.x_nchw
             else:  # later programs read the first one's input buffer
-                tape.add("az_scale_f32", plan.x_nchw.data_ptr(), x_in.data_ptr(), _one(x.device).data_ptr(), x_in.numel())
-            tape.extend(_copy_tape(plan.tape))
-            tape.keep.append(plan)
+                front.add("az_scale_f32", plan.x_nchw.data_ptr(), x_in.data_ptr(), _one(x.device).data_ptr(), x_in.numel())
 
             def prepare(call_kwargs: dict, plan=plan, key=i) -> None:
                 lab = call_kwargs.get("_az_labels", {}).get(key, call_kwargs.get("label"))
@@ -148,9 +146,7 @@ class JITDenoiser(Denoiser):
                     lab = torch.as_tensor(self.num_classes)
                 plan.labels.copy_(lab.to(device=plan.labels.device, dtype=torch.int64).expand(B))
 
-            programs.append(BackboneProgram(
-                tape=tape, x_in=x_in, x_in_cs=0, out=plan.out, f_channels=bb.out_channels, f_nhwc=False, prepare=prepare,
-            ))
+            programs.append(plan.program(bb.out_channels, front=front, x_in=x_in, prepare=prepare))
         return programs
 
     def _az_fused(self, x: Tensor, kwargs: dict, cur_coef: Tensor):

@@ -31,8 +31,9 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder, LinearView, PlanCache, SharedResidual, param_versions
-from ...gradplan import _GradTapes
+from ...engine import Act, LinearView, PlanCache, SharedResidual, param_versions
+from ...gradplan import _GradTapes, vjp_scope
+from ...plan import ForwardPlan
 
 __all__ = ["JiT", "JiTGradPlan", "JiT_models"]
 
@@ -282,20 +283,18 @@ def _emit_forward(plan, net: "JiT", B: int, t_shared: bool, x_nchw: Tensor, out_
                 joins=joins)
 
 
-class JiTPlan:
+class JiTPlan(ForwardPlan):
     r"""Compiled forward for one (batch, shared/per-sample time) signature."""
 
     def __init__(self, net: "JiT", B: int, t_shared: bool, device) -> None:
         # a network cast to half precision keeps its activations in HBM in its own type (engine.HALF_ACT): widths in multiples of 8,
         # SwiGLU through the GEMM's epilogue
         half_act = net.hidden_size % 8 == 0 and all((blk.mlp.w12.weight.shape[0] // 2) % 8 == 0 for blk in net.blocks) and net.hidden_size <= 4096
-        bld = self.bld = Builder(device, half=net.pos_embed.dtype, half_act=half_act)
+        super().__init__(device, half=net.pos_embed.dtype, half_act=half_act)
         Z, S = net.in_channels, net.input_size
-        self.x_nchw = torch.empty(B, Z, S, S, dtype=torch.float32, device=device)
         self.out = torch.empty(B, Z, S, S, dtype=torch.float32, device=device)
-        _emit_forward(self, net, B, t_shared, self.x_nchw, self.out)
-        bld.finish()
-        self.tape = bld.tape
+        _emit_forward(self, net, B, t_shared, self.nchw_input(B, Z, S, S), self.out)
+        self.end()
 
 
 class JiTGradPlan(_GradTapes):
@@ -487,10 +486,7 @@ class JiT(nn.Module):
         that ``azula.guidance`` takes from ``torch.autograd``, on HIP tapes (:class:`JiTGradPlan`).  ``t`` and ``y`` are constants
         of the pullback; it may be called any number of times until the next ``vjp`` with the same signature.  Scope: fp32
         parameters and fp32 device tensors; anything else raises ``NotImplementedError`` (the forward is not affected)."""
-        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
-            raise NotImplementedError("JiT.vjp: fp32 parameters and tensors only (half-precision modules have no input-gradient plan)")
-        if not x.is_cuda:
-            raise NotImplementedError("JiT.vjp: device tensors only (CPU tensors have no input-gradient path)")
+        vjp_scope(self, x, "JiT", "azula_amd.plugins.jit.JiT")
         self._check(x)
         t = t.reshape(-1)
         return self.grad_plan(x.shape[0], t.numel() == 1, x.device).run_jit(x.contiguous(), t, y)
@@ -510,11 +506,9 @@ class JiT(nn.Module):
         B = x.shape[0]
         t = t.reshape(-1)
         plan = self.plan(B, t.numel() == 1, x.device)
-        plan.x_nchw.copy_(x)
         plan.t.copy_(t.to(device=x.device, dtype=torch.float32))
         plan.labels.copy_(y.to(device=x.device, dtype=torch.int64).expand(B))
-        plan.tape.run()
-        return plan.out.to(out_dtype, copy=True)
+        return plan.run(x, out_dtype=out_dtype)
 
 
 _ARCH = {  # name: (depth, hidden, heads, bottleneck, context start, patch)   (_src/model.py:384-457)

@@ -82,9 +82,6 @@ class VelocityDenoiser(Denoiser):
     def _az_programs(self, x: Tensor, kwargs_list: list[dict], cur_coef: Tensor):
         r"""One compiled backbone program: the transition kernel leaves ``c_in' x_s`` in channels 0..2 of the stem's NHWC input,
         the program's first launch fills the time planes from the current step's ``c_time``."""
-        from ...nn.unet import _copy_tape
-        from ...sample import BackboneProgram
-
         bb = self.backbone
         if not isinstance(bb, VDMModel) or x.ndim != 4 or x.shape[1] != 3 or get_module_dtype(bb) != torch.float32:
             return None
@@ -94,10 +91,7 @@ class VelocityDenoiser(Denoiser):
         plan = bb.plan(B, H, W, x.device, coef_ptr=cur_coef.data_ptr())
         # wide = True: under an fp64 clock the loop converts the fp64 latent into this fp32 input itself and still fills the
         # fp32 coefficient row the time planes read
-        prog = BackboneProgram(tape=_copy_tape(plan.tape), x_in=plan.x_in.buf, x_in_cs=plan.x_in.cs, out=plan.out,
-                               f_channels=bb.out_channels, f_nhwc=False, wide=True)
-        prog.tape.keep.append(plan)
-        return [prog]
+        return [plan.program(bb.out_channels, wide=True)]
 
     def _az_fused(self, x: Tensor, kwargs: dict, cur_coef: Tensor):
         from ...sample import FusedDenoiser

@@ -27,7 +27,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from ... import _lib, engine
-from ...engine import Act, Builder, PlanCache
+from ...engine import Act, PlanCache
+from ...plan import ForwardPlan
 
 __all__ = ["ARCHITECTURES", "VDMModel", "VDMPlan", "ResConvBlock", "SelfAttention2d", "SkipBlock", "FourierFeatures"]
 
@@ -143,16 +144,16 @@ def _level_modules(a: dict, c: int) -> nn.Sequential:
 CONV_OVERRIDE: dict | None = None
 
 
-class VDMPlan:
+class VDMPlan(ForwardPlan):
     r"""Compiled forward of a ``nn.Sequential`` of ResConvBlock / SelfAttention2d / SkipBlock / AvgPool2d / Upsample modules for
     one (batch, H, W).  ``embed = (weight, mode)``: the input carries 3 image channels and the Fourier planes of the time in
     channels 3 .. 3 + 2 len(weight), written each run by ``az_fourier_planes_f32`` from ``t_ptr`` (stride ``t_stride``)."""
 
     def __init__(self, seq: nn.Sequential, B: int, H: int, W: int, cin: int, device, *, embed: tuple | None = None,
                  coef_ptr: int | None = None) -> None:
-        bld = self.bld = Builder(device)
-        cs = bld.pad(cin)
-        self.x_in = Act(torch.zeros(B * H * W * cs, dtype=torch.float32, device=device), B, H, W, cin, cs, True)
+        super().__init__(device)
+        bld = self.bld
+        cs = self.nhwc_input(B, H, W, cin).cs
         self.t = torch.zeros(B, dtype=torch.float32, device=device)
         if embed is not None:
             weight, mode = embed
@@ -262,17 +263,12 @@ class VDMPlan:
         assert up is None
         self.out = torch.empty(B, y.C, y.H, y.W, dtype=torch.float32, device=device)
         bld.tape.add("az_nhwc_to_nchw_f32", self.out.data_ptr(), y.ptr, B, y.C, y.H * y.W, y.cs, keep=[y.buf])
-        bld.finish()
-        self.tape = bld.tape
+        self.end()
 
     def __call__(self, x: Tensor, t: Tensor | None = None) -> Tensor:
-        B, Cin = x.shape[0], x.shape[1]
-        s = _lib.stream_ptr()
-        _lib.call("az_nchw_to_nhwc_f32", self.x_in.ptr, x.data_ptr(), None, B, Cin, x.shape[2] * x.shape[3], self.x_in.cs, s)
         if t is not None:
-            self.t.copy_(t.to(torch.float32).reshape(-1).expand(B))
-        self.tape.run(s)
-        return self.out.clone()
+            self.t.copy_(t.to(torch.float32).reshape(-1).expand(x.shape[0]))
+        return self.run(x)
 
 
 class VDMModel(nn.Module):
@@ -324,7 +320,6 @@ class VDMModel(nn.Module):
         backbone_io_dtype(self, x, "azula_amd VDM backbone")
         if x.ndim != 4 or x.shape[1] != 3:
             raise ValueError(f"vdm {self.model}: expected a (B, 3, H, W) input, got {tuple(x.shape)}")
-        x = x.to(torch.float32).contiguous()
         B, _, H, W = x.shape
         t = torch.as_tensor(t, device=x.device).reshape(-1)
         assert t.numel() in (1, B), "t: a scalar or one time per sample"

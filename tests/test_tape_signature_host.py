@@ -87,7 +87,7 @@ def test_temporaries_swapping_pool_buffers_differ():
 
 
 def test_case_groups_selectable_with_only():
-    assert list(ts.CASES) == ["unet", "adm", "dit", "jit", "samplers"] and all(callable(f) for f in ts.CASES.values())
+    assert list(ts.CASES) == ["unet", "adm", "dit", "jit", "samplers", "vdm", "unet3d", "vit.fused"] and all(callable(f) for f in ts.CASES.values())
 
 
 def test_unknown_address_gets_an_ordinal_of_its_own():

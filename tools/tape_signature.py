@@ -9,7 +9,7 @@ no known allocation gets an ordinal of its own (``["?", n, 0]``) by first appear
 are addresses; no size on the plans of this package reaches that.  What a kernel reads through a table on the device (the
 descriptors of ``az_linear_small_grouped_f32``) is not on the tape; the bit-equal outputs cover it.
 
-    python tools/tape_signature.py run DIR [--only unet,adm,dit,jit,samplers]    # builds the plans below, writes signatures + outputs
+    python tools/tape_signature.py run DIR [--only unet,adm,dit,jit,samplers,vdm,unet3d,vit.fused]    # builds the plans below, writes signatures + outputs
     python tools/tape_signature.py compare DIR_A DIR_B                  # equal signatures?  bit-equal outputs?
 """
 
@@ -129,16 +129,30 @@ def tensors_of(*roots) -> list:
     return found
 
 
+def _allocator_blocks() -> list:
+    r"""``(address, bytes)`` of every block of torch's caching allocator: each tensor allocation is one block, at its address."""
+    import torch
+
+    out = []
+    for seg in torch.cuda.memory_snapshot():
+        at = seg["address"]
+        for blk in seg["blocks"]:
+            out.append((at, blk["size"]))
+            at += blk["size"]
+    return out
+
+
 def plan_record(plan, module=None) -> dict:
     r"""Signatures of one plan: a forward plan (``.tape``, or a standalone block's tuple), or a gradient plan (``.fwd``, ``.bwd``)."""
     tapes = {}
-    if isinstance(plan, tuple):  # UNetBlock's one-block plans: (x_in, mod, tape, out)
+    allocs = tensors_of(plan, module, getattr(plan, "roots", None))
+    if isinstance(plan, tuple):  # UNetBlock's one-block plans on older checkouts: (x_in, mod, tape, out)
         tapes["tape"] = plan[2]
+        allocs = allocs + _allocator_blocks()  # (a tuple does not expose its pool: the temporaries are the allocator's own blocks)
     elif hasattr(plan, "fwd"):
         tapes["fwd"], tapes["bwd"] = plan.fwd, plan.bwd
     else:
         tapes["tape"] = plan.tape
-    allocs = tensors_of(plan, module, getattr(plan, "roots", None))
     pool = getattr(getattr(plan, "bld", None), "pool", None)
     pool_starts = {t.untyped_storage().data_ptr() for t in pool.all} if pool is not None else set()
     rec = {}
@@ -408,7 +422,84 @@ def sampler_cases(rec: Recorder) -> None:
             rec.save(f"samplers.{name}.{clock}", den, {"x0": x0.view(torch.float32)}, plans=plans)
 
 
-CASES = {"unet": unet_cases, "adm": adm_cases, "dit": dit_cases, "jit": jit_cases, "samplers": sampler_cases}
+def _two_step_loop(rec: Recorder, case: str, den, backbone, x1) -> None:
+    r"""A two-step DDIM sample on the captured loop: every plan the backbone holds afterwards (the sampler's own among them) and
+    every step tape."""
+    import torch
+
+    from azula_amd.sample import DDIMSampler
+
+    smp = DDIMSampler(den, steps=2, silent=True)
+    torch.manual_seed(44)
+    x0 = smp(x1)
+    loop = next(iter(smp._fused_cache.values()), None)
+    assert hasattr(loop, "step_tapes"), f"{case}: the sampler did not take the captured loop"
+    plans = dict(backbone._plans)
+    roots = [loop, *plans.values()]
+    plans.update({f"step{j}": _LoopTape(t, roots) for j, t in enumerate(loop.step_tapes)})
+    rec.save(case, backbone, {"x0": x0}, plans=plans)
+
+
+def vdm_cases(rec: Recorder) -> None:
+    r"""Narrow v-diffusion backbones: ``skip_main`` concatenation with nearest up-sampling (imagenet_128, five poolings: 32 x 32)
+    and ``main_skip`` with bilinear up-sampling (yfcc_1, seven poolings: 128 x 128 is its smallest map), then the ``coef_ptr`` plan
+    of the first under a two-step sampler."""
+    import torch
+
+    from azula_amd.plugins.vdm import VelocityDenoiser
+    from azula_amd.plugins.vdm.model import VDMModel
+
+    gen = torch.Generator().manual_seed(61)
+    for name, model, c, shape in (("nearest", "imagenet_128", 32, (2, 3, 32, 32)), ("bilinear", "yfcc_1", 16, (1, 3, 128, 128))):
+        torch.manual_seed(62)
+        net = VDMModel(model, base_channels=c)
+        _randomise(net, 63)
+        net = net.cuda().eval()
+        x = torch.randn(shape, generator=gen).cuda()
+        rec.save("vdm." + name, net, {"y": net(x, torch.tensor([0.3, 0.8][: shape[0]]).cuda())})
+        if name == "nearest":
+            net._plans.clear()
+            _two_step_loop(rec, "vdm.fused_loop", VelocityDenoiser(net).cuda().eval(), net, x)
+
+
+def _time_modulated(net, name: str):
+    from azula_amd.denoise import KarrasDenoiser
+    from azula_amd.nn import TimeModulated
+    from azula_amd.noise import VPSchedule
+
+    _randomise(net, 73)
+    return KarrasDenoiser(TimeModulated(net, 16, name=name), VPSchedule()).cuda().eval()
+
+
+def unet3d_cases(rec: Recorder) -> None:
+    import torch
+
+    from azula_amd.nn import UNet
+
+    gen = torch.Generator().manual_seed(71)
+    torch.manual_seed(72)
+    net = UNet(3, 3, hid_channels=(8, 16), hid_blocks=(1, 1), norm="group", groups=4, mod_features=16, spatial=3)
+    den = _time_modulated(net, "unet")
+    x, mod = torch.randn(1, 3, 4, 8, 8, generator=gen).cuda(), torch.randn(1, 16, generator=gen).cuda()
+    rec.save("unet3d.forward", net, {"y": net(x, mod)})
+    net._plans.clear()
+    _two_step_loop(rec, "unet3d.fused_loop", den, net, x)
+
+
+def vit_fused_cases(rec: Recorder) -> None:
+    import torch
+
+    from azula_amd.nn import ViT
+
+    gen = torch.Generator().manual_seed(81)
+    torch.manual_seed(82)
+    net = ViT(3, 3, hid_channels=64, hid_blocks=2, attention_heads=4, patch_size=4, mod_features=16)
+    den = _time_modulated(net, "vit")
+    _two_step_loop(rec, "vit.fused", den, net, torch.randn(2, 3, 16, 16, generator=gen).cuda())
+
+
+CASES = {"unet": unet_cases, "adm": adm_cases, "dit": dit_cases, "jit": jit_cases, "samplers": sampler_cases, "vdm": vdm_cases,
+         "unet3d": unet3d_cases, "vit.fused": vit_fused_cases}
 
 
 def run(out_dir: str, only: list[str]) -> None:
